@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: YOLOv9-C 640x640 frames/s on MI355X (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of the detect hot path (letterbox -> 144 convs -> decode -> top-300 + mask NMS)
 over one batch of 64 synthetic 640x640 BGR uint8 frames that are already resident in HBM.  The headline storage mode is
@@ -569,7 +569,12 @@ def main() -> None:
     ap.add_argument("--no-clip", action="store_true", help="skip the CLIP / search side metrics")
     ap.add_argument("--no-streams", action="store_true", help="skip the camera-pipeline side metrics (detect -> OC-SORT incl. PCIe)")
     ap.add_argument("--no-precisions", action="store_true", help="skip the f16 / f32 throughput legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections of the last timed step ((batch, 300, 6) float32 rows, what cc_yolo_submit / cc_yolo_detect return) "
+                         "as DIR/detections.npy (DIR/detections_rank<r>.npy on rank r > 0); inputs are seeded, so two builds compare row for row")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -643,6 +648,15 @@ def main() -> None:
     # hardware queues and two slots on one queue would not overlap)
     model_p = in_flight_model(args.dtype)
     elapsed = timed(model_p, args.steps, args.warmup, depth)
+    if args.dump_outputs:
+        # step k of the timed loop wrote outs[k % depth]; copied now, before the later legs reuse the buffers.  At most 64 MB: the
+        # leading frames of a larger batch
+        det = outs[(args.steps - 1) % depth].cpu().numpy()
+        det = det[:max(1, (64 << 20) // det[0].nbytes)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        path = os.path.join(args.dump_outputs, "detections.npy" if rank == 0 else f"detections_rank{rank}.npy")
+        np.save(path, det)
+        print(f"bench: wrote {path} {det.shape} {det.dtype}", file=sys.stderr, flush=True)
     model = YOLOv9(args.size, args.res, state_dict=sd, dtype=args.dtype, device=local) if depth > 1 else model_p
     elapsed_one = timed(model, args.steps, args.warmup, 1) if depth > 1 else elapsed
     # What the collective backend actually saw: an all-reduce of ones (= the number of ranks that took part) and every rank's own

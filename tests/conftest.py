@@ -4,11 +4,6 @@ import sys
 import numpy as np
 import pytest
 
-# the BPE vocabulary is clearcam's own data file; in the build container the reference checkout has it (test infrastructure only)
-_REF_VOCAB = "/root/reference/utils/bpe_simple_vocab_16e6.txt.gz"
-if os.path.exists(_REF_VOCAB):
-    os.environ.setdefault("CLEARCAM_BPE_VOCAB", _REF_VOCAB)
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -60,8 +55,18 @@ def noise_frames(seed, b, h, w, dtype=np.uint8):
 
 def sparse_tokenizer():
     """SimpleTokenizer over tests/golden/bpe_merges_subset.json: the merges (published ranks) that the strings of
-    tokenizer_kats.json can look up, so the string surface is testable where clearcam's vocabulary file is absent."""
+    tokenizer_kats.json and the queries of refrun_clip_l14.npz can look up, so the string surface is testable where clearcam's
+    vocabulary file is absent."""
     import json
     from clearcam_amd.clip_tokenizer import SimpleTokenizer
     sub = json.load(open(os.path.join(ROOT, "tests", "golden", "bpe_merges_subset.json")))["merges"]
     return SimpleTokenizer(sparse_merges={tuple(k.split(" ")): r for k, r in sub.items()})
+
+
+def vocab_tokenizer():
+    """SimpleTokenizer over clearcam's vocabulary file where one is found ($CLEARCAM_BPE_VOCAB, ...), else sparse_tokenizer()."""
+    from clearcam_amd.clip_tokenizer import SimpleTokenizer, find_vocab
+    try:
+        return SimpleTokenizer(find_vocab())
+    except FileNotFoundError:
+        return sparse_tokenizer()

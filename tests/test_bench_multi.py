@@ -5,17 +5,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(world, port, extra_env=None):
+def run_bench(world, port, extra_env=None, extra_args=()):
     env = dict(os.environ, **(extra_env or {}))
     env.pop("CLEARCAM_BENCH_FORCE_SHARDED", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "tests", "helpers", "bench_mock_driver.py"),
-           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--res", "64"]
+           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--res", "64", *extra_args]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -56,6 +57,16 @@ def test_single_rank_line_is_short_and_carries_roofline_and_cpu_baseline():
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(line["roofline"])
     assert {"value", "unit", "cores", "kind", "sample"} <= set(line["cpu_baseline"]) and line["cpu_baseline"]["kind"] == "port"
     assert "workload" in line["config"] and "model" not in line["config"]
+
+
+def test_dump_outputs_holds_the_last_timed_step_of_every_rank(tmp_path):
+    run_bench(2, 29647, extra_args=("--dump-outputs", str(tmp_path), "--no-streams", "--no-clip"))
+    assert sorted(os.listdir(tmp_path)) == ["detections.npy", "detections_rank1.npy"]
+    for name in ("detections.npy", "detections_rank1.npy"):
+        det = np.load(tmp_path / name)
+        assert det.dtype == np.float32 and det.shape == (4, 300, 6)
+        # the double stamps its call count: 3 slots built (--in-flight 3) + 1 warm-up + 3 timed steps -> the dump is the 7th call
+        assert (det[:, 0, 0] == 7).all() and (det[:, :3, 4] == 0.5).all()
 
 
 def test_a_failing_side_metric_on_one_rank_does_not_hang_or_kill_the_line():

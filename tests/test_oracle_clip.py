@@ -12,15 +12,6 @@ from oracle.clip_oracle import OpenCLIPOracle, pad_tokens, search_reference
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def _vocab_available():
-    from clearcam_amd.clip_tokenizer import find_vocab
-    try:
-        find_vocab()
-        return True
-    except FileNotFoundError:
-        return False
-
-
 def test_clip_structure_pins():
     s = clip_shapes(CLIP_L14)
     assert s["visual_conv1.weight"] == (1024, 3, 14, 14) and s["positional_embedding"] == (257, 1024)
@@ -45,11 +36,10 @@ def test_reference_golden_embeddings_are_consistent():
     assert pins["text_image_cosine_ferrari_f40"] == 0.330654
 
 
-@pytest.mark.skipif(not _vocab_available(), reason="bpe_simple_vocab_16e6.txt.gz not available")
 def test_tokenizer_matches_reference_ids():
-    from clearcam_amd.clip_tokenizer import SimpleTokenizer
+    from conftest import vocab_tokenizer
     k = json.load(open(os.path.join(GOLD, "tokenizer_kats.json")))
-    t = SimpleTokenizer()
+    t = vocab_tokenizer()
     assert (t.vocab_size, t.sot_token_id, t.eot_token_id) == (k["vocab_size"], k["sot"], k["eot"]) == (49408, 49406, 49407)
     for c in k["cases"]:
         assert t.encode(c["text"]) == c["ids"], c["text"]

@@ -66,14 +66,10 @@ def test_clip_oracle_equals_reference_run():
 
 def test_clip_tokens_of_the_reference_run():
     """The token rows in the fixture were produced by the reference's tokenizer inside the run; ours must give the same ids."""
-    from clearcam_amd.clip_tokenizer import SimpleTokenizer, find_vocab
+    from conftest import vocab_tokenizer
     from oracle.clip_oracle import pad_tokens
-    try:
-        find_vocab()
-    except FileNotFoundError:
-        pytest.skip("vocab file not on this box")
     g = np.load(os.path.join(GOLD, "refrun_clip_l14.npz"))
-    tok = SimpleTokenizer()
+    tok = vocab_tokenizer()
     for q, row in zip(g["queries"], g["tokens"]):
         assert np.array_equal(pad_tokens(tok.encode(str(q)))[0], row)
 
