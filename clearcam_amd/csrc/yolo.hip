@@ -1493,16 +1493,19 @@ int cc_yolo_wait(cc_yolo* h, long long ticket, void* stream) {
   CC_API_END
 }
 
-int cc_yolo_get_tensor(cc_yolo* h, const char* name, float* out, int64_t* shape, int* ndim) {
+// frames [b0, b0 + nb) of a tap; nb < 0: every frame
+static int get_tensor_frames(cc_yolo* h, const char* name, int b0, int nb, float* out, int64_t* shape, int* ndim) {
   CC_API_BEGIN
   CC_CHECK(h && name && shape && ndim, "null argument");
   CC_CHECK(h->last, "no detect call yet");
   Plan* P = h->last;
+  if (nb < 0) { b0 = 0; nb = P->B; }
+  CC_CHECK(b0 >= 0 && nb >= 1 && b0 < P->B && nb <= P->B - b0, "frame range outside [0, B)");
   CC_HIP(hipSetDevice(h->device));
   sync_all(h);
   if (!strcmp(name, "decoded")) {
-    shape[0] = P->B; shape[1] = P->A; shape[2] = 6; *ndim = 3;
-    if (out) CC_HIP(hipMemcpy(out, P->det, (size_t)P->B * P->A * 24, hipMemcpyDeviceToHost));
+    shape[0] = nb; shape[1] = P->A; shape[2] = 6; *ndim = 3;
+    if (out) CC_HIP(hipMemcpy(out, P->det + (size_t)b0 * P->A * 6, (size_t)nb * P->A * 24, hipMemcpyDeviceToHost));
     return 0;
   }
   auto it = P->taps.find(name);
@@ -1517,13 +1520,14 @@ int cc_yolo_get_tensor(cc_yolo* h, const char* name, float* out, int64_t* shape,
     CC_HIP(hipStreamSynchronize(h->stream));
   }
   const int C = !strcmp(name, "input") ? 3 : b.C;
-  shape[0] = P->B; shape[1] = b.H; shape[2] = b.W; shape[3] = C; *ndim = 4;
+  shape[0] = nb; shape[1] = b.H; shape[2] = b.W; shape[3] = C; *ndim = 4;
   if (!out) return 0;
-  const size_t n = (size_t)P->B * b.H * b.W * b.C;
+  const size_t frame = (size_t)b.H * b.W * b.C;
+  const size_t n = (size_t)nb * frame;
   const size_t es = b.f32 ? 4 : dtype_size(h->dtype);
   std::vector<char> tmp(n * es);
-  CC_HIP(hipMemcpy(tmp.data(), P->arena + b.off, n * es, hipMemcpyDeviceToHost));
-  const size_t px = (size_t)P->B * b.H * b.W;
+  CC_HIP(hipMemcpy(tmp.data(), P->arena + b.off + (size_t)b0 * frame * es, n * es, hipMemcpyDeviceToHost));
+  const size_t px = (size_t)nb * b.H * b.W;
   for (size_t i = 0; i < px; ++i)
     for (int c = 0; c < C; ++c) {
       const size_t j = i * b.C + c;
@@ -1534,6 +1538,15 @@ int cc_yolo_get_tensor(cc_yolo* h, const char* name, float* out, int64_t* shape,
       out[i * C + c] = v;
     }
   CC_API_END
+}
+
+int cc_yolo_get_tensor(cc_yolo* h, const char* name, float* out, int64_t* shape, int* ndim) {
+  return get_tensor_frames(h, name, 0, -1, out, shape, ndim);
+}
+
+int cc_yolo_get_tensor_frames(cc_yolo* h, const char* name, int b0, int nb, float* out, int64_t* shape, int* ndim) {
+  if (nb < 0) nb = 0;                                        // a negative count is a bad range here, not "every frame"
+  return get_tensor_frames(h, name, b0, nb, out, shape, ndim);
 }
 
 int cc_yolo_nonfinite(cc_yolo* h, int* count) {

@@ -156,12 +156,19 @@ class YOLOv9:
         _lib.check(_lib.lib().cc_yolo_wait(self._h, ticket, s))
 
     # -- parity taps --------------------------------------------------------------------------------
-    def get_tensor(self, name: str) -> np.ndarray:
+    def get_tensor(self, name: str, frames=None) -> np.ndarray:
+        """A named intermediate of the last detect call as float32 (include/clearcam_hip.h lists the names); frames = (b0, nb): only
+        frames [b0, b0 + nb) are copied (CCError if the range leaves [0, B))."""
         L = _lib.lib()
         shp, nd = (C.c_int64 * 4)(), C.c_int()
-        _lib.check(L.cc_yolo_get_tensor(self._h, name.encode(), None, shp, C.byref(nd)))
+        if frames is None:
+            get = lambda out: L.cc_yolo_get_tensor(self._h, name.encode(), out, shp, C.byref(nd))                          # noqa: E731
+        else:
+            b0, nb = (int(v) for v in frames)
+            get = lambda out: L.cc_yolo_get_tensor_frames(self._h, name.encode(), b0, nb, out, shp, C.byref(nd))           # noqa: E731
+        _lib.check(get(None))
         out = np.empty(tuple(shp[i] for i in range(nd.value)), np.float32)
-        _lib.check(L.cc_yolo_get_tensor(self._h, name.encode(), _lib.ptr(out), shp, C.byref(nd)))
+        _lib.check(get(_lib.ptr(out)))
         return out
 
     def nonfinite(self) -> int:

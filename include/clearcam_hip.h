@@ -96,6 +96,9 @@ int cc_yolo_wait(cc_yolo* h, long long ticket, void* stream);
  * re-runs that kernel: for both, device frames handed to the last cc_yolo_detect call must still be alive (host frames are
  * staged in a buffer the handle owns). */
 int cc_yolo_get_tensor(cc_yolo* h, const char* name, float* out, int64_t* shape, int* ndim);
+/* The same for frames [b0, b0 + nb) only: shape[0] = nb, and only those frames are copied and converted (a tap of a B = 64 plan can
+ * be several GB as float32).  A range outside [0, B) is an error.  "decoded" and "input" behave as in cc_yolo_get_tensor. */
+int cc_yolo_get_tensor_frames(cc_yolo* h, const char* name, int b0, int nb, float* out, int64_t* shape, int* ndim);
 /* GPU milliseconds of the last detect call's kernels (hipEvents on the launch stream). */
 int cc_yolo_last_gpu_ms(cc_yolo* h, float* ms);
 /* Eager replay of the last plan's launch list, `iters` times, with a hipEvent pair around every launch

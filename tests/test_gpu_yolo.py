@@ -1049,10 +1049,17 @@ frames = np.random.default_rng(5).integers(0, 256, (B, H, W, 3), dtype=np.uint8)
 sd = conditioned_yolov9_state_dict(size, 1234) if size == "c" else synthetic_yolov9_state_dict(size, 1234)
 m = YOLOv9(size, res, state_dict=sd, dtype=dtype, device=0)
 d = {"det": m.detect_batch(frames)}
+def grab(n):                                             # B > 16: a digest of every frame (several GB as float32) + the last two frames
+    if B <= 16: return m.get_tensor(n)
+    import hashlib
+    h = hashlib.sha256()
+    for b0 in range(0, B, 8): h.update(m.get_tensor(n, (b0, min(8, B - b0))).tobytes())
+    d[n + "_last"] = m.get_tensor(n, (B - 2, 2))
+    return np.frombuffer(h.digest(), np.uint8)
 for k in range(16):
-    try: d[f"csp{k}_u"] = m.get_tensor(f"csp{k}_u")
+    try: d[f"csp{k}_u"] = grab(f"csp{k}_u")
     except Exception: pass
-for n in ("p3", "p4", "p5"): d[n] = m.get_tensor(n)
+for n in ("p3", "p4", "p5"): d[n] = grab(n)
 d["launches"] = np.array(m.profile(iters=1)["conv_launches"])
 np.savez(out, **d)
 """
@@ -1078,6 +1085,7 @@ np.savez(out, **d)
     ("c", 608, "f16h", 608, 608, 2, "2", 6),      # ... ragged tiles
     ("c", 640, "f16h", 640, 640, 11, "2", 2),     # round 6: from one round of conv_tile64's tiles on (25 per frame at 80 x 80: B >= 11) level 2 leaves hidden width 64 to the four launches ...
     ("c", 640, "f16h", 640, 640, 11, "3", 6),     # ... level 3 fuses it at every batch size
+    ("c", 640, "f16h", 640, 640, 64, "2", 2),     # the bench batch: csp_tile_kernel at 160 x 160 (1600 tiles), hidden width 64 left to the four launches
 ])
 def test_fused_csp_equals_unfused(tmp_path, size, res, dtype, H, W, B, level, fused):
     """csp_fused_kernel (cv1|cv2, RepConvN 3x3, 3x3 + shortcut, cv3 of a RepNCSP in one launch, intermediates in LDS) against the
@@ -1098,7 +1106,8 @@ def test_fused_csp_equals_unfused(tmp_path, size, res, dtype, H, W, B, level, fu
     assert len(names) >= fused
     for n in names + ["p3", "p4", "p5", "det"]:
         assert np.array_equal(a[n], b[n]), n
-    assert np.abs(a["p3"]).max() > 0.05 and np.isfinite(a["p3"]).all()
+    p3 = a["p3_last"] if "p3_last" in a.files else a["p3"]
+    assert np.abs(p3).max() > 0.05 and np.isfinite(p3).all()
 
 
 def test_tile64_in_the_detector_same_bits(tmp_path):

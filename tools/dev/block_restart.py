@@ -1,6 +1,7 @@
 # dev tool (GPU): every block of the 16-bit path recomputed on the CPU FROM THE GPU'S OWN INPUTS to that block (exact float32 weights, f32
 # accumulation, f16 rounding where the kernels round - oracle/lowprec_oracle.py) and compared with the GPU's output of the block: a faithful
 # kernel differs only where an f32 sum lands within accumulation-order noise of a rounding boundary (~1 % of the elements, by one ulp).
+# The committed form of this check, at the bench configuration against a float64 reference: tests/test_gpu_plan_restart.py.
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ["CLEARCAM_TAP_BLOCKS"] = "1"

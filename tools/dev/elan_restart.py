@@ -1,4 +1,5 @@
 # dev tool (GPU): block_restart.py inside ONE RepNCSPELAN4 (block 6 = the third one: cat2, csp4, csp5), conv by conv
+# The committed form of this check, at the bench configuration against a float64 reference: tests/test_gpu_plan_restart.py.
 import os, sys, numpy as np, torch, torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ["CLEARCAM_TAP_BLOCKS"] = "1"; os.environ["CLEARCAM_TAP_CSP"] = "1"; os.environ["CLEARCAM_FUSE_CSP"] = "0"
