@@ -471,10 +471,7 @@ __global__ __launch_bounds__(256) void attn_simple_kernel(const AttnP p) {
 
 template <class T, int NF, int NFK, int LFULL = -1, int CAUSAL = -1, int NQ = 1> static void launch_attn_mfma(const AttnP& p, hipStream_t stream) {
   const size_t lds = std::max((size_t)NFK * 16 * 128, (size_t)(4 * 4 * 64 * 4 + 4 * 16 * 2) * 4) + (size_t)NF * 16 * 80 * sizeof(T);
-  static PerDevice once;                               // the attribute is per device (common.h)
-  if (once.first(once.index())) {
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_kernel<T, NF, NFK, LFULL, CAUSAL, NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
+  ensure_max_lds(attn_mfma_kernel<T, NF, NFK, LFULL, CAUSAL, NQ>, lds);
   if (p.abl & 64) {                                    // development: how many blocks share a CU
     int nb = 0; CC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(attn_mfma_kernel<T, NF, NFK, LFULL, CAUSAL, NQ>), 256, lds));
     fprintf(stderr, "[clearcam] attn_mfma_kernel<NF=%d, NFK=%d, LFULL=%d>: %zu bytes of LDS, %d blocks per CU\n", NF, NFK, LFULL, lds, nb);

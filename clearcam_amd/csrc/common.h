@@ -3,8 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include <map>
 #include <memory>
+#include <mutex>
+#include <set>
+#include <utility>
 #include <cstdlib>
 #include <string>
 #include <stdexcept>
@@ -125,24 +129,36 @@ struct ConvP {
   // from HBM unchanged.  Ktot = 2 ks^2 Cin.  oscale = 2^-e undoes the per-layer power-of-two scale that keeps W_lo a NORMAL f16
   // number (exact: the epilogue computes fma(acc, oscale, bias)).  split = 0: oscale is ignored (taken as 1).
   int split; float oscale;
-  int variant;                   // kernel choice: 0 auto; tests force 1 direct, 2 generic MFMA, 3 halo-resident 3x3, 4 weights-stationary 3x3, 5 single-barrier schedule with 256x256 tiles, 6 the same with 128x128 tiles, 7 eight-wave two-group 256x256 kernel, 8 wave-autonomous narrow 3x3, 9 few-tile configuration (narrow channel tiles, 3-4 LDS stages), 10 weights-resident streaming 1x1 (conv_stream.hip)
+  int variant;                   // kernel choice: 0 auto, else a forced kernel (ConvVariant, conv_select.h)
 };
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count are per DEVICE: a launcher's one-time set-up is keyed by the current
-// device ordinal (a process may hold handles on several GPUs), not by a process-wide flag.
-struct PerDevice {
-  bool done[64] = {}; int cus[64] = {};
-  int index() const { int d = 0; if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = -1; return d; }
-  // true once per device (always true for an ordinal outside the table: the set-up is idempotent)
-  bool first(int d) { if (d < 0) return true; const bool f = !done[d]; done[d] = true; return f; }
-  int cu_count(int d) {
-    if (d >= 0 && cus[d]) return cus[d];
-    int dev = 0; hipDeviceProp_t pr;
-    CC_HIP(hipGetDevice(&dev)); CC_HIP(hipGetDeviceProperties(&pr, dev));
-    if (d >= 0) cus[d] = pr.multiProcessorCount;
-    return pr.multiProcessorCount;
-  }
-};
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per (kernel, DEVICE): a process may hold handles on several GPUs and launch from
+// several host threads.  Sets it on the current device the first time, under a lock, so that no thread launches the kernel there before it
+// is set; a failed call is not remembered and throws.
+inline void ensure_max_lds(const void* kernel, size_t bytes) {
+  static std::mutex m;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  CC_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(m);
+  if (done.count({kernel, dev})) return;
+  CC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  done.insert({kernel, dev});
+}
+template <class K> inline void ensure_max_lds(K* kernel, size_t bytes) { ensure_max_lds(reinterpret_cast<const void*>(kernel), bytes); }
+
+// CU count of the current device, cached per device ordinal (hipGetDeviceProperties is not cheap)
+inline int cu_count() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  CC_HIP(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < 64;
+  if (cached) { const int n = cus[dev].load(std::memory_order_relaxed); if (n) return n; }
+  hipDeviceProp_t pr;
+  CC_HIP(hipGetDeviceProperties(&pr, dev));
+  if (cached) cus[dev].store(pr.multiProcessorCount, std::memory_order_relaxed);
+  return pr.multiProcessorCount;
+}
 
 // Plan cache of a model handle: one plan (buffers + captured hipGraph) per input shape, bounded.  A service that sees many
 // batch sizes would otherwise keep a multi-GB arena for each of them forever.  At most cap() plans live at once

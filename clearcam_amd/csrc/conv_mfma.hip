@@ -27,11 +27,11 @@
 //   neighbouring pixel tiles run on one XCD's L2.
 // * f32 mode uses v_mfma_f32_16x16x4_f32 (exact f32) with the k-slots of a 16-B chunk spread over 4 MFMAs.
 //
-// Kernels in this file, chosen per layer by launch_t():
+// Kernels in this file (choose_conv() below decides which kernel, here or in the other conv_*.hip files, runs a layer):
 //   conv_mfma_kernel     the generic one described above (every shape, every dtype)
-//   conv_big_kernel      256x256 tile / 4 waves / one barrier per K step, for deep GEMM-shaped 16-bit layers
-//   conv3x3_halo_kernel  3x3 s1 with the input patch resident in LDS across the nine taps (128/256-channel layers)
+//   conv_big_kernel      256x256 or 128x128 tile / 4 waves / one barrier per K step, for deep GEMM-shaped 16-bit layers
 //   conv3x3_ws_kernel    3x3 s1 for narrow layers: persistent blocks, all nine taps of the weights resident in LDS
+#include "conv_select.h"
 #include "conv_tile.h"
 
 namespace cc {
@@ -394,130 +394,6 @@ __global__ __launch_bounds__(256, (TS == 256 ? 1 : 2)) void conv_big_kernel(cons
   conv_epilogue<T, BM, BN, WM, MI, NJ, NT>(p, acc, n0, lds, [&](int row) { const int m = m0 + row; return m < M ? (long)m : -1L; });
 }
 
-// ---- 3x3 stride-1 convolution with the input halo tile resident in LDS ---------------------------------------------------
-// The implicit GEMM above stages a fresh 128-pixel x 64-channel slab for each of the nine taps: nine times the input bytes
-// through L2 -> LDS.  Bytes in flight per CU are capped by LDS capacity, so for the narrow layers (64..128 channels, where
-// the weight slab is small and the input slab dominates) that inflated traffic, not the MFMAs, sets the pace.
-// Here an output tile is 8 rows x 16 pixels and its 10 x 18 input patch (64 channels = one 128-byte row per pixel, same
-// chunk swizzle) is loaded ONCE per 64-channel slab; the nine taps read shifted windows of it (16 consecutive patch rows
-// at any offset still hit 16 distinct bank groups).  K order is (channel slab, tap) instead of (tap, channel slab).
-// Per K step only the BN x 64 weight slab streams in; pieces of the next slab's patch ride along in the first six taps.
-struct HaloAux { float inv_tiles, inv_tx; int tiles, tx, nt; };
-
-template <class T, int BN>
-__global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvP p, const HaloAux a) {
-  constexpr int BM = 128, WM = 2, WN = 2, MI = 4, NJ = BN / WN / 16;
-  constexpr int PW = 18, PROWS = 184;                  // 10 x 18 = 180 patch pixels, padded to whole 8-row DMA groups
-  constexpr int XP = PROWS * 8, WS = BN * 8;           // uint4 per patch buffer / weight stage
-  constexpr int WR = BN / 32;                          // weight rows per thread per step
-  static_assert(sizeof(T) == 2, "16-bit storage only");
-  static_assert(2 * XP * 16 >= BM * BN * 2, "epilogue tile must fit in the patch buffers");
-  extern __shared__ __attribute__((aligned(16))) uint4 lds[];   // [2][XP] patches, then [2][WS] weight stages
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned lds_base = lds_addr(lds);
-
-  int wg;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int mt = wg / a.nt, n0 = (wg - mt * a.nt) * BN;
-  const int b = fdiv(mt, a.tiles, a.inv_tiles), trem = mt - b * a.tiles, ty = fdiv(trem, a.tx, a.inv_tx), tx = trem - ty * a.tx;
-  const int h0 = ty * 8, w0 = tx * 16;
-
-  // ---- loaders: thread -> (row within an 8-row group, 16-byte position); source chunk = position ^ swizzle(row)
-  const int ppos = tid & 7, prow = tid >> 3;           // prow 0..31; rows prow + 32*i
-  const char* xcur[6];                                 // patch rows prow + 32*i, i < 6 (wave 3 has no i = 5: rows >= 184)
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const int pr = prow + 32 * i;
-    const int py = pr / PW, px = pr - py * PW;
-    const int ih = h0 - 1 + py, iw = w0 - 1 + px;
-    const bool ok = pr < 180 && (unsigned)ih < (unsigned)p.Hin && (unsigned)iw < (unsigned)p.Win;
-    const int chunk = ppos ^ swz<8>(pr);
-    xcur[i] = ok ? reinterpret_cast<const char*>(p.s0.ptr) +
-                       ((((long)b * p.s0.H + ih) * p.s0.W + iw) * (long)p.s0.cstride + p.s0.coff + chunk * 8) * (long)sizeof(T)
-                 : reinterpret_cast<const char*>(&g_zero16);
-  }
-  unsigned xinc[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) xinc[i] = xcur[i] == reinterpret_cast<const char*>(&g_zero16) ? 0u : 128u;
-  const char* wbase[WR];
-#pragma unroll
-  for (int i = 0; i < WR; ++i) {
-    const int row = prow + 32 * i, n = n0 + row;
-    const int chunk = ppos ^ swz<8>(row);
-    wbase[i] = n < p.Cout ? reinterpret_cast<const char*>(p.w) + ((size_t)n * p.Kw + chunk * 8) * sizeof(T) : nullptr;
-  }
-  auto issue_w = [&](int stage, int tap, int c0) {     // weight slab of (tap, channels c0..c0+63)
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(2 * XP + stage * WS + wave * 64) * 16u);
-    const long off = ((long)tap * p.Cin + c0) * (long)sizeof(T);
-#pragma unroll
-    for (int i = 0; i < WR; ++i)
-      glds16(wbase[i] ? static_cast<const void*>(wbase[i] + off) : static_cast<const void*>(&g_zero16), dst + i * (256 * 16u));
-  };
-  auto issue_x = [&](int buf, int i) {                 // 32 patch rows (one 8-row group per wave) of the current xcur slab
-    if (wave * 8 + 32 * i < PROWS) {
-      const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(buf * XP + (32 * i + wave * 8) * 8) * 16u);
-      glds16(xcur[i], dst);
-    }
-  };
-
-  const int wm = wave & 1, wn0 = (wave >> 1) * (BN / WN);
-  const int fr = lane & 15, fg = lane >> 4;
-  const int nch = p.Cin >> 6, nsteps = 9 * nch;
-
-  f32x4 acc[NJ][MI];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int i = 0; i < MI; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // prologue: patch of slab 0 and the first weight slab
-#pragma unroll
-  for (int i = 0; i < 6; ++i) issue_x(0, i);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) xcur[i] += xinc[i];
-  issue_w(0, 0, 0);
-
-  int ci = 0, tap = 0;
-  for (int t = 0; t < nsteps; ++t) {
-    wait_vmcnt<0>();
-    __syncthreads();                                   // step t's data landed for everyone; step t-1's buffers are free
-    {                                                  // stream the next weight slab and a piece of the next patch
-      int ntap = tap + 1, nci = ci;
-      if (ntap == 9) { ntap = 0; ++nci; }
-      if (t + 1 < nsteps) issue_w((t + 1) & 1, ntap, nci << 6);
-      if (tap < 6 && ci + 1 < nch) { issue_x((ci + 1) & 1, tap); xcur[tap] += xinc[tap]; }
-    }
-    const uint4* ldsX = lds + (ci & 1) * XP;
-    const uint4* ldsW = lds + 2 * XP + (t & 1) * WS;
-    const int r = tap / 3, sft = tap - r * 3;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      uint4 xf[MI], wf[NJ];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int row = (wm * 4 + i + r) * PW + fr + sft;
-        xf[i] = ldsX[row * 8 + ((h * 4 + fg) ^ swz<8>(row))];
-      }
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { const int row = wn0 + j * 16 + fr; wf[j] = ldsW[row * 8 + ((h * 4 + fg) ^ swz<8>(row))]; }
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int i = 0; i < MI; ++i) Mma<T>::run(wf[j], xf[i], acc[j][i]);
-    }
-    if (++tap == 9) { tap = 0; ++ci; }
-  }
-
-  conv_epilogue<T, BM, BN, WM, MI, NJ>(p, acc, n0, lds, [&](int row) {
-    const int ho = h0 + (row >> 4), wo = w0 + (row & 15);
-    return (ho < p.Ho && wo < p.Wo) ? ((long)b * p.Ho + ho) * p.Wo + wo : -1L;
-  });
-}
-
 // ---- 3x3 stride-1 convolution for narrow layers (Cin, Cout <= 64): weights stationary in LDS, persistent blocks ----------
 // With K = 9*Cin <= 576 a tile is nine tiny K steps; in the kernels above each step waits for a DMA issued one step
 // earlier, so a tile costs nine memory latencies for ~1 us of MFMA work (these layers ran at 2-3x their HBM time).
@@ -635,142 +511,54 @@ bool conv_mfma_supported(int dt, const ConvP& p) {
   return dt == F32 ? supported_t<float>(p) : supported_t<f16_t>(p);
 }
 
-// Tile configuration per channel-tile width, tunable with CLEARCAM_CONV_CFG="bm128,ns128,bm64,ns64"
-// (bm: 128|256 pixels per tile, ns: 2|3 stages).
-static int g_cfg[4] = {-1, 0, 0, 0};
-
-template <class T, int BM, int BN, int WM, bool SIMPLE, int CPRW, int NS, int NTH = 2 * BM>
-static void launch_k(const ConvP& p, const ConvAux& a, int mtiles, hipStream_t stream) {
-  constexpr size_t lds = (size_t)NS * (BM + BN) * CPRW * 16;
-  static PerDevice once;                               // the attribute is per device (common.h)
-  if (once.first(once.index())) {
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  note_launch(BM == 256 ? "conv_mfma_256" : (BM == 64 ? "conv_mfma_64" : (BM == 32 ? "conv_mfma_32" : "conv_mfma_128")), conv_mfma_kernel<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>, (long)mtiles * a.nt, NTH, lds);
-  hipLaunchKernelGGL((conv_mfma_kernel<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>), dim3(mtiles * a.nt), dim3(NTH), lds, stream, p, a);
-}
-
-static int g_thin_k = -1;     // K (elements) at or below which the 64-byte-row / 5-blocks-per-CU variant is used
-
-template <class T, int BN, bool SIMPLE>
-static void launch_cfg(const ConvP& p, const ConvAux& a, int M, int bm, int ns, hipStream_t stream) {
-  if (g_thin_k < 0) { const char* e = getenv("CLEARCAM_THIN_K"); g_thin_k = e ? atoi(e) : 256; }
-  if (p.Ktot * (int)sizeof(T) <= g_thin_k * 2) {        // few K steps: latency-bound -> favour occupancy over step size
-    launch_k<T, 128, BN, 2, SIMPLE, 4, 2>(p, a, (M + 127) / 128, stream);
-    return;
-  }
-  if (bm == 256) {
-    const int mt = (M + 255) / 256;
-    if (ns == 3) launch_k<T, 256, BN, 4, SIMPLE, 8, 3>(p, a, mt, stream);
-    else launch_k<T, 256, BN, 4, SIMPLE, 8, 2>(p, a, mt, stream);
-  } else {
-    const int mt = (M + 127) / 128;
-    if (ns == 3) launch_k<T, 128, BN, 2, SIMPLE, 8, 3>(p, a, mt, stream);
-    else launch_k<T, 128, BN, 2, SIMPLE, 8, 2>(p, a, mt, stream);
-  }
-}
-
-template <class T, int TS> static void launch_big(const ConvP& p, const ConvAux& a, int M, hipStream_t stream) {
-  constexpr size_t lds = (size_t)2 * (2 * TS) * 8 * 16;
-  static PerDevice once;                               // the attribute is per device (common.h)
-  if (once.first(once.index())) {
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_big_kernel<T, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  note_launch(TS == 256 ? "conv_big_256" : "conv_big_128", conv_big_kernel<T, TS>, (long)((M + TS - 1) / TS) * a.nt, 256, lds);
-  hipLaunchKernelGGL((conv_big_kernel<T, TS>), dim3(((M + TS - 1) / TS) * a.nt), dim3(256), lds, stream, p, a);
-}
-
-void launch_conv_phase(int dt, const ConvP& p, const ConvAux& a, int M, hipStream_t stream);   // conv_phase.hip
+bool conv_persist_ok(const ConvP& p);                                                            // conv_persist.hip
 bool conv_tile64_legal(const ConvP& p);                                                          // conv_tile64.hip
-void launch_conv_tile64(int dt, const ConvP& p, hipStream_t stream);
+void launch_conv_tile64(int dt, const ConvP& p, const ConvChoice& c, hipStream_t stream);
 bool conv_wave_legal(const ConvP& p);                                                            // conv_wave.hip
-void launch_conv_wave(int dt, const ConvP& p, hipStream_t stream);
+void launch_conv_wave(int dt, const ConvP& p, const ConvChoice& c, hipStream_t stream);
 bool conv_stream_legal(const ConvP& p);                                                          // conv_stream.hip
-void launch_conv_stream(int dt, const ConvP& p, hipStream_t stream);
+void launch_conv_stream(int dt, const ConvP& p, const ConvChoice& c, hipStream_t stream);
+void launch_conv_phase(int dt, const ConvP& p, const ConvAux& a, const ConvChoice& c, hipStream_t stream);   // conv_phase.hip
 
-template <class T, bool SIMPLE> static void launch_ts(const ConvP& p, const ConvAux& a, int bn, int M, hipStream_t stream) {
-  if (g_cfg[0] < 0) {
-    g_cfg[0] = 128; g_cfg[1] = 2; g_cfg[2] = 128; g_cfg[3] = 2;
-    if (const char* e = getenv("CLEARCAM_CONV_CFG")) sscanf(e, "%d,%d,%d,%d", &g_cfg[0], &g_cfg[1], &g_cfg[2], &g_cfg[3]);
-  }
-  if (bn == 256) {
-    if constexpr (SIMPLE && sizeof(T) == 2) {
-      static int sched = -1;
-      if (sched < 0) { const char* e = getenv("CLEARCAM_BIG_SCHED"); sched = e ? atoi(e) : 1; }
-      if (p.variant == 7 || (sched == 2 && p.Cin % 64 == 0)) {
-        CC_CHECK(p.Cin % 64 == 0 && p.Cout % 256 == 0, "eight-wave 256x256 kernel: Cin must be a multiple of 64 and Cout of 256");
-        launch_conv_phase(TypeTag<T>::dt, p, a, M, stream); return;
-      }
-      if (sched) { launch_big<T, 256>(p, a, M, stream); return; }
-    }
-    launch_k<T, 256, 256, 4, SIMPLE, 8, 2>(p, a, (M + 255) / 256, stream);
-  }
-  else if (bn == 128) {
-    if constexpr (SIMPLE && sizeof(T) == 2) {
-      // the single-barrier, register-double-buffered schedule with 128x128 tiles: 4-5 % faster than the two-barrier loop
-      // for K >= 1024 (3x3 with >= 128 channels, deep 1x1), 3-8 % slower for short K (per-layer A/B, YOLOv9-C B=64)
-      static int mid = -1;
-      if (mid < 0) { const char* e = getenv("CLEARCAM_MID_SCHED"); mid = e ? atoi(e) : 1024; }
-      if ((mid > 0 && p.Ktot >= mid) || p.variant == 6) { launch_big<T, 128>(p, a, M, stream); return; }
-    }
-    launch_cfg<T, 128, SIMPLE>(p, a, M, g_cfg[0], g_cfg[1], stream);
-  }
-  else if (bn == 64) {
-    // deep K on 64-wide channel tiles (the DDetect box branch's 3x3 256 -> 64 / 512 -> 64 entry convs): three LDS stages, i.e. the DMA
-    // two K steps ahead - 206 us against 257 with two stages at 80x80, B = 64 (399 against 485 with split weights; r04c_head_split.txt)
-    const int ns64 = (sizeof(T) == 2 && g_cfg[3] == 2 && p.Ktot >= 2048) ? 3 : g_cfg[3];
-    launch_cfg<T, 64, SIMPLE>(p, a, M, g_cfg[2], ns64, stream);
-  }
-  else launch_k<T, 128, 32, 4, SIMPLE, 8, 2>(p, a, (M + 127) / 128, stream);
+// ---- kernel selection --------------------------------------------------------------------------------------------------------
+std::atomic<int> g_stream_override{-1}, g_phase_flags_override{-1}, g_tile64_w_override{-1}, g_stream_flags_override{-1};
+std::atomic<int> g_stream_abl{0}, g_tile64_abl{0};
+
+const ConvSwitches& conv_switches() {
+  static const ConvSwitches s = [] {
+    auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    ConvSwitches w;
+    w.stream = env("CLEARCAM_STREAM", 1);
+    w.stream_min_pix = env("CLEARCAM_STREAM_MIN_PIX", 200000);   // measured (B = 64, profiles/r05f_stream_ab.txt): 1.13-1.5x at 160x160 and 80x80, a tie at 40x40 (102 400 pixels), 0.75x at 20x20
+    w.stream_flags = env("CLEARCAM_STREAM_FLAGS", 10);
+    w.ws = env("CLEARCAM_WS", 1);
+    w.small_tiles = env("CLEARCAM_SMALL_TILES", 1);
+    w.small_pix = env("CLEARCAM_SMALL_PIX", 1);
+    w.wave = env("CLEARCAM_WAVE", 1);
+    w.tile64 = env("CLEARCAM_TILE64", 1);
+    w.tile64_w = env("CLEARCAM_TILE64_W", 0);
+    w.big_tile = env("CLEARCAM_BIG_TILE", 1);
+    w.phase = env("CLEARCAM_PHASE", 2);
+    w.phase_flags = env("CLEARCAM_PHASE_FLAGS", -1);
+    return w;
+  }();
+  return s;
 }
 
-template <class T, int BN> static void launch_halo(const ConvP& p, hipStream_t stream) {
-  constexpr size_t lds = (size_t)(2 * 184 * 8 + 2 * BN * 8) * 16;
-  static PerDevice once;                               // the attribute is per device (common.h)
-  if (once.first(once.index())) {
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<T, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+static bool known_variant(int v) {
+  switch (v) {
+    case CONV_AUTO: case CONV_DIRECT: case CONV_GENERIC: case CONV_WS: case CONV_BIG256: case CONV_BIG128: case CONV_PHASE: case CONV_WAVE:
+    case CONV_SMALL: case CONV_STREAM: case CONV_TILE64: case CONV_SMALL_32_4: case CONV_SMALL_32_6: case CONV_SMALL_64_3:
+    case CONV_PIX64_6: case CONV_PIX64_4: case CONV_PIX32_6: case CONV_PIX32_4: return true;
+    default: return false;
   }
-  HaloAux a{};
-  a.tx = (p.Wo + 15) / 16; a.tiles = ((p.Ho + 7) / 8) * a.tx; a.nt = (p.Cout + BN - 1) / BN;
-  a.inv_tiles = 1.0f / (float)a.tiles; a.inv_tx = 1.0f / (float)a.tx;
-  note_launch("conv3x3_halo", conv3x3_halo_kernel<T, BN>, (long)p.B * a.tiles * a.nt, 256, lds);
-  hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN>), dim3(p.B * a.tiles * a.nt), dim3(256), lds, stream, p, a);
 }
 
-// 3x3 s1 p1, one source, whole 64-channel slabs.  Measured per layer (YOLOv9-C, B=64): 6-7 % faster than the generic
-// kernel for 128/256-channel layers whose image is covered by whole 8x16 tiles and whose Cout is a multiple of 128;
-// slower for Cout = 320 (64-wide channel tiles reload the patch five times), for ragged coverage (40x40) and for the
-// 64-channel layers (those are latency-chain bound, see conv3x3_ws_kernel).  Tests force it with variant 3.
-static bool halo_legal(const ConvP& p) {
-  return !p.split && p.ks == 3 && p.stride == 1 && p.pad == 1 && p.s1.C == 0 && p.s0.shift == 0 && p.Cin % 64 == 0 && p.Hin == p.Ho && p.Win == p.Wo;
-}
-static bool halo_applicable(const ConvP& p) {
-  static int on = -1;
-  // Off by default since round 2: with the single-barrier 128x128 schedule and the eight-wave kernel in place it no longer wins
-  // (whole plan, batch 64: 11.67 ms without it against 11.70 with it; single frame 1.30 against 1.34 ms, where it also kept its
-  // layers off the few-tile configuration because of its (channel slab, tap) K order).  CLEARCAM_HALO=1 brings it back.
-  if (on < 0) { const char* e = getenv("CLEARCAM_HALO"); on = e ? atoi(e) : 0; }
-  if (!on || !halo_legal(p)) return false;
-  const long covered = (long)((p.Ho + 7) / 8 * 8) * ((p.Wo + 15) / 16 * 16);
-  return p.Cin >= 128 && p.Cout % 128 == 0 && (long)p.Ho * p.Wo == covered;
-}
-
-template <class T, int CIN, int COUT> static void launch_ws(const ConvP& p, hipStream_t stream) {
-  constexpr int CPRW = CIN / 8, RPP = 256 / CPRW;
-  constexpr int XP = (180 + RPP - 1) / RPP * RPP * CPRW, WL = (9 * COUT + RPP - 1) / RPP * RPP * CPRW;
-  constexpr size_t lds = (size_t)(WL + 2 * XP + 128 * COUT * 2 / 16) * 16;
-  static PerDevice pd;                                 // attribute and CU count per device ordinal (common.h)
-  const int pdi = pd.index();
-  if (pd.first(pdi))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws_kernel<T, CIN, COUT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int cus = pd.cu_count(pdi);
-  WsAux a{};
-  a.tx = (p.Wo + 15) / 16; a.tiles = ((p.Ho + 7) / 8) * a.tx; a.total = p.B * a.tiles;
-  a.inv_tiles = 1.0f / (float)a.tiles; a.inv_tx = 1.0f / (float)a.tx;
-  const int blocks_per_cu = (int)(160 * 1024 / lds);           // persistent: as many blocks as fit, each walks total/grid tiles
-  note_launch("conv3x3_ws", conv3x3_ws_kernel<T, CIN, COUT>, (long)a.total, 256, lds, std::min(a.total, cus * std::max(1, blocks_per_cu)));
-  hipLaunchKernelGGL((conv3x3_ws_kernel<T, CIN, COUT>), dim3(std::min(a.total, cus * std::max(1, blocks_per_cu))), dim3(256), lds, stream, p, a);
+static ConvChoice generic(int bm, int bn, int wm, int cprw, int ns, bool simple) {
+  ConvChoice c;
+  c.bm = bm; c.bn = bn; c.wm = wm; c.cprw = cprw; c.ns = ns; c.simple = simple;
+  c.nth = bm == 256 ? 512 : 256;                       // 2 * BM; the few-tile configuration runs 32- and 64-pixel tiles on 256 threads too
+  return c;
 }
 
 // narrow 3x3 s1 p1 layers: Cin in {32, 64}, Cout <= 64 (a multiple of 8), one source
@@ -779,9 +567,7 @@ static bool ws_legal(const ConvP& p) {
          p.Cout <= 64 && p.Cout % 8 == 0 && p.Hin == p.Ho && p.Win == p.Wo;
 }
 static bool ws_applicable(const ConvP& p) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("CLEARCAM_WS"); on = e ? atoi(e) : 1; }
-  if (!on || !ws_legal(p)) return false;
+  if (!conv_switches().ws || !ws_legal(p)) return false;
   const long covered = (long)((p.Ho + 7) / 8 * 8) * ((p.Wo + 15) / 16 * 16);
   if ((long)p.Ho * p.Wo * 5 < covered * 4) return false; // 8x16 tiles must not waste more than a fifth of their pixels
   // Measured (YOLOv9-C, B=64): 32-channel layers (52 KB of LDS, three blocks and three patches in flight per CU) run 27 %
@@ -794,195 +580,265 @@ static bool ws_applicable(const ConvP& p) {
   const long tiles = (long)p.B * (covered / 128);
   return tiles >= 256L * 32;
 }
-template <class T> static void launch_ws_t(const ConvP& p, hipStream_t stream) {
-  if (p.Cin == 64) { if (p.Cout > 32) launch_ws<T, 64, 64>(p, stream); else launch_ws<T, 64, 32>(p, stream); }
-  else { if (p.Cout > 32) launch_ws<T, 32, 64>(p, stream); else launch_ws<T, 32, 32>(p, stream); }
+static ConvChoice ws_choice(const ConvP& p) {
+  ConvChoice c; c.kernel = ConvKernel::Ws; c.cin = p.Cin; c.cout = p.Cout > 32 ? 64 : 32;
+  return c;
 }
-
-static bool halo_applicable(const ConvP& p);
-static bool ws_legal(const ConvP& p);
-template <class T> static void launch_ws_t(const ConvP& p, hipStream_t stream);
 
 // Few-tile layers (a single frame, or the 20x20 maps of a batch): the grid does not fill the chip, one block per CU at best, and a
 // K step is then paced by the round trip of the DMA issued one step earlier (~0.6 us per step measured at batch 1: a 36-step 3x3
 // 256 -> 256 layer took 31 us on 8 blocks).  Here the generic kernel runs with narrow channel tiles (more blocks -> more CUs) and
 // three to six LDS stages (prefetch distance two to five steps: the queue is never drained, counted vmcnt only), which is
 // what the otherwise idle LDS is for.  CLEARCAM_SMALL_TILES=0 disables; tests force it with variant 9.
-template <class T> static bool launch_small(const ConvP& p, int M, hipStream_t stream, bool force) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("CLEARCAM_SMALL_TILES"); on = e ? atoi(e) : 1; }
-  if (!force && !on) return false;
+static bool choose_small(const ConvP& p, int M, bool simple, ConvChoice& c) {
+  const int v = p.variant;
+  const bool force = v != CONV_AUTO;
+  if (!force && !conv_switches().small_tiles) return false;
   const long mt = (M + 127) / 128, b32 = mt * ((p.Cout + 31) / 32), b64 = mt * ((p.Cout + 63) / 64);
   int bn = 0;
   if (b32 <= 512) bn = 32; else if (b64 <= 512) bn = 64;
   if (force && !bn) bn = 64;
   if (!bn) return false;
   bool deep = bn == 32 && b32 <= 256;                  // at most one block per CU anyway: six stages (120 KB), prefetch distance five
-  if (p.variant >= 91 && p.variant <= 93) { bn = p.variant == 93 ? 64 : 32; deep = p.variant == 92; }   // tuning sweeps: 91 32/4, 92 32/6, 93 64/3
-  {   // Round 6: smaller pixel tiles on 256 threads for the layers of a single frame.  A K step of the 128 x 32 configuration costs ~0.43 us however
-      // deep the prefetch: five LDS-DMA issues per wave (60-100 cycles each), two dependent fragment-read batches, one barrier - and a 40 x 40
-      // layer is 104 blocks on 256 CUs.  32 x 32 tiles: one pixel + one weight DMA per wave and step, four times the blocks; 64 x 32: three
-      // DMAs, twice the blocks.  Measured per shape at batch 1 (profiles/r06r_small_tiles_b1.txt, cc_conv_bench): 3x3 256 -> 256 at 40 x 40
-      // 18.2 -> 13.3 us, 3x3 512 -> 64 at 20 x 20 29.2 -> 17.8, 1x1 256 -> 256 at 40 x 40 5.0 -> 3.5; the sum over the 103 launches 1087 -> ~800 us.
-      // 32 x 32 up to 800 blocks, 64 x 32 up to 512; six stages for K >= 4096 on 32 x 32, four otherwise.  CLEARCAM_SMALL_PIX=0 disables;
-      // tests force them with variants 94-97.  Same K order and MFMA as every tile kernel: same bits, so the batch a frame arrives in does not matter.
-    static const int small_pix = [] { const char* e = getenv("CLEARCAM_SMALL_PIX"); return e ? atoi(e) : 1; }();
-    const long n32 = (p.Cout + 31) / 32, t32 = (long)((M + 31) / 32) * n32, t64 = (long)((M + 63) / 64) * n32;
-    int pix = 0, st = 4;
-    if (p.variant == 0 && small_pix) { if (t32 <= 800) { pix = 32; st = p.Ktot >= 4096 ? 6 : 4; } else if (t64 <= 512) pix = 64; }
-    if (p.variant == 94) { pix = 64; st = 6; } else if (p.variant == 95) pix = 64; else if (p.variant == 96) { pix = 32; st = 6; } else if (p.variant == 97) pix = 32;
-    if (pix) {
-      ConvAux a{};
-      a.nt = (int)n32;
-      a.inv_hw = 1.0f / (float)(p.Ho * p.Wo); a.inv_wo = 1.0f / (float)p.Wo;
-      const bool simple = p.s1.C == 0 && p.s0.shift == 0 && p.ks <= 3;
-      a.is1x1 = simple && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.Hin == p.Ho && p.Win == p.Wo;
-      const int mt64 = (M + 63) / 64, mt32 = (M + 31) / 32;
-      if (pix == 32 && st == 6) { if (simple) launch_k<T, 32, 32, 2, true, 8, 6, 256>(p, a, mt32, stream); else launch_k<T, 32, 32, 2, false, 8, 6, 256>(p, a, mt32, stream); }
-      else if (pix == 32) { if (simple) launch_k<T, 32, 32, 2, true, 8, 4, 256>(p, a, mt32, stream); else launch_k<T, 32, 32, 2, false, 8, 4, 256>(p, a, mt32, stream); }
-      else if (st == 6) { if (simple) launch_k<T, 64, 32, 4, true, 8, 6, 256>(p, a, mt64, stream); else launch_k<T, 64, 32, 4, false, 8, 6, 256>(p, a, mt64, stream); }
-      else { if (simple) launch_k<T, 64, 32, 4, true, 8, 4, 256>(p, a, mt64, stream); else launch_k<T, 64, 32, 4, false, 8, 4, 256>(p, a, mt64, stream); }
-      CC_HIP(hipGetLastError());
-      return true;
-    }
-  }
-  ConvAux a{};
-  a.nt = (p.Cout + bn - 1) / bn;
-  a.inv_hw = 1.0f / (float)(p.Ho * p.Wo); a.inv_wo = 1.0f / (float)p.Wo;
-  const bool simple = p.s1.C == 0 && p.s0.shift == 0 && p.ks <= 3;
-  a.is1x1 = simple && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.Hin == p.Ho && p.Win == p.Wo;
-  if (deep) { if (simple) launch_k<T, 128, 32, 4, true, 8, 6>(p, a, (int)mt, stream); else launch_k<T, 128, 32, 4, false, 8, 6>(p, a, (int)mt, stream); }
-  else if (bn == 32) { if (simple) launch_k<T, 128, 32, 4, true, 8, 4>(p, a, (int)mt, stream); else launch_k<T, 128, 32, 4, false, 8, 4>(p, a, (int)mt, stream); }
-  else { if (simple) launch_k<T, 128, 64, 2, true, 8, 3>(p, a, (int)mt, stream); else launch_k<T, 128, 64, 2, false, 8, 3>(p, a, (int)mt, stream); }
-  CC_HIP(hipGetLastError());
+  if (v >= CONV_SMALL_32_4 && v <= CONV_SMALL_64_3) { bn = v == CONV_SMALL_64_3 ? 64 : 32; deep = v == CONV_SMALL_32_6; }
+  // Round 6: smaller pixel tiles on 256 threads for the layers of a single frame.  A K step of the 128 x 32 configuration costs ~0.43 us however
+  // deep the prefetch: five LDS-DMA issues per wave (60-100 cycles each), two dependent fragment-read batches, one barrier - and a 40 x 40
+  // layer is 104 blocks on 256 CUs.  32 x 32 tiles: one pixel + one weight DMA per wave and step, four times the blocks; 64 x 32: three
+  // DMAs, twice the blocks.  Measured per shape at batch 1 (profiles/r06r_small_tiles_b1.txt, cc_conv_bench): 3x3 256 -> 256 at 40 x 40
+  // 18.2 -> 13.3 us, 3x3 512 -> 64 at 20 x 20 29.2 -> 17.8, 1x1 256 -> 256 at 40 x 40 5.0 -> 3.5; the sum over the 103 launches 1087 -> ~800 us.
+  // 32 x 32 up to 800 blocks, 64 x 32 up to 512; six stages for K >= 4096 on 32 x 32, four otherwise.  CLEARCAM_SMALL_PIX=0 disables;
+  // tests force them with variants 94-97.  Same K order and MFMA as every tile kernel: same bits, so the batch a frame arrives in does not matter.
+  const long n32 = (p.Cout + 31) / 32, t32 = (long)((M + 31) / 32) * n32, t64 = (long)((M + 63) / 64) * n32;
+  int pix = 0, st = 4;
+  if (v == CONV_AUTO && conv_switches().small_pix) { if (t32 <= 800) { pix = 32; st = p.Ktot >= 4096 ? 6 : 4; } else if (t64 <= 512) pix = 64; }
+  if (v == CONV_PIX64_6) { pix = 64; st = 6; } else if (v == CONV_PIX64_4) pix = 64; else if (v == CONV_PIX32_6) { pix = 32; st = 6; } else if (v == CONV_PIX32_4) pix = 32;
+  if (pix) c = generic(pix, 32, pix == 32 ? 2 : 4, 8, st, simple);
+  else if (deep) c = generic(128, 32, 4, 8, 6, simple);
+  else if (bn == 32) c = generic(128, 32, 4, 8, 4, simple);
+  else c = generic(128, 64, 2, 8, 3, simple);
   return true;
 }
 
-int g_stream_override = -1;                            // cc_dev_set("stream", v): A/B inside one process (tests, tools/dev)
+// The eight-wave two-group kernel's schedule.  CLEARCAM_PHASE_FLAGS / cc_dev_set("phase_flags"): unset = the default rule below;
+// 32: schedule 1 one tile per block; 0: schedule 0; 8 / 16: timing ablations of schedule 0; 64: buffer-descriptor DMA; 512: persistent
+// loop with the wave-staged epilogue (conv_persist.hip) for every eligible layer, + 1024: on v_mfma_f32_32x32x16, + 2048: drain the
+// previous tile's stores before the next K loop, bits 12-15: its timing ablations (development)
+static ConvChoice phase_choice(const ConvP& p, int M, bool simple, bool two) {
+  ConvChoice c; c.kernel = ConvKernel::Phase; c.bm = c.bn = 256; c.nth = 512; c.simple = simple; c.two = two;
+  const int ov = g_phase_flags_override.load();
+  int flags = ov >= 0 ? ov : conv_switches().phase_flags;
+  const bool persist_ok = conv_persist_ok(p);
+  if (flags < 0) {
+    // Default: the persistent loop where a block walks at least ~2.5 tiles (same results bit for bit; r03 A/B on MI355X: CLIP GEMMs
+    // +3-6 %, 1x1 convs at 80x80 / 160x160 +4-10 %, 3x3 256->256 at 80x80 +-1 %), one tile per block below that (400-tile layers at
+    // 40x40: the persistent form measured 2-4 % slower - its second round is as ragged, and the first has no dispatch skew)
+    // 1x1 layers take it from one full round on (their tiles are short - K <= 512 at 40x40 - so the next tile's first DMA under the
+    // store epilogue is a larger share: 256 -> 256 at 40x40, 400 tiles: 34.0 -> 30.2 us, 512 -> 256: 44.2 -> 41.7; r03p)
+    const bool is1x1 = simple && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.Hin == p.Ho && p.Win == p.Wo;
+    const long tiles = (long)((M + 255) / 256) * ((p.Cout + 255) / 256);
+    flags = ((tiles >= 640 || (is1x1 && tiles > 256)) && persist_ok) ? 512 : 32;
+  }
+  const size_t xb = (size_t)p.B * p.s0.H * p.s0.W * p.s0.cstride * 2, wbytes = (size_t)p.Cout * p.Kw * 2;
+  const bool buf_ok = xb < ((size_t)1 << 32) - 256 && wbytes < ((size_t)1 << 32) - 256;
+  c.flags = flags;
+  if ((flags & 512) && persist_ok) c.sched = PHASE_PERSIST;
+  else if ((flags & 64) && buf_ok && !two) c.sched = PHASE_BUFFER;
+  else c.sched = (flags & 32) ? PHASE_ONE_TILE : PHASE_SCHED0;
+  return c;
+}
 
-template <class T> static void launch_t(const ConvP& p, hipStream_t stream) {
+// 64 -> 64 from one round of 8 x 32-pixel tiles on: the persistent tile kernel with resident fragment-order weights (conv_tile64.hip, round 6;
+// CLEARCAM_TILE64=0 disables) - and only where its 256-pixel tiles cover the map without much waste (the better of 16 x 16 and 8 x 32 tiles
+// within 1.25x of the map: 80 x 80 and 160 x 160 exactly; a 40 x 40 map is 9 tiles of 16 x 16 = 1.44x and runs 21 us against 18 on the
+// wave-autonomous kernel).  Same K order as every kernel here: same bits.
+bool conv_tile64_takes(int B, int H, int W) {
+  const long per_frame = std::min((long)((H + 7) / 8) * ((W + 31) / 32), (long)((H + 15) / 16) * ((W + 15) / 16));
+  return conv_switches().tile64 && (long)B * per_frame >= 256 && per_frame * 256 * 4 <= (long)H * W * 5;
+}
+
+ConvChoice choose_conv(int dt, const ConvP& p) {
+  const int v = p.variant;
+  CC_CHECK(known_variant(v), "conv: ConvP::variant names no kernel");
+  ConvChoice c;
+  if (v == CONV_DIRECT || !conv_mfma_supported(dt, p)) { c.kernel = ConvKernel::Direct; return c; }
   const int M = p.B * p.Ho * p.Wo;
-  if constexpr (sizeof(T) == 2) {
-    // (layers the halo-resident kernel takes at any batch size keep it: its K order is (channel slab, tap), every other kernel's
-    //  (tap, channel), and a frame's result must not depend on the batch it arrives in - test_batch_invariance_and_determinism)
-    //  narrow 3x3 layers on a few tiles go to the weights-stationary kernel instead: 6.5-7.3 us against 8.5-10.5 at batch 1 (same K order))
-    {   // thin 1x1 layers whose roof is HBM: all weights resident in registers, pixels streamed through an LDS ring (conv_stream.hip).
-        // CLEARCAM_STREAM=0 disables; CLEARCAM_STREAM_MIN_PIX = fewest output pixels it is taken for; tests force it with variant 10.
-      // both values come from ONE thread-safe static (two plain statics let a second thread see stream_on set and stream_min still 0)
-      struct StreamEnv { int on, min_pix; };
-      static const StreamEnv env = [] {
-        const char* e = getenv("CLEARCAM_STREAM"); const char* m = getenv("CLEARCAM_STREAM_MIN_PIX");
-        return StreamEnv{e ? atoi(e) : 1, m ? atoi(m) : 200000};   // measured (B = 64, profiles/r05f_stream_ab.txt): 1.13-1.5x at 160x160 and 80x80, a tie at 40x40 (102 400 pixels), 0.75x at 20x20
-      }();
-      const int stream_min = env.min_pix;
-      const int on = g_stream_override >= 0 ? g_stream_override : env.on;
-      if (p.variant == 10 || (p.variant == 0 && on && M >= stream_min && conv_stream_legal(p))) {
-        launch_conv_stream(TypeTag<T>::dt, p, stream);
-        return;
-      }
+  const bool simple = p.s1.C == 0 && p.s0.shift == 0 && p.ks <= 3;
+  if (dt != F32) {
+    // thin 1x1 layers whose roof is HBM: all weights resident in registers, pixels streamed through an LDS ring (conv_stream.hip).
+    // CLEARCAM_STREAM=0 disables; CLEARCAM_STREAM_MIN_PIX = fewest output pixels it is taken for; tests force it with variant 10.
+    const int so = g_stream_override.load(), fo = g_stream_flags_override.load();
+    const int stream_on = so >= 0 ? so : conv_switches().stream;
+    if (v == CONV_STREAM || (v == CONV_AUTO && stream_on && M >= conv_switches().stream_min_pix && conv_stream_legal(p))) {
+      c.kernel = ConvKernel::Stream; c.cin = p.Cin; c.cout = p.Cout; c.flags = fo >= 0 ? fo : conv_switches().stream_flags;
+      return c;
     }
-    const bool few_narrow = p.variant == 0 && ws_legal(p) && (long)((M + 127) / 128) * ((p.Cout + 31) / 32) <= 512;
-    if (few_narrow) { launch_ws_t<T>(p, stream); CC_HIP(hipGetLastError()); return; }
-    if (((p.variant == 0 && !halo_applicable(p)) || p.variant == 9 || (p.variant >= 91 && p.variant <= 97)) && launch_small<T>(p, M, stream, p.variant >= 9)) return;
-    {   // narrow 3x3 layers: one autonomous wave per 2x16-pixel sub-tile over LDS-resident weights (conv_wave.hip).
-        // CLEARCAM_WAVE=0 falls back to the cooperative kernels below; tests force it with variant 8.
-      static int wave_on = -1;
-      if (wave_on < 0) { const char* e = getenv("CLEARCAM_WAVE"); wave_on = e ? atoi(e) : 1; }
-      // measured (B=64): 64 -> 64 at 80x80 51 us vs 57 (weights-stationary) / 59 (generic), at 160x160 204 vs 223 / 262; 32 -> 32
-      // ties the weights-stationary kernel (61 vs 58 us) and a handful of sub-tiles (batch 1) is better served by the tile kernels
-      // 64 -> 64 from one round of 8 x 32-pixel tiles on: the persistent tile kernel with resident fragment-order weights (conv_tile64.hip,
-      // round 6; CLEARCAM_TILE64=0 disables, tests force it with variant 12).  Same K order as every kernel here: same bits.
-      if constexpr (sizeof(T) == 2) {
-        static const int tile64_on = [] { const char* e = getenv("CLEARCAM_TILE64"); return e ? atoi(e) : 1; }();
-        // ... and only where its 256-pixel tiles cover the map without much waste (the better of 16 x 16 and 8 x 32 tiles within 1.25x of the map:
-        // 80 x 80 and 160 x 160 exactly; a 40 x 40 map is 9 tiles of 16 x 16 = 1.44x and runs 21 us against 18 on the wave-autonomous kernel)
-        const long per_frame = std::min((long)((p.Ho + 7) / 8) * ((p.Wo + 31) / 32), (long)((p.Ho + 15) / 16) * ((p.Wo + 15) / 16));
-        const long tiles64 = (long)p.B * per_frame;
-        const bool covers = per_frame * 256 * 4 <= (long)p.Ho * p.Wo * 5;
-        if (p.variant == 12 || (p.variant == 0 && tile64_on && conv_tile64_legal(p) && tiles64 >= 256 && covers)) {
-          CC_CHECK(conv_tile64_legal(p), "3x3 64 -> 64 tile kernel: shape not eligible");
-          launch_conv_tile64(TypeTag<T>::dt, p, stream);
-          return;
-        }
-      }
-      const long subtiles = (long)p.B * ((p.Ho + 1) / 2) * ((p.Wo + 15) / 16);
-      if (p.variant == 8 || (p.variant == 0 && wave_on && conv_wave_legal(p) && p.Cin == 64 && subtiles >= 4096)) {
-        CC_CHECK(conv_wave_legal(p), "wave-autonomous 3x3: shape not eligible");
-        launch_conv_wave(TypeTag<T>::dt, p, stream);
-        return;
-      }
+    // narrow 3x3 layers on a few tiles go to the weights-stationary kernel: 6.5-7.3 us against 8.5-10.5 at batch 1 (same K order)
+    if (v == CONV_AUTO && ws_legal(p) && (long)((M + 127) / 128) * ((p.Cout + 31) / 32) <= 512) return ws_choice(p);
+    if ((v == CONV_AUTO || v == CONV_SMALL || v >= CONV_SMALL_32_4) && choose_small(p, M, simple, c)) return c;
+    // the geometry with fewer tiles, 16 x 16 on a tie (its patch is 324 pixels against 340: 162 against 173 us at 160 x 160, 44.5 against 48.8
+    // at 80 x 80, B = 64, profiles/r06q_tile64.txt); CLEARCAM_TILE64_W / cc_dev_set("tile64_w") = 32 / 16 forces one (tests, A/B)
+    if (v == CONV_TILE64 || (v == CONV_AUTO && conv_tile64_legal(p) && conv_tile64_takes(p.B, p.Ho, p.Wo))) {
+      const int wo = g_tile64_w_override.load(), forced = wo >= 0 ? wo : conv_switches().tile64_w;
+      const long t32 = (long)((p.Ho + 7) / 8) * ((p.Wo + 31) / 32), t16 = (long)((p.Ho + 15) / 16) * ((p.Wo + 15) / 16);
+      c.kernel = ConvKernel::Tile64; c.tile64_w = (forced == 16 || (forced != 32 && t16 <= t32)) ? 16 : 32;
+      return c;
     }
-    if (p.variant == 4 || (p.variant == 0 && ws_applicable(p))) {
+    // narrow 3x3 layers: one autonomous wave per 2x16-pixel sub-tile over LDS-resident weights (conv_wave.hip).  CLEARCAM_WAVE=0 falls
+    // back to the cooperative kernels below; tests force it with variant 8.  Measured (B=64): 64 -> 64 at 80x80 51 us vs 57 (weights-
+    // stationary) / 59 (generic), at 160x160 204 vs 223 / 262; 32 -> 32 ties the weights-stationary kernel (61 vs 58 us) and a handful of
+    // sub-tiles (batch 1) is better served by the tile kernels
+    const long subtiles = (long)p.B * ((p.Ho + 1) / 2) * ((p.Wo + 15) / 16);
+    if (v == CONV_WAVE || (v == CONV_AUTO && conv_switches().wave && conv_wave_legal(p) && p.Cin == 64 && subtiles >= 4096)) {
+      c.kernel = ConvKernel::Wave; c.cin = p.Cin; c.cout = p.Cout;
+      return c;
+    }
+    if (v == CONV_WS || (v == CONV_AUTO && ws_applicable(p))) {
       CC_CHECK(ws_legal(p), "weights-stationary 3x3: shape not eligible");
-      launch_ws_t<T>(p, stream);
-      CC_HIP(hipGetLastError());
-      return;
-    }
-    if (p.variant == 3 || (p.variant == 0 && halo_applicable(p))) {
-      CC_CHECK(halo_legal(p), "halo-resident 3x3: shape not eligible");
-      auto padded = [&](int bn) { return (p.Cout + bn - 1) / bn * bn; };
-      if (padded(64) < padded(128)) launch_halo<T, 64>(p, stream); else launch_halo<T, 128>(p, stream);
-      CC_HIP(hipGetLastError());
-      return;
+      return ws_choice(p);
     }
   }
   auto padded = [&](int bn) { return (p.Cout + bn - 1) / bn * bn; };
   int bn = 128;
-  bool use_phase = false, use_two = false;
   if (padded(64) < padded(bn)) bn = 64;
   if (padded(32) < padded(bn)) bn = 32;
-  {   // 256x256 tiles / four-wave single-barrier schedule (conv_big_kernel) for wide, deep, GEMM-shaped layers.
-      // One block per CU, so whole rounds of 256 tiles matter: taken when K >= 1024 and the last round wastes <= 12 %
-      // (measured: -7..-18 % on such layers, +3..+16 % when K = 512 or when 400-800 tiles leave a half-empty round).
-      // CLEARCAM_BIG_TILE=0 disables, -1 forces it for every Cout % 256 == 0 layer (tests use variant 5).
-    static int big = -2, phase = -2;
-    if (big == -2) { const char* e = getenv("CLEARCAM_BIG_TILE"); big = e ? atoi(e) : 1; }
-    if (phase == -2) { const char* e = getenv("CLEARCAM_PHASE"); phase = e ? atoi(e) : 2; }
-    if (sizeof(T) == 2 && p.Cout % 256 == 0) {
-      const long tiles = (long)((M + 255) / 256) * (p.Cout / 256), rounds = (tiles + 255) / 256;
-      const bool fits = p.Ktot >= 1024 && tiles >= 256 && rounds * 256 * 100 <= tiles * 112;
-      // layers with a residual keep the 128x128 kernel: their f32 read-modify-write epilogue needs another block to hide behind
-      if ((big > 0 && fits && !p.res && p.variant == 0) || big < 0 || p.variant == 5 || p.variant == 7) bn = 256;
-      // The eight-wave two-group kernel (conv_phase.hip).  Per-layer A/B on YOLOv9-C B=64 and on the CLIP GEMMs (profiles/r02c):
-      // 5-18 % faster than the kernels above for layers with >= 400 tiles of 256x256 and for every CLIP GEMM (with or without
-      // the f32 residual epilogue), slower below ~400 tiles (one block per CU: a 100-tile layer leaves 156 CUs idle).
-      // CLEARCAM_PHASE=0 disables, 1 forces it for every eligible layer.
-      const bool simple1 = p.s1.C == 0 && p.s0.shift == 0 && p.ks <= 3;
-      // one block of eight waves per CU vs two blocks of four with 128x128 tiles: whichever fills its last round of CUs better wins,
-      // the eight-wave kernel being 12-20 % faster at equal fill (per-layer A/B, profiles/r02c_*)
-      const long t128 = (long)((M + 127) / 128) * ((p.Cout + 127) / 128);
-      const double fill256 = (double)tiles / (double)(rounds * 256), fill128 = (double)t128 / (double)(((t128 + 511) / 512) * 512);
-      const bool phase_rule = tiles >= 128 && fill256 * 1.2 >= fill128;
-      // ... and the 1x1 convs that read a Concat (two sources, one possibly upsampled: the first conv of the neck's ELAN blocks)
-      const bool concat1 = p.s1.C > 0 && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.s0.C % 64 == 0 && p.s1.C % 64 == 0;
-      use_two = concat1;
-      if ((p.variant == 0 || (p.variant == 7 && concat1)) && (simple1 || concat1) && p.Cin % 64 == 0 && (phase == 1 || p.variant == 7 || (phase != 0 && phase_rule))) { bn = 256; use_phase = true; }
-    }
+  if (dt != F32 && p.Cout % 256 == 0) {
+    // 256x256 tiles / four-wave single-barrier schedule (conv_big_kernel) for wide, deep, GEMM-shaped layers.
+    // One block per CU, so whole rounds of 256 tiles matter: taken when K >= 1024 and the last round wastes <= 12 %
+    // (measured: -7..-18 % on such layers, +3..+16 % when K = 512 or when 400-800 tiles leave a half-empty round).
+    // CLEARCAM_BIG_TILE=0 disables, -1 forces it for every Cout % 256 == 0 layer (tests use variant 5).
+    const int big = conv_switches().big_tile, phase = conv_switches().phase;
+    const long tiles = (long)((M + 255) / 256) * (p.Cout / 256), rounds = (tiles + 255) / 256;
+    const bool fits = p.Ktot >= 1024 && tiles >= 256 && rounds * 256 * 100 <= tiles * 112;
+    // layers with a residual keep the 128x128 kernel: their f32 read-modify-write epilogue needs another block to hide behind
+    if ((big > 0 && fits && !p.res && v == CONV_AUTO) || big < 0 || v == CONV_BIG256 || v == CONV_PHASE) bn = 256;
+    // The eight-wave two-group kernel (conv_phase.hip).  Per-layer A/B on YOLOv9-C B=64 and on the CLIP GEMMs (profiles/r02c):
+    // 5-18 % faster than the kernels above for layers with >= 400 tiles of 256x256 and for every CLIP GEMM (with or without
+    // the f32 residual epilogue), slower below ~400 tiles (one block per CU: a 100-tile layer leaves 156 CUs idle).
+    // CLEARCAM_PHASE=0 disables, 1 forces it for every eligible layer.
+    // One block of eight waves per CU vs two blocks of four with 128x128 tiles: whichever fills its last round of CUs better wins,
+    // the eight-wave kernel being 12-20 % faster at equal fill (per-layer A/B, profiles/r02c_*)
+    const long t128 = (long)((M + 127) / 128) * ((p.Cout + 127) / 128);
+    const double fill256 = (double)tiles / (double)(rounds * 256), fill128 = (double)t128 / (double)(((t128 + 511) / 512) * 512);
+    const bool phase_rule = tiles >= 128 && fill256 * 1.2 >= fill128;
+    // ... and the 1x1 convs that read a Concat (two sources, one possibly upsampled: the first conv of the neck's ELAN blocks)
+    const bool concat1 = p.s1.C > 0 && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.s0.C % 64 == 0 && p.s1.C % 64 == 0;
+    if ((v == CONV_AUTO || (v == CONV_PHASE && concat1)) && (simple || concat1) && p.Cin % 64 == 0 && (phase == 1 || v == CONV_PHASE || (phase != 0 && phase_rule)))
+      return phase_choice(p, M, simple, concat1);
   }
-  if (p.variant == 6) bn = 128;
-  ConvAux a{};
-  a.nt = (p.Cout + bn - 1) / bn;
-  a.inv_hw = 1.0f / (float)(p.Ho * p.Wo); a.inv_wo = 1.0f / (float)p.Wo;
+  if (v == CONV_BIG128) bn = 128;
+  const bool single_barrier = dt != F32 && simple;     // conv_big_kernel / the forced eight-wave kernel: 16-bit storage, one plain source
+  if (bn == 256) {
+    if (single_barrier && v == CONV_PHASE) {
+      CC_CHECK(p.Cin % 64 == 0 && p.Cout % 256 == 0, "eight-wave 256x256 kernel: Cin must be a multiple of 64 and Cout of 256");
+      return phase_choice(p, M, simple, false);
+    }
+    c = generic(256, 256, 4, 8, 2, simple);
+    if (single_barrier) c.kernel = ConvKernel::Big;
+    return c;
+  }
+  // the single-barrier, register-double-buffered schedule with 128x128 tiles: 4-5 % faster than the two-barrier loop
+  // for K >= 1024 (3x3 with >= 128 channels, deep 1x1), 3-8 % slower for short K (per-layer A/B, YOLOv9-C B=64)
+  if (bn == 128 && single_barrier && (p.Ktot >= 1024 || v == CONV_BIG128)) { c = generic(128, 128, 2, 8, 2, simple); c.kernel = ConvKernel::Big; return c; }
+  if (bn == 32) return generic(128, 32, 4, 8, 2, simple);
+  // few K steps (at most 512 bytes of K): latency-bound -> favour occupancy over step size with 64-byte rows
+  if (p.Ktot * (int)dtype_size(dt) <= 512) return generic(128, bn, 2, 4, 2, simple);
+  // deep K on 64-wide channel tiles (the DDetect box branch's 3x3 256 -> 64 / 512 -> 64 entry convs): three LDS stages, i.e. the DMA
+  // two K steps ahead - 206 us against 257 with two stages at 80x80, B = 64 (399 against 485 with split weights; r04c_head_split.txt)
+  return generic(128, bn, 2, 8, bn == 64 && dt != F32 && p.Ktot >= 2048 ? 3 : 2, simple);
+}
 
-  const bool simple = p.s1.C == 0 && p.s0.shift == 0 && p.ks <= 3;
-  a.is1x1 = simple && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.Hin == p.Ho && p.Win == p.Wo;
-  a.two = use_phase && use_two;
-  if (use_phase) { if constexpr (sizeof(T) == 2) launch_conv_phase(TypeTag<T>::dt, p, a, M, stream); }
-  else if (simple) launch_ts<T, true>(p, a, bn, M, stream); else launch_ts<T, false>(p, a, bn, M, stream);
-  CC_HIP(hipGetLastError());
+// ---- launchers: the instantiation the choice names ---------------------------------------------------------------------------
+template <class T, int BM, int BN, int WM, bool SIMPLE, int CPRW, int NS, int NTH>
+static void launch_k(const ConvP& p, const ConvAux& a, hipStream_t stream) {
+  constexpr size_t lds = (size_t)NS * (BM + BN) * CPRW * 16;
+  const int mtiles = (p.B * p.Ho * p.Wo + BM - 1) / BM;
+  ensure_max_lds(conv_mfma_kernel<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>, lds);
+  note_launch(BM == 256 ? "conv_mfma_256" : (BM == 64 ? "conv_mfma_64" : (BM == 32 ? "conv_mfma_32" : "conv_mfma_128")), conv_mfma_kernel<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>, (long)mtiles * a.nt, NTH, lds);
+  hipLaunchKernelGGL((conv_mfma_kernel<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>), dim3(mtiles * a.nt), dim3(NTH), lds, stream, p, a);
+}
+
+// every instantiation of conv_mfma_kernel that choose_conv names: (BM, BN, WM, CPRW, NS, NTH)
+template <class T, bool SIMPLE> static void launch_generic(const ConvP& p, const ConvAux& a, const ConvChoice& c, hipStream_t stream) {
+#define CC_GENERIC(BM, BN, WM, CPRW, NS, NTH) \
+  if (c.bm == BM && c.bn == BN && c.wm == WM && c.cprw == CPRW && c.ns == NS && c.nth == NTH) { launch_k<T, BM, BN, WM, SIMPLE, CPRW, NS, NTH>(p, a, stream); return; }
+  CC_GENERIC(128, 128, 2, 8, 2, 256)
+  CC_GENERIC(128, 64, 2, 8, 2, 256)
+  CC_GENERIC(128, 32, 4, 8, 2, 256)
+  CC_GENERIC(128, 128, 2, 4, 2, 256)                   // few K steps
+  CC_GENERIC(128, 64, 2, 4, 2, 256)
+  if constexpr (sizeof(T) == 2) {
+    CC_GENERIC(256, 256, 4, 8, 2, 512)
+    CC_GENERIC(128, 64, 2, 8, 3, 256)
+    CC_GENERIC(128, 32, 4, 8, 4, 256)                  // the few-tile configurations
+    CC_GENERIC(128, 32, 4, 8, 6, 256)
+    CC_GENERIC(64, 32, 4, 8, 4, 256)
+    CC_GENERIC(64, 32, 4, 8, 6, 256)
+    CC_GENERIC(32, 32, 2, 8, 4, 256)
+    CC_GENERIC(32, 32, 2, 8, 6, 256)
+  }
+#undef CC_GENERIC
+  CC_CHECK(false, "conv_mfma: no such instantiation of the generic kernel");
+}
+
+template <class T, int TS> static void launch_big(const ConvP& p, const ConvAux& a, hipStream_t stream) {
+  constexpr size_t lds = (size_t)2 * (2 * TS) * 8 * 16;
+  const int M = p.B * p.Ho * p.Wo;
+  ensure_max_lds(conv_big_kernel<T, TS>, lds);
+  note_launch(TS == 256 ? "conv_big_256" : "conv_big_128", conv_big_kernel<T, TS>, (long)((M + TS - 1) / TS) * a.nt, 256, lds);
+  hipLaunchKernelGGL((conv_big_kernel<T, TS>), dim3(((M + TS - 1) / TS) * a.nt), dim3(256), lds, stream, p, a);
+}
+
+template <class T, int CIN, int COUT> static void launch_ws(const ConvP& p, hipStream_t stream) {
+  constexpr int CPRW = CIN / 8, RPP = 256 / CPRW;
+  constexpr int XP = (180 + RPP - 1) / RPP * RPP * CPRW, WL = (9 * COUT + RPP - 1) / RPP * RPP * CPRW;
+  constexpr size_t lds = (size_t)(WL + 2 * XP + 128 * COUT * 2 / 16) * 16;
+  ensure_max_lds(conv3x3_ws_kernel<T, CIN, COUT>, lds);
+  const int cus = cu_count();
+  WsAux a{};
+  a.tx = (p.Wo + 15) / 16; a.tiles = ((p.Ho + 7) / 8) * a.tx; a.total = p.B * a.tiles;
+  a.inv_tiles = 1.0f / (float)a.tiles; a.inv_tx = 1.0f / (float)a.tx;
+  const int blocks_per_cu = (int)(160 * 1024 / lds);           // persistent: as many blocks as fit, each walks total/grid tiles
+  note_launch("conv3x3_ws", conv3x3_ws_kernel<T, CIN, COUT>, (long)a.total, 256, lds, std::min(a.total, cus * std::max(1, blocks_per_cu)));
+  hipLaunchKernelGGL((conv3x3_ws_kernel<T, CIN, COUT>), dim3(std::min(a.total, cus * std::max(1, blocks_per_cu))), dim3(256), lds, stream, p, a);
+}
+
+template <class T> static void launch_t(const ConvP& p, const ConvAux& a, const ConvChoice& c, hipStream_t stream) {
+  if constexpr (sizeof(T) == 2) {
+    if (c.kernel == ConvKernel::Ws) {
+      if (c.cin == 64) { if (c.cout == 64) launch_ws<T, 64, 64>(p, stream); else launch_ws<T, 64, 32>(p, stream); }
+      else { if (c.cout == 64) launch_ws<T, 32, 64>(p, stream); else launch_ws<T, 32, 32>(p, stream); }
+      return;
+    }
+    if (c.kernel == ConvKernel::Big) { if (c.bm == 256) launch_big<T, 256>(p, a, stream); else launch_big<T, 128>(p, a, stream); return; }
+  }
+  CC_CHECK(c.kernel == ConvKernel::Generic, "conv_mfma: kernel not available for this storage type");
+  if (c.simple) launch_generic<T, true>(p, a, c, stream); else launch_generic<T, false>(p, a, c, stream);
 }
 
 void launch_conv_mfma(int dt, const ConvP& p, hipStream_t stream) {
-  CC_CHECK(conv_mfma_supported(dt, p), "conv_mfma: unsupported shape/alignment");
-  if (dt == F32) launch_t<float>(p, stream);
-  else if (dt == F16) launch_t<f16_t>(p, stream);
-  else launch_t<bf16_t>(p, stream);
+  const ConvChoice c = choose_conv(dt, p);
+  ConvAux a{};
+  a.nt = (p.Cout + c.bn - 1) / c.bn;
+  a.inv_hw = 1.0f / (float)(p.Ho * p.Wo); a.inv_wo = 1.0f / (float)p.Wo;
+  a.is1x1 = c.simple && p.ks == 1 && p.stride == 1 && p.pad == 0 && p.Hin == p.Ho && p.Win == p.Wo;
+  a.two = c.two;
+  switch (c.kernel) {
+    case ConvKernel::Direct: launch_conv_direct(dt, p, stream); return;
+    case ConvKernel::Stream: launch_conv_stream(dt, p, c, stream); return;
+    case ConvKernel::Tile64: launch_conv_tile64(dt, p, c, stream); return;
+    case ConvKernel::Wave: launch_conv_wave(dt, p, c, stream); return;
+    case ConvKernel::Phase: launch_conv_phase(dt, p, a, c, stream); break;
+    default:
+      if (dt == F32) launch_t<float>(p, a, c, stream);
+      else if (dt == F16) launch_t<f16_t>(p, a, c, stream);
+      else launch_t<bf16_t>(p, a, c, stream);
+  }
+  CC_HIP(hipGetLastError());
 }
 
 void launch_conv(int dt, const ConvP& p, hipStream_t stream) {
-  if (p.s0.shift < 0) { launch_conv_adown(dt, p, stream); return; }
-  if (conv_mfma_supported(dt, p)) launch_conv_mfma(dt, p, stream);
-  else launch_conv_direct(dt, p, stream);
+  if (p.s0.shift < 0) launch_conv_adown(dt, p, stream);
+  else launch_conv_mfma(dt, p, stream);
 }
 
 }  // namespace cc

@@ -535,11 +535,8 @@ bool conv_persist_ok(const ConvP& p) {
 
 template <class T, int MM, int ABL = 0> static void launch_persist_t(const ConvP& p, const ConvAux& a, int M, hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * 512 * 8 * 16 + 512 * 4 * 16;     // two K tiles of (256 + 256) rows x 128 bytes + the per-row loader table
-  static PerDevice pd;                                 // attribute and CU count per device ordinal
-  const int d = pd.index();
-  if (pd.first(d))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_persist_kernel<T, MM, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int cus = pd.cu_count(d);
+  ensure_max_lds(conv_persist_kernel<T, MM, ABL>, lds);
+  const int cus = cu_count();
   ConvAux b = a;
   b.ntiles = ((M + 255) / 256) * a.nt;
   note_launch("conv_persist", conv_persist_kernel<T, MM, ABL>, (long)b.ntiles, 512, lds, std::min(b.ntiles, cus));

@@ -1,4 +1,5 @@
 // The eight-wave, two-group ("ping-pong") 256 x 256 implicit-GEMM kernel: its own translation unit (compile time).
+#include "conv_select.h"
 #include "conv_tile.h"
 
 namespace cc {
@@ -298,50 +299,30 @@ __global__ __launch_bounds__(512) void conv_phase_kernel(const ConvP p, const Co
 // block on every shape (CLIP fc GEMM 736 vs 632 us) and was removed.
 bool conv_persist_ok(const ConvP& p);
 void launch_conv_persist(int dt, int mm, int abl, const ConvP& p, const ConvAux& a, int M, hipStream_t stream);
-int g_phase_flags_override = -1;                       // cc_dev_set("phase_flags", v): A/B inside one process (tools/dev)
-
-template <class T> static void launch_phase(const ConvP& p, const ConvAux& a, int M, hipStream_t stream) {
+template <class T, int SCHED> static void launch_phase_k(const ConvP& p, const ConvAux& a, hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * 512 * 8 * 16 + 512 * 4 * 16;     // two K tiles of (256 + 256) rows x 128 bytes + the per-row loader table
-  static PerDevice once;                               // the attribute is per device (common.h)
-  if (once.first(once.index())) {
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_phase_kernel<T, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_phase_kernel<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_phase_kernel<T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  static int env_flags = -2;
-  // CLEARCAM_PHASE_FLAGS: unset = the default rule below; 32: schedule 1 one tile per block; 0: schedule 0; 8 / 16: timing ablations of
-  // schedule 0; 64: buffer-descriptor DMA; 512: persistent loop with the wave-staged epilogue (conv_persist.hip) for every
-  // eligible layer, + 1024: on v_mfma_f32_32x32x16, + 2048: drain the previous tile's stores before the next K loop, bits 12-15:
-  // its timing ablations (development)
-  if (env_flags == -2) { const char* e = getenv("CLEARCAM_PHASE_FLAGS"); env_flags = e ? atoi(e) : -1; }
-  int flags = g_phase_flags_override >= 0 ? g_phase_flags_override : env_flags;
-  if (flags < 0) {
-    // Default: the persistent loop where a block walks at least ~2.5 tiles (same results bit for bit; r03 A/B on MI355X: CLIP GEMMs
-    // +3-6 %, 1x1 convs at 80x80 / 160x160 +4-10 %, 3x3 256->256 at 80x80 +-1 %), one tile per block below that (400-tile layers at
-    // 40x40: the persistent form measured 2-4 % slower - its second round is as ragged, and the first has no dispatch skew)
-    // 1x1 layers take it from one full round on (their tiles are short - K <= 512 at 40x40 - so the next tile's first DMA under the
-    // store epilogue is a larger share: 256 -> 256 at 40x40, 400 tiles: 34.0 -> 30.2 us, 512 -> 256: 44.2 -> 41.7; r03p)
-    const long tiles = (long)((M + 255) / 256) * a.nt;
-    flags = ((tiles >= 640 || (a.is1x1 && tiles > 256)) && conv_persist_ok(p)) ? 512 : 32;
-  }
-  ConvAux b = a; b.flags = flags;
-  const size_t xb = (size_t)p.B * p.s0.H * p.s0.W * p.s0.cstride * sizeof(T), wbytes = (size_t)p.Cout * p.Kw * sizeof(T);
-  const bool buf_ok = xb < ((size_t)1 << 32) - 256 && wbytes < ((size_t)1 << 32) - 256;
-  b.x_bytes = (unsigned)xb; b.w_bytes = (unsigned)wbytes;
-  if ((flags & 512) && conv_persist_ok(p)) { launch_conv_persist(TypeTag<T>::dt, (flags & 1024) ? 1 : 0, (flags >> 12) & 15, p, b, M, stream); return; }
-  const long tiles = (long)((M + 255) / 256) * a.nt;                   // the note names the variant that is actually launched
-  if ((flags & 64) && buf_ok && !a.two) {
-    note_launch("conv_phase", conv_phase_kernel<T, 2>, tiles, 512, lds);
-    hipLaunchKernelGGL((conv_phase_kernel<T, 2>), dim3(tiles), dim3(512), lds, stream, p, b);
-    return;
-  }
-  if (flags & 32) { note_launch("conv_phase", conv_phase_kernel<T, 1>, tiles, 512, lds); hipLaunchKernelGGL((conv_phase_kernel<T, 1>), dim3(tiles), dim3(512), lds, stream, p, b); }
-  else { note_launch("conv_phase", conv_phase_kernel<T, 0>, tiles, 512, lds); hipLaunchKernelGGL((conv_phase_kernel<T, 0>), dim3(tiles), dim3(512), lds, stream, p, b); }
+  const long tiles = (long)((p.B * p.Ho * p.Wo + 255) / 256) * a.nt;
+  ensure_max_lds(conv_phase_kernel<T, SCHED>, lds);
+  note_launch("conv_phase", conv_phase_kernel<T, SCHED>, tiles, 512, lds);
+  hipLaunchKernelGGL((conv_phase_kernel<T, SCHED>), dim3(tiles), dim3(512), lds, stream, p, a);
 }
 
-void launch_conv_phase(int dt, const ConvP& p, const ConvAux& a, int M, hipStream_t stream) {
-  if (dt == F16) launch_phase<f16_t>(p, a, M, stream);
-  else launch_phase<bf16_t>(p, a, M, stream);
+// the schedule and ConvAux::flags come from choose_conv (conv_mfma.hip)
+template <class T> static void launch_phase(const ConvP& p, const ConvAux& a, const ConvChoice& c, hipStream_t stream) {
+  ConvAux b = a; b.flags = c.flags;
+  b.x_bytes = (unsigned)((size_t)p.B * p.s0.H * p.s0.W * p.s0.cstride * sizeof(T)); b.w_bytes = (unsigned)((size_t)p.Cout * p.Kw * sizeof(T));
+  switch (c.sched) {
+    case PHASE_PERSIST: launch_conv_persist(TypeTag<T>::dt, (c.flags & 1024) ? 1 : 0, (c.flags >> 12) & 15, p, b, p.B * p.Ho * p.Wo, stream); break;
+    case PHASE_BUFFER: launch_phase_k<T, 2>(p, b, stream); break;
+    case PHASE_ONE_TILE: launch_phase_k<T, 1>(p, b, stream); break;
+    default: launch_phase_k<T, 0>(p, b, stream);
+  }
+}
+
+void launch_conv_phase(int dt, const ConvP& p, const ConvAux& a, const ConvChoice& c, hipStream_t stream) {
+  CC_CHECK(dt != F32, "eight-wave 256x256 kernel: 16-bit storage only");
+  if (dt == F16) launch_phase<f16_t>(p, a, c, stream);
+  else launch_phase<bf16_t>(p, a, c, stream);
 }
 
 }  // namespace cc

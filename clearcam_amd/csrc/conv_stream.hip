@@ -16,6 +16,7 @@
 //     pixel (16 bytes) and every store instruction 64 contiguous bytes per pixel.
 // Same MFMA instruction, same chunk -> k mapping, same (plane, channel) walk and the same epilogue arithmetic as the tile kernels: the same
 // bits (tests/test_gpu_yolo.py::test_stream_1x1_equals_generic).
+#include "conv_select.h"
 #include "conv_tile.h"
 
 namespace cc {
@@ -283,60 +284,52 @@ static bool stream_cfg(const ConvP& p, StreamCfg& c) {
 }
 bool conv_stream_legal(const ConvP& p) { StreamCfg c; return stream_cfg(p, c); }
 
-// cc_dev_set("stream_flags", bits): StreamAux::flags.  CLEARCAM_STREAM_FLAGS is read HERE, once, when the library is loaded, so that a later
-// cc_dev_set wins (a lazy read inside the launcher overwrote an earlier cc_dev_set on the first launch)
-int g_stream_flags = [] { const char* e = getenv("CLEARCAM_STREAM_FLAGS"); return e ? atoi(e) : 10; }();
-int g_stream_abl = 0;                                  // cc_dev_set("stream_abl", bits): timing ablations of the f16 256 -> 256 shapes (development)
-template <class T, int WN, int KT, int CINC, int NP, int ABL = 0, int LATE = 0> static void launch_stream_k(const ConvP& p, hipStream_t stream) {
+// flags: StreamAux::flags (choose_conv: cc_dev_set("stream_flags") / CLEARCAM_STREAM_FLAGS)
+template <class T, int WN, int KT, int CINC, int NP, int ABL = 0, int LATE = 0> static void launch_stream_k(const ConvP& p, int flags, hipStream_t stream) {
   constexpr int PT = (8 / WN) * NP * 16;
   constexpr size_t lds = (size_t)4 * PT * (CINC / 2) * 128;
-  static PerDevice pd;
-  const int d = pd.index();
-  if (pd.first(d))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stream_kernel<T, WN, KT, CINC, NP, ABL, LATE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int cus = pd.cu_count(d);
+  ensure_max_lds(conv_stream_kernel<T, WN, KT, CINC, NP, ABL, LATE>, lds);
+  const int cus = cu_count();
   StreamAux a{};
   a.M = p.B * p.Ho * p.Wo;
   a.ntiles = (a.M + PT - 1) / PT;
-  a.flags = g_stream_flags;
+  a.flags = flags;
   note_launch("conv_stream", conv_stream_kernel<T, WN, KT, CINC, NP, ABL, LATE>, (long)a.ntiles, 512, lds, std::min(a.ntiles, cus));
   hipLaunchKernelGGL((conv_stream_kernel<T, WN, KT, CINC, NP, ABL, LATE>), dim3(std::min(a.ntiles, cus)), dim3(512), lds, stream, p, a);
 }
 
-template <class T> static void launch_stream_t(const ConvP& p, const StreamCfg& c, hipStream_t stream) {
-  const int pl = p.split ? 2 : 1;
+template <class T> static void launch_stream_t(const ConvP& p, const ConvChoice& c, hipStream_t stream) {
+  const int pl = p.split ? 2 : 1, f = c.flags;
 #ifdef CC_STREAM_ABLATIONS                              // development build only (HIPCC_EXTRA=-DCC_STREAM_ABLATIONS python clearcam_amd/build.py --force; tools/dev/stream_ablate.py)
   if constexpr (std::is_same<T, f16_t>::value) {
-    if (g_stream_abl && p.Cout == 256 && p.Cin == 256) {
-#define CC_ABL_CASE(b) case b: if (pl == 2) launch_stream_k<T, 8, 16, 8, 4, b>(p, stream); else launch_stream_k<T, 8, 8, 8, 4, b>(p, stream); return;
-      switch (g_stream_abl) { CC_ABL_CASE(1) CC_ABL_CASE(2) CC_ABL_CASE(3) CC_ABL_CASE(4) CC_ABL_CASE(8) CC_ABL_CASE(16) CC_ABL_CASE(20) CC_ABL_CASE(23) CC_ABL_CASE(24) CC_ABL_CASE(7) default: break; }
+    if (g_stream_abl.load() && c.cout == 256 && c.cin == 256) {
+#define CC_ABL_CASE(b) case b: if (pl == 2) launch_stream_k<T, 8, 16, 8, 4, b>(p, f, stream); else launch_stream_k<T, 8, 8, 8, 4, b>(p, f, stream); return;
+      switch (g_stream_abl.load()) { CC_ABL_CASE(1) CC_ABL_CASE(2) CC_ABL_CASE(3) CC_ABL_CASE(4) CC_ABL_CASE(8) CC_ABL_CASE(16) CC_ABL_CASE(20) CC_ABL_CASE(23) CC_ABL_CASE(24) CC_ABL_CASE(7) default: break; }
 #undef CC_ABL_CASE
     }
   }
 #else
-  CC_CHECK(!g_stream_abl, "timing ablations of the streaming kernel need a development build (-DCC_STREAM_ABLATIONS)");
+  CC_CHECK(!g_stream_abl.load(), "timing ablations of the streaming kernel need a development build (-DCC_STREAM_ABLATIONS)");
 #endif
   // flags bit 4: the activation arithmetic in the memory phase (LATE) - A/B per shape (cc_dev_set("stream_flags"))
-  const bool late = (g_stream_flags & 4) != 0;
-  if (p.Cout == 256 && p.Cin == 256) {
-    if (pl == 2) { if (late) launch_stream_k<T, 8, 16, 8, 4, 0, 1>(p, stream); else launch_stream_k<T, 8, 16, 8, 4>(p, stream); }
-    else { if (late) launch_stream_k<T, 8, 8, 8, 4, 0, 1>(p, stream); else launch_stream_k<T, 8, 8, 8, 4>(p, stream); }
+  const bool late = (f & 4) != 0;
+  if (c.cout == 256 && c.cin == 256) {
+    if (pl == 2) { if (late) launch_stream_k<T, 8, 16, 8, 4, 0, 1>(p, f, stream); else launch_stream_k<T, 8, 16, 8, 4>(p, f, stream); }
+    else { if (late) launch_stream_k<T, 8, 8, 8, 4, 0, 1>(p, f, stream); else launch_stream_k<T, 8, 8, 8, 4>(p, f, stream); }
   }
-  else if (p.Cout == 256 && p.Cin == 512) { if (late) launch_stream_k<T, 8, 16, 16, 2, 0, 1>(p, stream); else launch_stream_k<T, 8, 16, 16, 2>(p, stream); }
-  else if (p.Cout == 128) {
-    if (pl == 2) { if (late) launch_stream_k<T, 4, 8, 4, 4, 0, 1>(p, stream); else launch_stream_k<T, 4, 8, 4, 4>(p, stream); }
-    else { if (late) launch_stream_k<T, 4, 4, 4, 4, 0, 1>(p, stream); else launch_stream_k<T, 4, 4, 4, 4>(p, stream); }
+  else if (c.cout == 256 && c.cin == 512) { if (late) launch_stream_k<T, 8, 16, 16, 2, 0, 1>(p, f, stream); else launch_stream_k<T, 8, 16, 16, 2>(p, f, stream); }
+  else if (c.cout == 128) {
+    if (pl == 2) { if (late) launch_stream_k<T, 4, 8, 4, 4, 0, 1>(p, f, stream); else launch_stream_k<T, 4, 8, 4, 4>(p, f, stream); }
+    else { if (late) launch_stream_k<T, 4, 4, 4, 4, 0, 1>(p, f, stream); else launch_stream_k<T, 4, 4, 4, 4>(p, f, stream); }
   }
   else {
-    if (pl == 2) { if (late) launch_stream_k<T, 2, 4, 2, 4, 0, 1>(p, stream); else launch_stream_k<T, 2, 4, 2, 4>(p, stream); }
-    else { if (late) launch_stream_k<T, 2, 2, 2, 4, 0, 1>(p, stream); else launch_stream_k<T, 2, 2, 2, 4>(p, stream); }
+    if (pl == 2) { if (late) launch_stream_k<T, 2, 4, 2, 4, 0, 1>(p, f, stream); else launch_stream_k<T, 2, 4, 2, 4>(p, f, stream); }
+    else { if (late) launch_stream_k<T, 2, 2, 2, 4, 0, 1>(p, f, stream); else launch_stream_k<T, 2, 2, 2, 4>(p, f, stream); }
   }
-  (void)c;
 }
 
-void launch_conv_stream(int dt, const ConvP& p, hipStream_t stream) {
-  StreamCfg c;
-  CC_CHECK(dt != F32 && stream_cfg(p, c), "streaming 1x1: shape not eligible");
+void launch_conv_stream(int dt, const ConvP& p, const ConvChoice& c, hipStream_t stream) {
+  CC_CHECK(dt != F32 && conv_stream_legal(p), "streaming 1x1: shape not eligible");
   if (dt == F16) launch_stream_t<f16_t>(p, c, stream); else launch_stream_t<bf16_t>(p, c, stream);
   CC_HIP(hipGetLastError());
 }

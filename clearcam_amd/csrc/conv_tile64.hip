@@ -30,6 +30,7 @@
 //    own (the next vmcnt(0) of the wave is a whole K loop later).
 // K order (tap, 32-channel step) is that of every other conv kernel: same bits (tests/test_gpu_yolo.py::test_tile64_3x3_equals_generic).
 #include <utility>
+#include "conv_select.h"
 #include "conv_tile.h"
 
 namespace cc {
@@ -59,8 +60,6 @@ template <int TWIDTH> struct Tile64Geom {
 // global stores, 4 = no activation arithmetic, 8 = no MFMA (fragment reads stay), 16 = no K loop at all, 32 = no finish phase (the accumulators
 // are kept alive), 64 = fragment reads two k steps ahead instead of one, 256 = the K loop at priority 1,
 // 512 / 1024 = the finish phase at priority 3 while it requests the patch / at priority 1 throughout, 128 = cycle counts per phase kind behind the output.
-int g_tile64_abl = 0;
-int g_tile64_w = -1;
 
 template <class T, int ABL = 0, int TWIDTH = 32>
 __global__ __launch_bounds__(512) void conv3x3_tile64_kernel(const ConvP p, const Tile64Aux a) {
@@ -300,11 +299,8 @@ bool conv_tile64_legal(const ConvP& p) {
 template <class T, int ABL = 0, int TWIDTH = 32> static void launch_tile64_g(const ConvP& p, hipStream_t stream) {
   using G = Tile64Geom<TWIDTH>;
   constexpr int lds = G::LDS_BYTES;
-  static PerDevice pd;
-  const int pdi = pd.index();
-  if (pd.first(pdi))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_tile64_kernel<T, ABL, TWIDTH>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const int cus = pd.cu_count(pdi);
+  ensure_max_lds(conv3x3_tile64_kernel<T, ABL, TWIDTH>, lds);
+  const int cus = cu_count();
   Tile64Aux a{};
   a.tx = (p.Wo + G::TW - 1) / G::TW; a.tiles = ((p.Ho + G::TH - 1) / G::TH) * a.tx; a.total = p.B * a.tiles;
   a.inv_tiles = 1.0f / (float)a.tiles; a.inv_tx = 1.0f / (float)a.tx;
@@ -313,54 +309,44 @@ template <class T, int ABL = 0, int TWIDTH = 32> static void launch_tile64_g(con
   hipLaunchKernelGGL((conv3x3_tile64_kernel<T, ABL, TWIDTH>), dim3(grid), dim3(512), lds, stream, p, a);
 }
 
-// the geometry with fewer tiles, 16 x 16 on a tie (its patch is 324 pixels against 340: 162 against 173 us at 160 x 160, 44.5 against 48.8 at 80 x 80,
-// B = 64, profiles/r06q_tile64.txt); CLEARCAM_TILE64_W=32 / 16 forces one (tests, A/B)
-template <class T, int ABL = 0> static void launch_tile64_t(const ConvP& p, hipStream_t stream) {
-  static const int env_w = [] { const char* e = getenv("CLEARCAM_TILE64_W"); return e ? atoi(e) : 0; }();
-  const int forced = g_tile64_w >= 0 ? g_tile64_w : env_w;      // cc_dev_set("tile64_w", 32 / 16 / -1)
-  const long t32 = (long)((p.Ho + 7) / 8) * ((p.Wo + 31) / 32), t16 = (long)((p.Ho + 15) / 16) * ((p.Wo + 15) / 16);
-  if constexpr (ABL == 0) {
-    if (forced == 16 || (forced != 32 && t16 <= t32)) { launch_tile64_g<T, 0, 16>(p, stream); return; }
-  }
-  launch_tile64_g<T, ABL, 32>(p, stream);
-}
-
-void launch_conv_tile64(int dt, const ConvP& p, hipStream_t stream) {
+// c.tile64_w: the tile geometry choose_conv picked (conv_mfma.hip)
+void launch_conv_tile64(int dt, const ConvP& p, const ConvChoice& c, hipStream_t stream) {
   CC_CHECK(conv_tile64_legal(p) && dt != F32, "3x3 64 -> 64 tile kernel: shape not eligible");
-#ifdef CC_TILE64_ABLATIONS
-  if (g_tile64_abl && dt == F16) {
-    switch (g_tile64_abl) {
-      case 1: launch_tile64_t<f16_t, 1>(p, stream); return;
-      case 2: launch_tile64_t<f16_t, 2>(p, stream); return;
-      case 4: launch_tile64_t<f16_t, 4>(p, stream); return;
-      case 6: launch_tile64_t<f16_t, 6>(p, stream); return;
-      case 7: launch_tile64_t<f16_t, 7>(p, stream); return;
-      case 8: launch_tile64_t<f16_t, 8>(p, stream); return;
-      case 16: launch_tile64_t<f16_t, 16>(p, stream); return;
-      case 32: launch_tile64_t<f16_t, 32>(p, stream); return;
-      case 33: launch_tile64_t<f16_t, 33>(p, stream); return;
-      case 40: launch_tile64_t<f16_t, 40>(p, stream); return;
-      case 64: launch_tile64_t<f16_t, 64>(p, stream); return;
-      case 128: launch_tile64_t<f16_t, 128>(p, stream); return;
-      case 256: launch_tile64_t<f16_t, 256>(p, stream); return;
-      case 512: launch_tile64_t<f16_t, 512>(p, stream); return;
-      case 768: launch_tile64_t<f16_t, 768>(p, stream); return;
-      case 1280: launch_tile64_t<f16_t, 1280>(p, stream); return;
-      case 384: launch_tile64_t<f16_t, 384>(p, stream); return;
-      case 640: launch_tile64_t<f16_t, 640>(p, stream); return;
-      case 160: launch_tile64_t<f16_t, 160>(p, stream); return;
-      case 144: launch_tile64_t<f16_t, 144>(p, stream); return;
-      case 96: launch_tile64_t<f16_t, 96>(p, stream); return;
-      case 104: launch_tile64_t<f16_t, 104>(p, stream); return;
-      case 17: launch_tile64_t<f16_t, 17>(p, stream); return;
-      case 18: launch_tile64_t<f16_t, 18>(p, stream); return;
-      case 20: launch_tile64_t<f16_t, 20>(p, stream); return;
-      case 23: launch_tile64_t<f16_t, 23>(p, stream); return;
+#ifdef CC_TILE64_ABLATIONS                              // timing ablations: 8 x 32-pixel tiles only
+  if (const int abl = g_tile64_abl.load(); abl && dt == F16) {
+    switch (abl) {
+      case 1: launch_tile64_g<f16_t, 1, 32>(p, stream); return;
+      case 2: launch_tile64_g<f16_t, 2, 32>(p, stream); return;
+      case 4: launch_tile64_g<f16_t, 4, 32>(p, stream); return;
+      case 6: launch_tile64_g<f16_t, 6, 32>(p, stream); return;
+      case 7: launch_tile64_g<f16_t, 7, 32>(p, stream); return;
+      case 8: launch_tile64_g<f16_t, 8, 32>(p, stream); return;
+      case 16: launch_tile64_g<f16_t, 16, 32>(p, stream); return;
+      case 32: launch_tile64_g<f16_t, 32, 32>(p, stream); return;
+      case 33: launch_tile64_g<f16_t, 33, 32>(p, stream); return;
+      case 40: launch_tile64_g<f16_t, 40, 32>(p, stream); return;
+      case 64: launch_tile64_g<f16_t, 64, 32>(p, stream); return;
+      case 128: launch_tile64_g<f16_t, 128, 32>(p, stream); return;
+      case 256: launch_tile64_g<f16_t, 256, 32>(p, stream); return;
+      case 512: launch_tile64_g<f16_t, 512, 32>(p, stream); return;
+      case 768: launch_tile64_g<f16_t, 768, 32>(p, stream); return;
+      case 1280: launch_tile64_g<f16_t, 1280, 32>(p, stream); return;
+      case 384: launch_tile64_g<f16_t, 384, 32>(p, stream); return;
+      case 640: launch_tile64_g<f16_t, 640, 32>(p, stream); return;
+      case 160: launch_tile64_g<f16_t, 160, 32>(p, stream); return;
+      case 144: launch_tile64_g<f16_t, 144, 32>(p, stream); return;
+      case 96: launch_tile64_g<f16_t, 96, 32>(p, stream); return;
+      case 104: launch_tile64_g<f16_t, 104, 32>(p, stream); return;
+      case 17: launch_tile64_g<f16_t, 17, 32>(p, stream); return;
+      case 18: launch_tile64_g<f16_t, 18, 32>(p, stream); return;
+      case 20: launch_tile64_g<f16_t, 20, 32>(p, stream); return;
+      case 23: launch_tile64_g<f16_t, 23, 32>(p, stream); return;
       default: break;
     }
   }
 #endif
-  if (dt == F16) launch_tile64_t<f16_t>(p, stream); else launch_tile64_t<bf16_t>(p, stream);
+  if (c.tile64_w == 16) { if (dt == F16) launch_tile64_g<f16_t, 0, 16>(p, stream); else launch_tile64_g<bf16_t, 0, 16>(p, stream); }
+  else { if (dt == F16) launch_tile64_g<f16_t, 0, 32>(p, stream); else launch_tile64_g<bf16_t, 0, 32>(p, stream); }
   CC_HIP(hipGetLastError());
 }
 

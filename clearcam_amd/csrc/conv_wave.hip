@@ -12,6 +12,7 @@
 // Eight waves (64 channels) or sixteen (32 channels) share a CU, two or four per SIMD: while one wave waits for its patch or
 // runs its epilogue VALU the others keep the matrix pipe busy, with no s_barrier anywhere in the loop.  A wave orders its own
 // LDS-DMA writes against its own ds_reads with its vmcnt (MI355X_MICROARCH.md: nothing else is needed for same-wave data).
+#include "conv_select.h"
 #include "conv_tile.h"
 
 namespace cc {
@@ -146,11 +147,8 @@ template <class T, int CIN, int COUT, int NW> static void launch_wave(const Conv
   constexpr int CPRW = CIN / 8, ROWB = CIN * 2, RPI = 64 / CPRW, NPI = (72 + RPI - 1) / RPI;
   constexpr int RPP = NW * 64 / CPRW, WPASS = (9 * COUT + RPP - 1) / RPP;
   constexpr size_t lds = (size_t)WPASS * RPP * ROWB + (size_t)NW * NPI * RPI * ROWB;
-  static PerDevice pd;                                 // attribute and CU count per device ordinal (common.h)
-  const int pdi = pd.index();
-  if (pd.first(pdi))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wave_kernel<T, CIN, COUT, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int cus = pd.cu_count(pdi);
+  ensure_max_lds(conv3x3_wave_kernel<T, CIN, COUT, NW>, lds);
+  const int cus = cu_count();
   WaveAux a{};
   a.tx = (p.Wo + 15) / 16; a.tiles = ((p.Ho + 1) / 2) * a.tx; a.total = p.B * a.tiles;
   a.inv_tiles = 1.0f / (float)a.tiles; a.inv_tx = 1.0f / (float)a.tx;
@@ -164,14 +162,14 @@ bool conv_wave_legal(const ConvP& p) {
          (p.Cout == 32 || p.Cout == 64) && p.Hin == p.Ho && p.Win == p.Wo && (long)p.B * ((p.Ho + 1) / 2) * ((p.Wo + 15) / 16) < (1L << 22);
 }
 
-template <class T> static void launch_wave_t(const ConvP& p, hipStream_t stream) {
-  if (p.Cin == 64) { if (p.Cout == 64) launch_wave<T, 64, 64, 8>(p, stream); else launch_wave<T, 64, 32, 8>(p, stream); }
-  else { if (p.Cout == 64) launch_wave<T, 32, 64, 16>(p, stream); else launch_wave<T, 32, 32, 16>(p, stream); }
+template <class T> static void launch_wave_t(const ConvP& p, const ConvChoice& c, hipStream_t stream) {
+  if (c.cin == 64) { if (c.cout == 64) launch_wave<T, 64, 64, 8>(p, stream); else launch_wave<T, 64, 32, 8>(p, stream); }
+  else { if (c.cout == 64) launch_wave<T, 32, 64, 16>(p, stream); else launch_wave<T, 32, 32, 16>(p, stream); }
 }
 
-void launch_conv_wave(int dt, const ConvP& p, hipStream_t stream) {
+void launch_conv_wave(int dt, const ConvP& p, const ConvChoice& c, hipStream_t stream) {
   CC_CHECK(conv_wave_legal(p) && dt != F32, "wave-autonomous 3x3: shape not eligible");
-  if (dt == F16) launch_wave_t<f16_t>(p, stream); else launch_wave_t<bf16_t>(p, stream);
+  if (dt == F16) launch_wave_t<f16_t>(p, c, stream); else launch_wave_t<bf16_t>(p, c, stream);
   CC_HIP(hipGetLastError());
 }
 

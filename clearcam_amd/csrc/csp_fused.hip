@@ -427,11 +427,8 @@ bool csp_fused_supported(int dt, int hid, int split) { return (dt == F16 || (dt 
 
 template <class T, int HID, bool RES, int SPLIT = 0> static void launch_csp(const CspP& p, hipStream_t stream) {
   constexpr int lds = RES ? CspGeom<HID, SPLIT>::R_LDS_BYTES : CspGeom<HID, SPLIT>::S_LDS_BYTES;
-  static PerDevice pd;                                 // attribute and CU count per device ordinal (common.h)
-  const int pdi = pd.index();
-  if (pd.first(pdi))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(csp_fused_kernel<T, HID, RES, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const int cus = pd.cu_count(pdi);
+  ensure_max_lds(csp_fused_kernel<T, HID, RES, SPLIT>, lds);
+  const int cus = cu_count();
   const int total = p.B * p.tiles;
   // persistent: one block per CU, a multiple of 8 so that every XCD gets the same number of walkers
   const int grid = RES ? std::max(8, std::min(cus, total) & ~7) : total;

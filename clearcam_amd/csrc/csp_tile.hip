@@ -305,11 +305,8 @@ bool csp_tile_supported(int dt, int hid, int split) { return (dt == F16 || (dt =
 
 template <class T, int SPLIT> static void launch_csp_tile_t(const CspP& p, hipStream_t stream) {
   constexpr int lds = CspTileGeom<SPLIT>::LDS_BYTES;
-  static PerDevice pd;
-  const int pdi = pd.index();
-  if (pd.first(pdi))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(csp_tile_kernel<T, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const int cus = pd.cu_count(pdi);
+  ensure_max_lds(csp_tile_kernel<T, SPLIT>, lds);
+  const int cus = cu_count();
   const int total = p.B * p.tiles;
   const int grid = std::max(8, std::min(cus, total) & ~7);          // persistent, one block per CU, the same number of walkers on every XCD
   note_launch("csp_tile", csp_tile_kernel<T, SPLIT>, (long)total, 512, lds, grid);

@@ -551,10 +551,7 @@ template <class T, int CH, bool SPLIT = false> static void launch_head_tail_t(co
   constexpr int PL = SPLIT ? 2 : 1;
   constexpr size_t lds = (size_t)80 * (PL * CH * 2 + 16) + 64 * (PL * 64 * 2 + 16) + 4 * 16 * 68 * 4;
   static_assert(lds <= 160 * 1024, "the level's weights must fit in LDS");
-  // (per device: a process may hold handles on several GPUs, and the attribute is per device)
-  static PerDevice once;
-  if (once.first(once.index()))
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(head_tail_kernel<T, CH, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ensure_max_lds(head_tail_kernel<T, CH, SPLIT>, lds);
   int nb[3];
   for (int l = 0; l < 3; ++l) { const long M = (long)p.B * p.H[l] * p.W[l]; nb[l] = (int)((M + 64 * kTailTPB - 1) / (64 * kTailTPB)); }
   hipLaunchKernelGGL((head_tail_kernel<T, CH, SPLIT>), dim3(nb[0] + nb[1] + nb[2]), dim3(256), lds, stream, p, nb[0], nb[0] + nb[1]);

@@ -17,8 +17,7 @@ template <class K> inline void note_launch(const char* name, K kernel, long tile
   if (!slots) {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kernel), threads, lds) != hipSuccess) nb = 1;
-    static PerDevice pd;                                   // CU count cached per device (hipGetDeviceProperties is not cheap)
-    slots = (long)nb * pd.cu_count(pd.index());
+    slots = (long)nb * cu_count();
   }
   g_launch_note = LaunchNote{name, tiles, slots > 0 ? slots : 1};
 }

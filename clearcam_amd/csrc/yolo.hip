@@ -23,6 +23,7 @@
 #include <vector>
 #include <cmath>
 #include <cstring>
+#include "conv_select.h"
 #include "kernels.h"
 #include "../../include/clearcam_hip.h"
 
@@ -467,9 +468,7 @@ struct Builder {
     if (level == 0 || (level == 1 && hid != 32)) return false;
     if (level == 2 && hid == 64 && !pconv({r + ".m.list.0.cv1.conv"}, {1}).split) {
       const Buf& ib = P->bufs[in.buf];
-      const char* t64 = getenv("CLEARCAM_TILE64");
-      const long per_frame = std::min((long)((ib.H + 7) / 8) * ((ib.W + 31) / 32), (long)((ib.H + 15) / 16) * ((ib.W + 15) / 16));   // conv_mfma.hip's rule for conv_tile64
-      if (!(t64 && atoi(t64) == 0) && (long)P->B * per_frame >= 256 && per_frame * 256 * 4 <= (long)ib.H * ib.W * 5) return false;
+      if (conv_tile64_takes(P->B, ib.H, ib.W)) return false;
     }
     const char* only = dev_env("CLEARCAM_CSP_ONLY");                // development: fuse just this block (csp_debug.py)
     if (only && atoi(only) != index) return false;
@@ -1147,12 +1146,6 @@ namespace cc { void set_error(const std::string& m) { g_err = m; } }
   catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
   catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
 
-namespace cc { extern int g_phase_flags_override; }   // conv_phase.hip
-namespace cc { extern int g_stream_flags; }           // conv_stream.hip
-namespace cc { extern int g_stream_abl; }             // conv_stream.hip
-namespace cc { extern int g_tile64_abl, g_tile64_w; }  // conv_tile64.hip
-namespace cc { extern int g_stream_override; }        // conv_mfma.hip: -1 = CLEARCAM_STREAM / default, 0 / 1 = streaming 1x1 kernel off / on
-
 extern "C" {
 
 const char* cc_last_error(void) { return g_err.c_str(); }
@@ -1735,8 +1728,8 @@ int cc_conv2d_nhwc(int dtype, const void* x_dev, int B, int H, int W, int Cin, c
   c.Ho = (H + 2 * c.pad - k) / stride + 1; c.Wo = (W + 2 * c.pad - k) / stride + 1; c.Cout = Cout; c.Ktot = k * k * Cin * (1 + split); c.Kw = pc.kw;
   c.split = pc.split; c.oscale = pc.oscale;
   c.w = pc.w; c.bias = pc.bias; c.out = out_dev; c.out_cstride = Cout; c.out_coff = 0; c.out_f32 = 0; c.res = nullptr; c.act = act;
-  c.variant = force_direct;                              // 0 auto, 1 direct, 2 generic MFMA, 3 halo-resident, 4 weights-stationary
-  if (force_direct == 1) launch_conv_direct(dtype, c, (hipStream_t)stream); else launch_conv(dtype, c, (hipStream_t)stream);
+  c.variant = force_direct;                              // ConvVariant (conv_select.h): 0 auto, 1 direct, 2 generic MFMA, ...
+  launch_conv(dtype, c, (hipStream_t)stream);
   CC_HIP(hipStreamSynchronize((hipStream_t)stream));
   hipFree(pc.w); hipFree(pc.bias);
   CC_API_END
@@ -1785,9 +1778,9 @@ int cc_dev_set(const char* key, int value) {
   if (std::string(key) == "phase_flags") cc::g_phase_flags_override = value;
   else if (std::string(key) == "stream") cc::g_stream_override = value;
   else if (std::string(key) == "stream_abl") cc::g_stream_abl = value;
-  else if (std::string(key) == "stream_flags") cc::g_stream_flags = value;
+  else if (std::string(key) == "stream_flags") cc::g_stream_flags_override = value;
   else if (std::string(key) == "tile64_abl") cc::g_tile64_abl = value;
-  else if (std::string(key) == "tile64_w") cc::g_tile64_w = value;
+  else if (std::string(key) == "tile64_w") cc::g_tile64_w_override = value;
   else throw cc::Error(-22, std::string("cc_dev_set: unknown key ") + key);
   CC_API_END
 }

@@ -117,8 +117,8 @@ void cc_yolo_destroy(cc_yolo* h);
  * x (B,H,W,Cin) and out (B,Ho,Wo,Cout) in storage dtype `dtype`; w OIHW float32 host, bias host.
  * groups>1 is densified to block-diagonal weights exactly as the detector does for the head convs.
  * force_direct selects the kernel: 0 = what the detector would pick, 1 = direct (non-MFMA) fallback, 2 = generic MFMA
- * implicit GEMM, 3 = halo-resident 3x3, 4 = weights-stationary 3x3, ... 10 = weights-resident streaming 1x1 (ConvP::variant in
- * csrc/common.h lists them all; the specialised ones fail if the shape is not eligible). */
+ * implicit GEMM, 4 = weights-stationary 3x3, ... 10 = weights-resident streaming 1x1, 12 = 3x3 64 -> 64 tile kernel (ConvVariant in
+ * csrc/conv_select.h lists them all; the specialised ones fail if the shape is not eligible, a value that names no kernel fails). */
 int cc_conv2d_nhwc(int dtype, const void* x_dev, int B, int H, int W, int Cin, const float* w_oihw,
                    const float* bias, int Cout, int k, int stride, int groups, int act, void* out_dev,
                    int force_direct, void* stream);
@@ -137,7 +137,8 @@ int cc_round_weights(int dtype, const float* w, int64_t cout, int64_t cin, int64
  * key "phase_flags": the CLEARCAM_PHASE_FLAGS bit set of the eight-wave kernel (-1 = back to the environment / default);
  * key "stream": the weights-resident streaming 1x1 kernel off (0) / on (1) / as CLEARCAM_STREAM says (-1);
  * key "tile64_w": tile geometry of the 3x3 64 -> 64 tile kernel, 32 (8 x 32 pixels) / 16 (16 x 16) / -1 (its own rule);
- * keys "stream_abl", "stream_flags", "tile64_abl": timing ablations / flag bits of development builds (no effect otherwise).
+ * key "stream_flags": the CLEARCAM_STREAM_FLAGS bit set of the streaming 1x1 kernel (-1 = back to the environment / default);
+ * keys "stream_abl", "tile64_abl": timing ablations of development builds (no effect otherwise).
  * Plans already built keep the launches they were built with.  Not part of the drop-in surface. */
 int cc_dev_set(const char* key, int value);
 

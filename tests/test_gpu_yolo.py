@@ -66,10 +66,6 @@ CONV_CASES = [
 ]
 # (name, B, Cin, H, W, Cout, variant): the specialised 3x3 kernels, forced through cc_conv2d_nhwc's selector (16-bit modes)
 SPECIAL_CASES = [
-    ("halo_ragged", 2, 64, 14, 30, 64, 3),               # ragged 8x16 tiles
-    ("halo_3slabs", 3, 192, 24, 32, 128, 3),             # several 64-channel slabs
-    ("halo_cout320", 1, 128, 16, 16, 320, 3),            # 64-wide channel tiles, five of them
-    ("halo_1row", 1, 64, 8, 160, 192, 3),
     ("ws_64_64", 5, 64, 24, 48, 64, 4),                  # more tiles than one block's share: the persistent loop
     ("ws_64_64_ragged", 2, 64, 13, 21, 64, 4),
     ("ws_32_32", 3, 32, 16, 32, 32, 4),
@@ -323,7 +319,43 @@ def test_specialised_kernels_refuse_ineligible_shapes():
         conv_hip(x, w, b, 1, 1, 1, "bf16", force_direct=4)           # Cin = 128: not a narrow layer
     x, w = torch.randn(1, 32, 16, 16), torch.randn(64, 32, 3, 3)
     with pytest.raises(CCError):
-        conv_hip(x, w, b, 1, 1, 1, "bf16", force_direct=3)           # Cin = 32: not whole 64-channel slabs
+        conv_hip(x, w, b, 1, 1, 1, "bf16", force_direct=12)          # Cin = 32: not a 64 -> 64 layer
+    for variant in (3, 11):                                           # values that name no kernel
+        with pytest.raises(CCError, match="names no kernel"):
+            conv_hip(x, w, b, 1, 1, 1, "bf16", force_direct=variant)
+
+
+_LDS_RACE_SCRIPT = r"""
+import threading, numpy as np, torch
+from clearcam_amd import _lib
+L = _lib.lib()
+g = torch.Generator().manual_seed(11)
+x = torch.randn(2, 40, 40, 64, generator=g).to("cuda", torch.float16)
+w = np.ascontiguousarray((torch.randn(64, 64, 3, 3, generator=g) / 24).numpy())
+b = np.ascontiguousarray((torch.randn(64, generator=g) * 0.1).numpy())
+outs = [torch.full((2, 40, 40, 64), float("nan"), dtype=torch.float16, device="cuda") for _ in range(2)]
+torch.cuda.synchronize()
+start, errs = threading.Barrier(2), [None, None]
+def run(i):
+    start.wait()
+    if L.cc_conv2d_nhwc(1, _lib.ptr(x), 2, 40, 40, 64, _lib.ptr(w), _lib.ptr(b), 64, 3, 1, 1, 1, _lib.ptr(outs[i]), 12, None) != 0:
+        errs[i] = L.cc_last_error().decode()
+threads = [threading.Thread(target=run, args=(i,)) for i in range(2)]
+for t in threads: t.start()
+for t in threads: t.join()
+assert errs == [None, None], errs
+torch.cuda.synchronize()
+assert torch.isfinite(outs[0].float()).all() and torch.equal(outs[0], outs[1])
+"""
+
+
+def test_first_launch_from_two_threads():
+    """Two host threads make a process's first launch of the 160 KB conv_tile64 kernel at the same time: the dynamic-LDS attribute is set once,
+    before either launch, so both calls succeed and return the same output."""
+    import subprocess
+    import sys
+    env = dict(os.environ, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    subprocess.run([sys.executable, "-c", _LDS_RACE_SCRIPT], check=True, env=env, timeout=300)
 
 
 def test_conv_direct_fallback_odd_channels():
