@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libclearcam_hip.so")
 SYMBOLS = [
     "cc_last_error", "cc_version", "cc_device_count",
     "cc_yolo_create", "cc_yolo_load", "cc_yolo_calibrate", "cc_yolo_calibration_info", "cc_gptq_round_f16", "cc_yolo_finalize", "cc_yolo_detect", "cc_yolo_set_in_flight", "cc_yolo_submit", "cc_yolo_wait",
+    "cc_yolo_detect_ragged", "cc_yolo_submit_ragged", "cc_letterbox_geometry", "cc_yolo_plans_built",
     "cc_yolo_get_tensor", "cc_yolo_get_tensor_frames", "cc_yolo_nonfinite",
     "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
     "cc_clip_create", "cc_clip_load", "cc_clip_finalize", "cc_clip_encode_image", "cc_clip_encode_text",
@@ -66,6 +67,10 @@ def lib() -> C.CDLL:
         "cc_yolo_set_in_flight": [vp, C.c_int],
         "cc_yolo_submit": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.POINTER(C.c_longlong)],
         "cc_yolo_wait": [vp, C.c_longlong, vp],
+        "cc_yolo_detect_ragged": [vp, vp, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp],
+        "cc_yolo_submit_ragged": [vp, vp, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.POINTER(C.c_longlong)],
+        "cc_letterbox_geometry": [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip],
+        "cc_yolo_plans_built": [vp, ip],
         "cc_yolo_get_tensor": [vp, C.c_char_p, vp, i64p, ip],
         "cc_yolo_get_tensor_frames": [vp, C.c_char_p, C.c_int, C.c_int, vp, i64p, ip],
         "cc_yolo_nonfinite": [vp, ip],

@@ -58,13 +58,35 @@ __device__ __forceinline__ void letterbox_rgb(const PreP& p, int b, int y, int x
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(256) void preprocess_kernel(const PreP p) {
+// Ragged batch: the geometry image b is letterboxed with = the launch's PreP with the frame's record desc[b] filled in and `frames` moved to
+// the frame's first byte - image fb = 0 of a one-image batch - so that everything downstream is the uniform code, which takes the launch's
+// own PreP and fb = b (the record is block-uniform: scalar loads).
+// The kernels that know the source size take the records as an OPTIONAL trailing argument (a parameter pack that is empty for the uniform
+// launch): one kernel text for both, and the uniform instantiation is the kernel it was before the ragged form existed.
+struct RaggedArgs { const FrameDesc* desc; size_t buf_bytes; };     // buf_bytes: size of the packed buffer the frames sit in
+__device__ __forceinline__ const RaggedArgs& ragged_args(const RaggedArgs& r) { return r; }
+__device__ __forceinline__ PreP frame_view(const PreP& p, const FrameDesc* __restrict__ desc, int b, int& fb) {
+  const FrameDesc& d = desc[b];
+  PreP q = p;
+  q.frames = reinterpret_cast<const unsigned char*>(p.frames) + d.off;
+  q.B = 1; q.H = d.H; q.W = d.W; q.nh = d.nh; q.nw = d.nw; q.pad_y = d.pad_y; q.pad_x = d.pad_x;
+  q.xlo = d.xlo; q.xhi = d.xhi; q.xfr = d.xfr; q.ylo = d.ylo; q.yhi = d.yhi; q.yfr = d.yfr;
+  fb = 0;
+  return q;
+}
+
+template <class T, class... R>
+__global__ __launch_bounds__(256) void preprocess_kernel(const PreP p0, const R... ragged) {
+  constexpr bool RAGGED = sizeof...(R) != 0;
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;      // grid = (row tiles, row, image)
-  if (x >= p.Wn) return;
-  const size_t idx = ((size_t)b * p.Hn + y) * p.Wn + x;
+  if (x >= p0.Wn) return;
+  const size_t idx = ((size_t)b * p0.Hn + y) * p0.Wn + x;
   float rgb[3];
-  letterbox_rgb(p, b, y, x, rgb);
+  int fb = b;
+  PreP pr;
+  if constexpr (RAGGED) pr = frame_view(p0, ragged_args(ragged...).desc, b, fb);
+  const PreP& p = RAGGED ? pr : p0;
+  letterbox_rgb(p, fb, y, x, rgb);
   T* o = reinterpret_cast<T*>(p.out) + idx * p.out_c;
   if (p.out_c * (int)sizeof(T) == 16) {                         // the stem's one 16-byte channel chunk: a single store
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -90,8 +112,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreP p) {
 // share a CU instead of three.
 // SPLIT: the weights are two f16 planes (ConvP::split): a second MFMA per channel fragment on the low plane, the accumulator scaled by the
 // exact 2^-e in the epilogue.
-template <class T, int COUT, bool BIG, bool SPLIT = false>
-__global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p) {
+// Ragged batch (R = RaggedArgs): image b's source geometry comes from desc[b] (frame_view) - every block still makes the staging decision
+// for its own tile, so a 4K frame reads directly beside a 720p frame that stages.
+template <class T, int COUT, bool BIG, bool SPLIT = false, class... R>
+__global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p, const R... ragged) {
+  constexpr bool RAGGED = sizeof...(R) != 0;
   constexpr int PW = 33, PROW = 104;                     // patch row: 33 pixels x 3 channels (+ pad) in storage type
   constexpr int NT = COUT / 16, OROW = COUT + 8;         // staged output row: COUT channels + 16 bytes (bank spread)
   constexpr int SCRATCH = (BIG ? 256 : 128) * 72 * 2;    // bytes: the source-pixel stage (phase 1) and the output stage (phase 3) share it
@@ -120,7 +145,10 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p) {
   // Per-pixel byte loads from HBM are what bounds the stand-alone letterbox kernel (12 load instructions per pixel), so the
   // tile's interpolation tables and - for uint8 frames whose source rectangle fits - the source bytes themselves are
   // staged in LDS with aligned dword loads first; the taps are then LDS reads.  Arithmetic is letterbox_taps either way.
-  const PreP& q = p.pre;
+  int fb = b;                                            // image b's index inside q.frames
+  PreP qr;
+  if constexpr (RAGGED) qr = frame_view(p.pre, ragged_args(ragged...).desc, b, fb);
+  const PreP& q = RAGGED ? qr : p.pre;
   const int Y0 = 2 * oy0 - 1, X0 = 2 * ox0 - 1;
   if (tid < 2 * PW) {
     const bool isx = tid < PW;
@@ -145,7 +173,10 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p) {
   const bool staged = !q.frame_f32 && any && nrows * dpr * 4 <= SCRATCH;
   if (staged && !(p.abl & 4)) {
     const uintptr_t base = reinterpret_cast<uintptr_t>(q.frames);
+    // end of the caller's buffer: of the PACKED buffer for a ragged batch, whose frames start at arbitrary byte offsets inside it
     const size_t total = (size_t)q.B * q.H * q.W * 3;
+    uintptr_t end = base + total;
+    if constexpr (RAGGED) end = reinterpret_cast<uintptr_t>(p.pre.frames) + ragged_args(ragged...).buf_bytes;
     // four independent dword loads per thread in flight (unconditional, index clamped), then the LDS writes
     const int n = nrows * dpr;
     const float inv_dpr = 1.0f / (float)dpr;
@@ -159,8 +190,8 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p) {
         const int d = i - r * dpr;
         // absolute addresses: an aligned dword never straddles a page, so the words holding the buffer's first and last
         // byte are readable whatever the alignment of the caller's pointer or the size of the buffer
-        const uintptr_t a0 = base + (((size_t)b * q.H + sr0 + r) * q.W + sc0) * 3;   // first byte this row needs
-        const uintptr_t al = min((a0 & ~(uintptr_t)3) + 4 * (uintptr_t)d, (base + total - 1) & ~(uintptr_t)3);
+        const uintptr_t a0 = base + (((size_t)fb * q.H + sr0 + r) * q.W + sc0) * 3;   // first byte this row needs
+        const uintptr_t al = min((a0 & ~(uintptr_t)3) + 4 * (uintptr_t)d, (end - 1) & ~(uintptr_t)3);
         v[u] = *reinterpret_cast<const unsigned*>(al);
       }
 #pragma unroll
@@ -171,8 +202,8 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p) {
   // thread -> (column tid & 31, rows tid >> 5, +8, ...): whatever depends on the column only is read once; column 32 of the
   // patch is done by the first 33 threads afterwards
   const T zero = from_f32<T>(0.f), padv = from_f32<T>(q.pad_val);
-  const size_t img = (size_t)b * q.H;
-  const unsigned fr_lo = (unsigned)reinterpret_cast<uintptr_t>(q.frames);
+  const size_t img = (size_t)fb * q.H;
+  const unsigned fr_lo = (unsigned)reinterpret_cast<uintptr_t>(q.frames);     // ragged: the frame's own first byte, whatever its offset
   auto pixel = [&](int pr, int pc, int x0, int x1, int wx, float fx) {
     T o[3] = {zero, zero, zero};                                        // outside the network input: the conv's zero padding
     const int y = Y0 + pr, x = X0 + pc;
@@ -187,7 +218,7 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const StemP p) {
           int v[3];
           if (staged) {
             auto rowoff = [&](int r) {                                   // LDS byte offset of source column sc0 in row r
-              const unsigned sh = (fr_lo + ((unsigned)(b * q.H + r) * (unsigned)q.W + (unsigned)sc0) * 3u) & 3u;
+              const unsigned sh = (fr_lo + ((unsigned)(fb * q.H + r) * (unsigned)q.W + (unsigned)sc0) * 3u) & 3u;
               return (r - sr0) * dpr * 4 + (int)sh;                      // the row's first byte, modulo its aligned dword
             };
             const int r0 = rowoff(y0), r1 = rowoff(y1), c0 = (x0 - sc0) * 3, c1 = (x1 - sc0) * 3;
@@ -309,35 +340,47 @@ void stem_pack_weights(int dt, const void* w_packed, int w_row, int tap_stride, 
 
 bool stem_fused_supported(int dt, int Cout) { return dt != F32 && (Cout == 16 || Cout == 32 || Cout == 64); }
 
-template <class T, bool BIG> static void launch_stem_b(const StemP& p, hipStream_t stream) {
+// desc == nullptr: the uniform kernel; else the ragged one over the same body
+template <class T, int COUT, bool BIG, bool SPLIT> static void launch_stem_k(const StemP& p, const FrameDesc* desc, size_t buf_bytes, hipStream_t stream) {
   const dim3 grid((unsigned)((p.Wo + 15) / 16), (unsigned)((p.Ho + 15) / 16), (unsigned)p.pre.B), block(256);
+  if (desc) hipLaunchKernelGGL((stem_fused_kernel<T, COUT, BIG, SPLIT, RaggedArgs>), grid, block, 0, stream, p, RaggedArgs{desc, buf_bytes});
+  else hipLaunchKernelGGL((stem_fused_kernel<T, COUT, BIG, SPLIT>), grid, block, 0, stream, p);
+}
+template <class T, bool BIG> static void launch_stem_b(const StemP& p, const FrameDesc* desc, size_t buf_bytes, hipStream_t stream) {
   if constexpr (std::is_same<T, f16_t>::value) {
     if (p.w_lo) {                                                     // split weights (f16 storage only)
-      if (p.Cout == 64) hipLaunchKernelGGL((stem_fused_kernel<T, 64, BIG, true>), grid, block, 0, stream, p);
-      else if (p.Cout == 32) hipLaunchKernelGGL((stem_fused_kernel<T, 32, BIG, true>), grid, block, 0, stream, p);
-      else hipLaunchKernelGGL((stem_fused_kernel<T, 16, BIG, true>), grid, block, 0, stream, p);
+      if (p.Cout == 64) launch_stem_k<T, 64, BIG, true>(p, desc, buf_bytes, stream);
+      else if (p.Cout == 32) launch_stem_k<T, 32, BIG, true>(p, desc, buf_bytes, stream);
+      else launch_stem_k<T, 16, BIG, true>(p, desc, buf_bytes, stream);
       return;
     }
   }
-  if (p.Cout == 64) hipLaunchKernelGGL((stem_fused_kernel<T, 64, BIG>), grid, block, 0, stream, p);
-  else if (p.Cout == 32) hipLaunchKernelGGL((stem_fused_kernel<T, 32, BIG>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((stem_fused_kernel<T, 16, BIG>), grid, block, 0, stream, p);
+  if (p.Cout == 64) launch_stem_k<T, 64, BIG, false>(p, desc, buf_bytes, stream);
+  else if (p.Cout == 32) launch_stem_k<T, 32, BIG, false>(p, desc, buf_bytes, stream);
+  else launch_stem_k<T, 16, BIG, false>(p, desc, buf_bytes, stream);
 }
-template <class T> static void launch_stem_t(const StemP& p, hipStream_t stream) {
-  // bytes the source rectangle of a 33x33-pixel patch can take in the stage (the kernel checks the exact figure per tile and reads
-  // the frame directly where it does not fit): small scratch, twice the blocks per CU, when that is at most 18 KB
-  const PreP& q = p.pre;
-  const long nr = (33L * q.H + q.nh - 1) / q.nh + 2, nc = (33L * q.W + q.nw - 1) / q.nw + 2;
-  const bool big = !q.frame_f32 && nr * ((nc * 3 + 6) / 4) * 4 > 128 * 72 * 2;
-  if (big) launch_stem_b<T, true>(p, stream); else launch_stem_b<T, false>(p, stream);
+// bytes the source rectangle of a 33x33-pixel patch can take in the stage (the kernel checks the exact figure per tile and reads
+// the frame directly where it does not fit): small scratch, twice the blocks per CU, when that is at most 18 KB
+bool stem_needs_big(int H, int W, int nh, int nw, int frame_f32) {
+  const long nr = (33L * H + nh - 1) / nh + 2, nc = (33L * W + nw - 1) / nw + 2;
+  return !frame_f32 && nr * ((nc * 3 + 6) / 4) * 4 > 128 * 72 * 2;
 }
 
-void launch_stem_fused(int dt, const StemP& p0, hipStream_t stream) {
+static void launch_stem_any(int dt, const StemP& p0, const FrameDesc* desc, size_t buf_bytes, bool big, hipStream_t stream) {
   StemP p = p0;
   { static const int abl = [] { const char* e = getenv("CLEARCAM_STEM_ABL"); return e ? atoi(e) : 0; }(); p.abl = abl; }
   CC_CHECK(stem_fused_supported(dt, p.Cout) && p.out_coff % 8 == 0 && p.out_cstride % 8 == 0 && (!p.w_lo || dt == F16), "fused stem: unsupported dtype / channel count");
-  if (dt == F16) launch_stem_t<f16_t>(p, stream); else launch_stem_t<bf16_t>(p, stream);
+  if (dt == F16) { if (big) launch_stem_b<f16_t, true>(p, desc, buf_bytes, stream); else launch_stem_b<f16_t, false>(p, desc, buf_bytes, stream); }
+  else { if (big) launch_stem_b<bf16_t, true>(p, desc, buf_bytes, stream); else launch_stem_b<bf16_t, false>(p, desc, buf_bytes, stream); }
   CC_HIP(hipGetLastError());
+}
+void launch_stem_fused(int dt, const StemP& p, hipStream_t stream) {
+  const PreP& q = p.pre;
+  launch_stem_any(dt, p, nullptr, 0, stem_needs_big(q.H, q.W, q.nh, q.nw, q.frame_f32), stream);
+}
+void launch_stem_fused_ragged(int dt, const StemP& p, const FrameDesc* desc, size_t packed_bytes, bool big, hipStream_t stream) {
+  CC_CHECK(desc && packed_bytes > 0, "ragged fused stem: no frame records");
+  launch_stem_any(dt, p, desc, packed_bytes, big, stream);
 }
 
 void launch_preprocess(int dt, const PreP& p, hipStream_t stream) {
@@ -345,6 +388,15 @@ void launch_preprocess(int dt, const PreP& p, hipStream_t stream) {
   if (dt == F32) hipLaunchKernelGGL(preprocess_kernel<float>, grid, block, 0, stream, p);
   else if (dt == F16) hipLaunchKernelGGL(preprocess_kernel<f16_t>, grid, block, 0, stream, p);
   else hipLaunchKernelGGL(preprocess_kernel<bf16_t>, grid, block, 0, stream, p);
+  CC_HIP(hipGetLastError());
+}
+void launch_preprocess_ragged(int dt, const PreP& p, const FrameDesc* desc, size_t, hipStream_t stream) {
+  CC_CHECK(desc, "ragged letterbox: no frame records");
+  const dim3 grid((unsigned)((p.Wn + 255) / 256), (unsigned)p.Hn, (unsigned)p.B), block(256);
+  const RaggedArgs ra{desc, 0};
+  if (dt == F32) hipLaunchKernelGGL((preprocess_kernel<float, RaggedArgs>), grid, block, 0, stream, p, ra);
+  else if (dt == F16) hipLaunchKernelGGL((preprocess_kernel<f16_t, RaggedArgs>), grid, block, 0, stream, p, ra);
+  else hipLaunchKernelGGL((preprocess_kernel<bf16_t, RaggedArgs>), grid, block, 0, stream, p, ra);
   CC_HIP(hipGetLastError());
 }
 
@@ -581,7 +633,10 @@ __device__ __forceinline__ unsigned long long det_key(const float* det, int a) {
   return ((unsigned long long)__float_as_uint(det[(size_t)a * 6 + 4]) << 32) | (unsigned)(~(unsigned)a);
 }
 
-__global__ __launch_bounds__(1024) void topk_nms_kernel(const NmsP p) {
+// Ragged batch (R = RaggedArgs): the epilogue's scale_boxes takes image b's pad / gain / source size from desc[b] instead of the launch's own.
+template <class... R>
+__global__ __launch_bounds__(1024) void topk_nms_kernel(const NmsP p, const R... ragged) {
+  constexpr bool RAGGED = sizeof...(R) != 0;
   __shared__ unsigned hist[256];
   __shared__ unsigned long long s_prefix;
   __shared__ int s_k;
@@ -720,17 +775,25 @@ __global__ __launch_bounds__(1024) void topk_nms_kernel(const NmsP p) {
     const float keep = (sup || tid >= K) ? 0.f : 1.f;
     float* o = p.out + ((size_t)b * kMaxDet + tid) * 6;
     // scale_boxes + clip_boxes (applied to zeroed rows too)
-    o[0] = fminf(fmaxf((x1 * keep - p.pad_x) / p.gain, 0.f), p.src_w);
-    o[1] = fminf(fmaxf((y1 * keep - p.pad_y) / p.gain, 0.f), p.src_h);
-    o[2] = fminf(fmaxf((x2 * keep - p.pad_x) / p.gain, 0.f), p.src_w);
-    o[3] = fminf(fmaxf((y2 * keep - p.pad_y) / p.gain, 0.f), p.src_h);
+    NmsP gr;
+    if constexpr (RAGGED) { const FrameDesc& d = ragged_args(ragged...).desc[b]; gr.pad_x = d.fpad_x; gr.pad_y = d.fpad_y; gr.gain = d.gain; gr.src_w = d.src_w; gr.src_h = d.src_h; }
+    const NmsP& g = RAGGED ? gr : p;
+    o[0] = fminf(fmaxf((x1 * keep - g.pad_x) / g.gain, 0.f), g.src_w);
+    o[1] = fminf(fmaxf((y1 * keep - g.pad_y) / g.gain, 0.f), g.src_h);
+    o[2] = fminf(fmaxf((x2 * keep - g.pad_x) / g.gain, 0.f), g.src_w);
+    o[3] = fminf(fmaxf((y2 * keep - g.pad_y) / g.gain, 0.f), g.src_h);
     o[4] = bx[tid][4] * keep;
     o[5] = cl * keep;
   }
 }
 
 void launch_topk_nms(const NmsP& p, hipStream_t stream) {
-  hipLaunchKernelGGL(topk_nms_kernel, dim3(p.B), dim3(1024), 0, stream, p);
+  hipLaunchKernelGGL(topk_nms_kernel<>, dim3(p.B), dim3(1024), 0, stream, p);
+  CC_HIP(hipGetLastError());
+}
+void launch_topk_nms_ragged(const NmsP& p, const FrameDesc* desc, hipStream_t stream) {
+  CC_CHECK(desc, "ragged NMS: no frame records");
+  hipLaunchKernelGGL(topk_nms_kernel<RaggedArgs>, dim3(p.B), dim3(1024), 0, stream, p, RaggedArgs{desc, 0});
   CC_HIP(hipGetLastError());
 }
 

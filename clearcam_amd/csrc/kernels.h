@@ -95,6 +95,21 @@ struct PreP {                 // letterbox: detection/yolov9.py:376-379,390-404
 };
 void launch_preprocess(int dt, const PreP& p, hipStream_t stream);
 
+// Ragged batch: B frames of different source sizes that letterbox to ONE network shape (Hn, Wn) run as one batch.  Only the letterbox in
+// front of the network and scale_boxes behind it know the source size; each reads this per-frame record from device memory, indexed
+// by the image index, instead of the single geometry PreP / NmsP carry.  One record per frame, 96 bytes.
+struct FrameDesc {
+  long long off;                          // byte offset of the frame in the packed buffer (PreP::frames); float32 frames: a multiple of 4
+  int H, W, nh, nw, pad_y, pad_x;         // source dims, resized dims, padding
+  const int* xlo; const int* xhi; const float* xfr;   // the frame's six axis tables (device; shared by every frame of that size)
+  const int* ylo; const int* yhi; const float* yfr;
+  float fpad_x, fpad_y, gain, src_w, src_h;           // scale_boxes, computed on the host as the uniform plan computes NmsP's
+  int reserved;
+};
+// PreP of a ragged launch: frames = the packed buffer, B, Hn, Wn, frame_f32, out, flip / div / sub / pad_val; H, W, nh, nw, pads and tables
+// are ignored (the records carry them).  packed_bytes = size of the packed buffer.
+void launch_preprocess_ragged(int dt, const PreP& p, const FrameDesc* desc, size_t packed_bytes, hipStream_t stream);
+
 // Letterbox fused into the detector's first conv (3x3 stride 2, 3 -> Cout, bias + SiLU): the network-input tensor
 // (B,Hn,Wn,8) is never written or read; 16-bit storage types only (detect.hip).
 struct StemP {
@@ -111,6 +126,10 @@ bool stem_fused_supported(int dt, int Cout);
 // split: tap_stride = 2*cin_pad, plane_off = 0 / cin_pad for the high / low plane) into the fused kernel's [Cout][32] rows
 void stem_pack_weights(int dt, const void* w_packed, int w_row, int tap_stride, int plane_off, int Cout, void* out, hipStream_t stream);
 void launch_stem_fused(int dt, const StemP& p, hipStream_t stream);
+// The same over a ragged batch (p.pre as launch_preprocess_ragged takes it).  big: the launch's scratch size - stem_needs_big() of any frame
+// of the batch (each block still tests whether ITS tile's source rectangle fits the stage and reads the frame directly where it does not).
+bool stem_needs_big(int H, int W, int nh, int nw, int frame_f32);
+void launch_stem_fused_ragged(int dt, const StemP& p, const FrameDesc* desc, size_t packed_bytes, bool big, hipStream_t stream);
 // tinygrad `interpolate(mode='linear', align_corners=False)` index tables for one axis, evaluated in float32 (yolo.hip)
 void axis_tables(int n_in, int n_out, std::vector<int>& lo, std::vector<int>& hi, std::vector<float>& fr);
 
@@ -158,6 +177,9 @@ struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yol
   float* out;                             // (B,300,6)
 };
 void launch_topk_nms(const NmsP& p, hipStream_t stream);
+// Ragged batch: image b's pad / gain / source size come from desc[b] (p's own are ignored).  `desc` is read when the kernel RUNS: inside a
+// captured graph it is a fixed device address whose contents the caller refreshes before each replay.
+void launch_topk_nms_ragged(const NmsP& p, const FrameDesc* desc, hipStream_t stream);
 
 // ---- CLIP towers (clip_kernels.hip) -------------------------------------------------------------
 // Plain GEMM through the conv kernel:  out[M][N] = act(A[M][K] W[N][K]^T + bias) (+res).

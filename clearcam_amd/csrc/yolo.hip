@@ -79,8 +79,19 @@ struct Plan {
   int* nonfinite = nullptr;                            // device counter of anchors with non-finite logits (decode / DDetect tail), summed over the plan's life
   hipGraphExec_t exec = nullptr;
   std::vector<hipEvent_t> lane_ev;                     // the cross-lane edges of the captured graph (run_ops_lanes)
+  // Ragged plan (cc_yolo_detect_ragged): B frames of ANY source sizes that letterbox to Hn x Wn; H, W, nh, nw = Hn, Wn and the pads are 0
+  // (placeholders).  The per-frame records live at the FIXED device address desc_dev - the NMS launch inside the captured graph reads it -
+  // and are refreshed from the pinned desc_host on the plan's stream before each replay.  desc_host is a single buffer, not a ring: before
+  // it is overwritten the host waits for desc_up, recorded right after the previous upload on this plan (a refinement of waiting for the
+  // slot's slot_done: the upload is the first thing a submission does, so the wait ends when the previous batch of the slot STARTS).
+  bool ragged = false;
+  FrameDesc* desc_dev = nullptr; FrameDesc* desc_host = nullptr; hipEvent_t desc_up = nullptr; bool desc_pending = false;
+  size_t packed_bytes = 0; bool stem_big = false;      // of the last call: size of the packed buffer, scratch size of the stem launch
   ~Plan() {
     if (exec) hipGraphExecDestroy(exec);
+    if (desc_up) hipEventDestroy(desc_up);
+    if (desc_host) hipHostFree(desc_host);
+    if (desc_dev) hipFree(desc_dev);
     for (hipEvent_t e : lane_ev) if (e) hipEventDestroy(e);
     for (void* p : {(void*)arena, (void*)xlo, (void*)xhi, (void*)ylo, (void*)yhi, (void*)xfr, (void*)yfr, frames_dev, (void*)det, (void*)out_dev, (void*)nonfinite})
       if (p) hipFree(p);
@@ -118,6 +129,12 @@ struct cc_yolo {
   bool finalized = false;
   PlanCache<std::vector<int>, Plan> plans;
   Plan* last = nullptr;
+  int plans_built = 0;                                 // plans built (arena + graph capture) over the handle's life: cc_yolo_plans_built
+  // Axis tables of the ragged entry points, one device allocation (lo | hi | fr) per distinct (n_in, n_out), least recently used dropped
+  // beyond kMaxAxisTabs (ragged_prepare): a site has a handful of camera models, so a frame's tables are almost always already there.
+  struct AxisTab { int* lo; int* hi; float* fr; unsigned long long used; };
+  std::map<std::pair<int, int>, AxisTab> axis_tabs;
+  unsigned long long axis_tick = 0;
   int cin_pad() const { return dtype == F32 ? 4 : 8; }
 };
 
@@ -922,7 +939,7 @@ static void launch_op(int dtype, const Plan* P, const Op& op, hipStream_t s, boo
     case 0: launch_conv(dtype, op.conv, s); break;
     case 1: launch_pool(dtype, op.pool, s); break;
     case 2: launch_decode(op.dec, s); break;
-    case 3: launch_topk_nms(op.nms, s); break;
+    case 3: if (P->ragged) launch_topk_nms_ragged(op.nms, P->desc_dev, s); else launch_topk_nms(op.nms, s); break;
     case 4: launch_fuse(dtype, op.fuse, s); break;
     case 5: if (with_stem) { StemP q = op.stem; q.pre.frames = P->last_frames; launch_stem_fused(dtype, q, s); } break;
     case 6: launch_csp_fused(dtype, op.csp, s); break;
@@ -995,31 +1012,48 @@ static void run_ops_lanes(cc_yolo* Y, Plan* P, hipStream_t s) {
 // The fused letterbox + first conv launches read the caller's frames, whose address changes from call to call, so they
 // stay outside the captured graph and run right before it.
 static void run_stems(cc_yolo* Y, Plan* P, const void* frames, hipStream_t s) {
-  for (Op& op : P->ops) if (op.kind == 5) { op.stem.pre.frames = frames; launch_stem_fused(Y->dtype, op.stem, s); }
+  for (Op& op : P->ops) if (op.kind == 5) {
+    op.stem.pre.frames = frames;
+    if (P->ragged) launch_stem_fused_ragged(Y->dtype, op.stem, P->desc_dev, P->packed_bytes, P->stem_big, s);
+    else launch_stem_fused(Y->dtype, op.stem, s);
+  }
 }
 
-static Plan* get_plan(cc_yolo* Y, int B, int H, int W, int frame_f32, int slot = 0) {
-  const std::vector<int> key{B, H, W, frame_f32, slot};
+// letterbox geometry, detection/yolov9.py:390-403 (python round = half-to-even)
+static void letterbox_geometry(int H, int W, int res, int& nh, int& nw, int& pad_y, int& pad_x) {
+  const double r = std::min((double)res / H, (double)res / W);
+  nw = round_half_even(W * r); nh = round_half_even(H * r);
+  const double dw = ((res - nw) % 32) / 2.0, dh = ((res - nh) % 32) / 2.0;
+  pad_x = round_half_even(dw - 0.1); pad_y = round_half_even(dh - 0.1);
+}
+static const char* kNot32 = "letterboxed frame is not a multiple of 32 (the reference graph cannot run this shape either)";
+
+// ragged: H x W IS the network shape; the key carries the flag and NOT the source sizes, so a camera that changes resolution keeps its graph
+static Plan* get_plan(cc_yolo* Y, int B, int H, int W, int frame_f32, int slot = 0, bool ragged = false) {
+  std::vector<int> key{B, H, W, frame_f32, slot};
+  if (ragged) key.push_back(1);
   if (Plan* hit = Y->plans.find(key)) return hit;
   std::unique_ptr<Plan> P(new Plan());
-  P->B = B; P->H = H; P->W = W; P->frame_f32 = frame_f32;
-  // letterbox geometry, detection/yolov9.py:390-403 (python round = half-to-even)
-  const int res = Y->res;
-  const double r = std::min((double)res / H, (double)res / W);
-  P->nw = round_half_even(W * r); P->nh = round_half_even(H * r);
-  const double dw = ((res - P->nw) % 32) / 2.0, dh = ((res - P->nh) % 32) / 2.0;
-  P->pad_x = round_half_even(dw - 0.1); P->pad_y = round_half_even(dh - 0.1);
+  P->B = B; P->H = H; P->W = W; P->frame_f32 = frame_f32; P->ragged = ragged;
+  if (ragged) { P->nh = H; P->nw = W; P->pad_x = P->pad_y = 0; }
+  else letterbox_geometry(H, W, Y->res, P->nh, P->nw, P->pad_y, P->pad_x);
   P->Hn = P->nh + 2 * P->pad_y; P->Wn = P->nw + 2 * P->pad_x;
-  CC_CHECK(P->Hn % 32 == 0 && P->Wn % 32 == 0 && P->Hn > 0 && P->Wn > 0,
-           "letterboxed frame is not a multiple of 32 (the reference graph cannot run this shape either)");
+  CC_CHECK(P->Hn % 32 == 0 && P->Wn % 32 == 0 && P->Hn > 0 && P->Wn > 0, kNot32);
   std::vector<int> lo, hi; std::vector<float> fr;
   axis_tables(W, P->nw, lo, hi, fr); P->xlo = to_device(lo); P->xhi = to_device(hi); P->xfr = to_device(fr);
   axis_tables(H, P->nh, lo, hi, fr); P->ylo = to_device(lo); P->yhi = to_device(hi); P->yfr = to_device(fr);
   Builder bld(Y, P.get());
   bld.build();
   bld.resolve();
-  P->frames_bytes = (size_t)B * H * W * 3 * (frame_f32 ? 4 : 1);
-  CC_HIP(hipMalloc(&P->frames_dev, P->frames_bytes));
+  if (ragged) {                                          // the staging buffer for host frames grows with the calls (stage_frames)
+    CC_HIP(hipMalloc((void**)&P->desc_dev, (size_t)B * sizeof(FrameDesc)));
+    CC_HIP(hipMemset(P->desc_dev, 0, (size_t)B * sizeof(FrameDesc)));
+    CC_HIP(hipHostMalloc((void**)&P->desc_host, (size_t)B * sizeof(FrameDesc)));
+    CC_HIP(hipEventCreateWithFlags(&P->desc_up, hipEventDisableTiming));
+  } else {
+    P->frames_bytes = (size_t)B * H * W * 3 * (frame_f32 ? 4 : 1);
+    CC_HIP(hipMalloc(&P->frames_dev, P->frames_bytes));
+  }
   // capture the launch list once; replay afterwards (the TinyJit role, helpers.py:214-221)
   hipGraph_t graph = nullptr;
   CC_HIP(hipStreamBeginCapture(Y->stream, hipStreamCaptureModeThreadLocal));
@@ -1027,6 +1061,7 @@ static Plan* get_plan(cc_yolo* Y, int B, int H, int W, int frame_f32, int slot =
   CC_HIP(hipStreamEndCapture(Y->stream, &graph));
   CC_HIP(hipGraphInstantiate(&P->exec, graph, nullptr, nullptr, 0));
   CC_HIP(hipGraphDestroy(graph));
+  ++Y->plans_built;
   // a plan that cc_yolo_get_tensor / cc_yolo_profile still point at must not dangle when it is evicted
   return Y->plans.insert(key, std::move(P), Y->stream, [&](Plan* gone) {
     for (hipStream_t t : Y->slot_stream) hipStreamSynchronize(t);        // the evicted plan may be running on a slot's stream
@@ -1153,6 +1188,10 @@ int cc_version(void) { return 100; }
 int cc_device_count(int* n) { CC_API_BEGIN CC_HIP(hipGetDeviceCount(n)); CC_API_END }
 
 static void input_step(cc_yolo* h, Plan* P, hipStream_t s, const void* fdev);   // letterbox (below)
+static void detect_on_plan(cc_yolo* h, Plan* P, const void* frames, size_t bytes, int frames_on_device, float* out, int out_on_device, void* stream);
+static int next_slot(cc_yolo* h);
+static void submit_on_plan(cc_yolo* h, Plan* P, int slot, const void* frames, size_t bytes, int frames_on_device, float* out, int out_on_device,
+                           void* stream, long long* ticket);
 
 // dtype "f16c": the float32 weights of the 1x1 convs in h->host are replaced by f16-representable values chosen by the GPTQ recursion
 // (calibrate.hip) on the second moments of each conv's own input - measured on an f32 twin of the handle running the calibration frames
@@ -1360,8 +1399,27 @@ static void input_step(cc_yolo* h, Plan* P, hipStream_t s, const void* fdev) {
   pp.out = P->arena + P->bufs[P->in_buf].off; pp.out_c = P->bufs[P->in_buf].C;
   pp.flip = 1; pp.div = 255.0f; pp.sub = 0.0f; pp.pad_val = 0.0f;          // [..., ::-1] and / 255.0 (detection/yolov9.py:377-379)
   if (P->fused_stem) run_stems(h, P, fdev, s);
+  else if (P->ragged) launch_preprocess_ragged(h->dtype, pp, P->desc_dev, P->packed_bytes, s);
   else launch_preprocess(h->dtype, pp, s);
   P->last_frames = fdev;
+}
+// Host frames go through the plan's staging buffer.  A uniform plan's is allocated with the plan; a ragged plan's grows to the largest
+// packed buffer seen (hipFree waits for the device, so no batch in flight still reads the old one).
+static const void* stage_frames(Plan* P, const void* frames, size_t bytes, hipStream_t s) {
+  if (P->frames_bytes < bytes) {
+    if (P->frames_dev) { CC_HIP(hipFree(P->frames_dev)); P->frames_dev = nullptr; P->frames_bytes = 0; }
+    CC_HIP(hipMalloc(&P->frames_dev, bytes));
+    P->frames_bytes = bytes;
+  }
+  CC_HIP(hipMemcpyAsync(P->frames_dev, frames, bytes, hipMemcpyHostToDevice, s));
+  return P->frames_dev;
+}
+// ragged plan: this call's records go up on the plan's stream, ahead of the stem launches and the graph that read them
+static void upload_desc(Plan* P, hipStream_t s) {
+  if (!P->ragged) return;
+  CC_HIP(hipMemcpyAsync(P->desc_dev, P->desc_host, (size_t)P->B * sizeof(FrameDesc), hipMemcpyHostToDevice, s));
+  CC_HIP(hipEventRecord(P->desc_up, s));
+  P->desc_pending = true;
 }
 static void enqueue_step(cc_yolo* h, Plan* P, hipStream_t s, const void* fdev) {
   input_step(h, P, s, fdev);
@@ -1385,13 +1443,20 @@ int cc_yolo_detect(cc_yolo* h, const void* frames, int B, int H, int W, int fram
   CC_CHECK(B > 0 && H > 0 && W > 0, "bad frame shape");
   CC_HIP(hipSetDevice(h->device));
   Plan* P = get_plan(h, B, H, W, frame_f32 ? 1 : 0);
+  detect_on_plan(h, P, frames, P->frames_bytes, frames_on_device, out, out_on_device, stream);
+  CC_API_END
+}
+
+// cc_yolo_detect / cc_yolo_detect_ragged from the plan on: `bytes` of frames (uniform: B*H*W*3 elements; ragged: the packed buffer)
+static void detect_on_plan(cc_yolo* h, Plan* P, const void* frames, size_t bytes, int frames_on_device, float* out, int out_on_device, void* stream) {
+  const int B = P->B;
   hipStream_t s = h->stream;
   if (stream) {   // order our stream after the caller's
     hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     CC_HIP(hipEventRecord(e, (hipStream_t)stream)); CC_HIP(hipStreamWaitEvent(s, e, 0)); CC_HIP(hipEventDestroy(e));
   }
-  const void* fdev = frames;
-  if (!frames_on_device) { CC_HIP(hipMemcpyAsync(P->frames_dev, frames, P->frames_bytes, hipMemcpyHostToDevice, s)); fdev = P->frames_dev; }
+  const void* fdev = frames_on_device ? frames : stage_frames(P, frames, bytes, s);
+  upload_desc(P, s);
   // the plan's non-finite counter sums over the plan's life (device-output / submitted batches are read by cc_yolo_nonfinite): a host-output
   // call answers for ITS OWN batch only - the counter is snapshotted before the step and the difference is what this call reports
   if (!out_on_device) CC_HIP(hipMemcpyAsync(h->nonfinite_host + 1, P->nonfinite, 4, hipMemcpyDeviceToHost, s));
@@ -1420,7 +1485,6 @@ int cc_yolo_detect(cc_yolo* h, const void* frames, int B, int H, int W, int fram
     }
   }
   h->last = P;
-  CC_API_END
 }
 
 // taps and profilers read what the last call left behind: every stream of the handle has to be idle
@@ -1452,9 +1516,22 @@ int cc_yolo_submit(cc_yolo* h, const void* frames, int B, int H, int W, int fram
   CC_CHECK(h->finalized, "cc_yolo_submit before cc_yolo_finalize");
   CC_CHECK(B > 0 && H > 0 && W > 0, "bad frame shape");
   CC_HIP(hipSetDevice(h->device));
-  if (h->slot_done.empty()) { hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->slot_done.push_back(e); }
-  const int depth = (int)h->slot_stream.size() + 1, slot = (int)(h->submitted % depth);
+  const int slot = next_slot(h);
   Plan* P = get_plan(h, B, H, W, frame_f32 ? 1 : 0, slot);
+  submit_on_plan(h, P, slot, frames, P->frames_bytes, frames_on_device, out, out_on_device, stream, ticket);
+  CC_API_END
+}
+
+// the slot the next submission runs on (round robin over the in-flight depth)
+static int next_slot(cc_yolo* h) {
+  if (h->slot_done.empty()) { hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->slot_done.push_back(e); }
+  const int depth = (int)h->slot_stream.size() + 1;
+  return (int)(h->submitted % depth);
+}
+// cc_yolo_submit / cc_yolo_submit_ragged from the plan on (`bytes` as detect_on_plan)
+static void submit_on_plan(cc_yolo* h, Plan* P, int slot, const void* frames, size_t bytes, int frames_on_device, float* out, int out_on_device,
+                           void* stream, long long* ticket) {
+  const int B = P->B;
   hipStream_t s = h->stream_of_slot(slot);
   if (stream) {   // the frames are ready on the caller's stream; the caller's stream is NOT made to wait for the result (cc_yolo_wait does that)
     hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1462,14 +1539,13 @@ int cc_yolo_submit(cc_yolo* h, const void* frames, int B, int H, int W, int fram
   }
   // host frames / rows (pinned, or the copies are not asynchronous): upload, detect and download are one in-order chain on the slot's
   // stream, and the chains of the slots overlap - the upload of one batch runs under the convs of another
-  const void* fdev = frames;
-  if (!frames_on_device) { CC_HIP(hipMemcpyAsync(P->frames_dev, frames, P->frames_bytes, hipMemcpyHostToDevice, s)); fdev = P->frames_dev; }
+  const void* fdev = frames_on_device ? frames : stage_frames(P, frames, bytes, s);
+  upload_desc(P, s);
   enqueue_step(h, P, s, fdev);
   CC_HIP(hipMemcpyAsync(out, P->out_dev, (size_t)B * CC_MAX_DET * 6 * 4, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
   CC_HIP(hipEventRecord(h->slot_done[slot], s));
   h->last = P;
   *ticket = h->submitted++;
-  CC_API_END
 }
 
 int cc_yolo_wait(cc_yolo* h, long long ticket, void* stream) {
@@ -1483,6 +1559,118 @@ int cc_yolo_wait(cc_yolo* h, long long ticket, void* stream) {
   hipEvent_t e = h->slot_done[(int)(ticket % depth)];
   if (stream) CC_HIP(hipStreamWaitEvent((hipStream_t)stream, e, 0));
   else CC_HIP(hipEventSynchronize(e));
+  CC_API_END
+}
+
+int cc_letterbox_geometry(int H, int W, int res, int* nh, int* nw, int* pad_y, int* pad_x) {
+  CC_API_BEGIN
+  CC_CHECK(H > 0 && W > 0 && res > 0 && nh && nw && pad_y && pad_x, "bad argument");
+  letterbox_geometry(H, W, res, *nh, *nw, *pad_y, *pad_x);
+  CC_API_END
+}
+
+// The frame's tables for one axis, from the handle's cache (built and uploaded the first time a size is seen).
+static cc_yolo::AxisTab& axis_tab(cc_yolo* h, int n_in, int n_out) {
+  auto it = h->axis_tabs.find({n_in, n_out});
+  if (it == h->axis_tabs.end()) {
+    std::vector<int> lo, hi; std::vector<float> fr;
+    axis_tables(n_in, n_out, lo, hi, fr);
+    char* d = nullptr;
+    CC_HIP(hipMalloc((void**)&d, (size_t)n_out * 12 + 16));
+    CC_HIP(hipMemcpy(d, lo.data(), (size_t)n_out * 4, hipMemcpyHostToDevice));
+    CC_HIP(hipMemcpy(d + (size_t)n_out * 4, hi.data(), (size_t)n_out * 4, hipMemcpyHostToDevice));
+    CC_HIP(hipMemcpy(d + (size_t)n_out * 8, fr.data(), (size_t)n_out * 4, hipMemcpyHostToDevice));
+    it = h->axis_tabs.emplace(std::make_pair(n_in, n_out), cc_yolo::AxisTab{(int*)d, (int*)(d + (size_t)n_out * 4), (float*)(d + (size_t)n_out * 8), 0}).first;
+  }
+  it->second.used = ++h->axis_tick;
+  return it->second;
+}
+constexpr size_t kMaxAxisTabs = 256;
+
+// Checks a ragged call, finds (or builds) its plan and fills the plan's pinned records; *bytes = size of the packed buffer.
+static Plan* ragged_prepare(cc_yolo* h, const void* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B,
+                            int frame_f32, int slot, size_t* bytes) {
+  CC_CHECK(pixels && offsets && heights && widths && B > 0, "null argument / empty batch");
+  const size_t es = frame_f32 ? 4 : 1;
+  struct Geo { int nh, nw, pad_y, pad_x; };
+  std::vector<Geo> geo(B);
+  int Hn = 0, Wn = 0;
+  size_t end = 0;
+  for (int b = 0; b < B; ++b) {
+    const std::string who = "frame " + std::to_string(b) + " (" + std::to_string(heights[b]) + "x" + std::to_string(widths[b]) + ")";
+    if (heights[b] <= 0 || widths[b] <= 0 || offsets[b] < 0) throw cc::Error(-22, who + ": bad shape or offset");
+    if (frame_f32 && offsets[b] % 4 != 0) throw cc::Error(-22, who + ": float32 frames must start at a multiple of 4 bytes");
+    Geo& g = geo[b];
+    letterbox_geometry(heights[b], widths[b], h->res, g.nh, g.nw, g.pad_y, g.pad_x);
+    const int hn = g.nh + 2 * g.pad_y, wn = g.nw + 2 * g.pad_x;
+    if (!(hn % 32 == 0 && wn % 32 == 0 && hn > 0 && wn > 0 && g.nh > 0 && g.nw > 0)) throw cc::Error(-22, who + ": " + kNot32);
+    if (b == 0) { Hn = hn; Wn = wn; }
+    else if (hn != Hn || wn != Wn)
+      throw cc::Error(-22, who + " letterboxes to " + std::to_string(hn) + "x" + std::to_string(wn) + " but frame 0 (" + std::to_string(heights[0]) + "x" +
+                               std::to_string(widths[0]) + ") to " + std::to_string(Hn) + "x" + std::to_string(Wn) +
+                               ": the frames of one ragged batch must share one network shape (group them with cc_letterbox_geometry)");
+    end = std::max(end, (size_t)offsets[b] + (size_t)heights[b] * widths[b] * 3 * es);
+  }
+  Plan* P = get_plan(h, B, Hn, Wn, frame_f32 ? 1 : 0, slot, true);
+  // the pinned records may still be the source of the previous upload on this plan (see Plan): wait for that copy, not for the batch
+  if (P->desc_pending) { CC_HIP(hipEventSynchronize(P->desc_up)); P->desc_pending = false; }
+  if (h->axis_tabs.size() > kMaxAxisTabs) {             // bounded: drop the least recently used half once nothing in flight can read them
+    sync_all(h);
+    std::vector<std::pair<unsigned long long, std::pair<int, int>>> byage;
+    for (auto& kv : h->axis_tabs) byage.emplace_back(kv.second.used, kv.first);
+    std::sort(byage.begin(), byage.end());
+    for (size_t i = 0; i < byage.size() / 2; ++i) { hipFree(h->axis_tabs[byage[i].second].lo); h->axis_tabs.erase(byage[i].second); }
+  }
+  bool big = false;
+  for (int b = 0; b < B; ++b) {
+    const Geo& g = geo[b];
+    const int H = heights[b], W = widths[b];
+    FrameDesc d{};
+    d.off = offsets[b]; d.H = H; d.W = W; d.nh = g.nh; d.nw = g.nw; d.pad_y = g.pad_y; d.pad_x = g.pad_x;
+    const cc_yolo::AxisTab &tx = axis_tab(h, W, g.nw), &ty = axis_tab(h, H, g.nh);
+    d.xlo = tx.lo; d.xhi = tx.hi; d.xfr = tx.fr; d.ylo = ty.lo; d.yhi = ty.hi; d.yfr = ty.fr;
+    // scale_boxes exactly as the uniform plan's NMS launch gets it (Builder::head_finish): double arithmetic, then one cast to float
+    const double gain = std::min((double)Hn / H, (double)Wn / W);
+    d.gain = (float)gain;
+    d.fpad_x = (float)((Wn - W * gain) / 2); d.fpad_y = (float)((Hn - H * gain) / 2);
+    d.src_w = (float)W; d.src_h = (float)H;
+    P->desc_host[b] = d;
+    big = big || stem_needs_big(H, W, g.nh, g.nw, frame_f32);
+  }
+  P->stem_big = big; P->packed_bytes = end;
+  *bytes = end;
+  return P;
+}
+
+int cc_yolo_detect_ragged(cc_yolo* h, const void* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B,
+                          int frame_f32, int pixels_on_device, float* out, int out_on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && out, "null argument");
+  CC_CHECK(h->finalized, "cc_yolo_detect_ragged before cc_yolo_finalize");
+  CC_HIP(hipSetDevice(h->device));
+  size_t bytes = 0;
+  Plan* P = ragged_prepare(h, pixels, offsets, heights, widths, B, frame_f32, 0, &bytes);
+  detect_on_plan(h, P, pixels, bytes, pixels_on_device, out, out_on_device, stream);
+  CC_API_END
+}
+
+int cc_yolo_submit_ragged(cc_yolo* h, const void* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B,
+                          int frame_f32, int pixels_on_device, float* out, int out_on_device, void* stream, long long* ticket) {
+  CC_API_BEGIN
+  CC_CHECK(h && out && ticket, "null argument");
+  CC_CHECK(h->finalized, "cc_yolo_submit_ragged before cc_yolo_finalize");
+  CC_HIP(hipSetDevice(h->device));
+  const int slot = next_slot(h);
+  size_t bytes = 0;
+  Plan* P = ragged_prepare(h, pixels, offsets, heights, widths, B, frame_f32, slot, &bytes);
+  submit_on_plan(h, P, slot, pixels, bytes, pixels_on_device, out, out_on_device, stream, ticket);
+  CC_API_END
+}
+
+int cc_yolo_plans_built(cc_yolo* h, int* n) {
+  CC_API_BEGIN
+  CC_CHECK(h && n, "null argument");
+  *n = h->plans_built;
   CC_API_END
 }
 
@@ -1509,7 +1697,8 @@ static int get_tensor_frames(cc_yolo* h, const char* name, int b0, int nb, float
     PreP pp{};
     for (const Op& op : P->ops) if (op.kind == 5) { pp = op.stem.pre; break; }
     pp.frames = P->last_frames; pp.out = P->arena + b.off; pp.out_c = b.C;
-    launch_preprocess(h->dtype, pp, h->stream);
+    if (P->ragged) launch_preprocess_ragged(h->dtype, pp, P->desc_dev, P->packed_bytes, h->stream);   // the records of the last call are still there
+    else launch_preprocess(h->dtype, pp, h->stream);
     CC_HIP(hipStreamSynchronize(h->stream));
   }
   const int C = !strcmp(name, "input") ? 3 : b.C;
@@ -1569,6 +1758,7 @@ int cc_yolo_profile(cc_yolo* h, int iters, float* ms, double* alg_macs_per_step,
   CC_API_BEGIN
   CC_CHECK(h && ms && h->last && iters > 0, "bad argument / no detect call yet");
   Plan* P = h->last;
+  CC_CHECK(!P->ragged, "cc_yolo_profile: the last call was a ragged batch - profile the uniform plan of the same network shape");
   CC_HIP(hipSetDevice(h->device));
   sync_all(h);
   hipStream_t s = h->stream;
@@ -1667,6 +1857,7 @@ int cc_yolo_profile_graph(cc_yolo* h, int iters, int which, float* ms_per_replay
   CC_API_BEGIN
   CC_CHECK(h && ms_per_replay && h->last && iters > 0 && which >= 0 && which <= 2, "bad argument / no detect call yet");
   Plan* P = h->last;
+  CC_CHECK(!P->ragged, "cc_yolo_profile_graph: the last call was a ragged batch - profile the uniform plan of the same network shape");
   CC_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   sync_all(h);
@@ -1699,6 +1890,7 @@ void cc_yolo_destroy(cc_yolo* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   for (hipStream_t t : h->slot_stream) hipStreamSynchronize(t);
   h->plans.clear();
+  for (auto& kv : h->axis_tabs) hipFree(kv.second.lo);
   for (auto& kv : h->packed) { hipFree(kv.second.w); hipFree(kv.second.bias); }
   if (h->dfl_w) hipFree(h->dfl_w);
   if (h->ev0) hipEventDestroy(h->ev0);

@@ -258,7 +258,7 @@ class StreamPipeline:
         pool.shutdown()
         dt = time.perf_counter() - t0
         frames = n_batches * self.n
-        nbytes = self.n * self.hw[0] * self.hw[1] * 3
+        nbytes = self._tick_bytes()
         lat = sorted(self.latency)
         return {"cameras": self.n, "frame_hw": list(self.hw), "batches": n_batches, "frames_per_sec": frames / dt,
                 "fps_per_camera": frames / dt / self.n, "ms_per_batch": dt / n_batches * 1e3,
@@ -268,10 +268,160 @@ class StreamPipeline:
                 "det_thresh": self.det_thresh, "dets_above_thresh_per_frame": self.n_dets / frames,
                 "tracks_alive": int(sum(t.num_tracks() for t in self.trackers)), "tracker_threads": self.n_threads}
 
+    def _tick_bytes(self) -> int:
+        return self.n * self.hw[0] * self.hw[1] * 3
+
     def close(self):
         for t in self.trackers:
             t.close()
         getattr(self.model, "_pipelines", set()).discard(self)
+
+
+class MixedCameraBank(list):
+    """Cameras of DIFFERENT resolutions writing into ONE pinned flat buffer (ring, total bytes): camera i owns the byte range
+    [offsets[i], offsets[i] + h_i * w_i * 3) of every ring slot, so a tick still goes up as a single copy.  sizes: (h, w) per camera,
+    in camera order.  A list of the SyntheticCamera objects plus read_all()."""
+
+    def __init__(self, sizes: Sequence, ring: int = 3, seed: int = 100):
+        import torch
+        self.sizes = [(int(h), int(w)) for h, w in sizes]
+        nbytes = [h * w * 3 for h, w in self.sizes]
+        self.offsets = [int(v) for v in np.concatenate([[0], np.cumsum(nbytes)[:-1]])]
+        self.total = int(sum(nbytes))
+        self.bank = torch.empty((ring, self.total), dtype=torch.uint8).pin_memory()
+        bases: Dict[tuple, np.ndarray] = {}
+        cams = []
+        for i, ((h, w), off, n) in enumerate(zip(self.sizes, self.offsets, nbytes)):
+            if (h, w) not in bases:
+                bases[(h, w)] = np.random.default_rng(seed + len(bases)).integers(0, 256, (h, w, 3), dtype=np.uint8)
+            cams.append(SyntheticCamera(h, w, seed=i, ring=ring, base=bases[(h, w)], storage=self.bank[:, off:off + n].unflatten(1, (h, w, 3))))
+        super().__init__(cams)
+        self.ring, self.t = ring, 0
+
+    def read_all(self):
+        """The next frame of every camera as one pinned (total bytes,) uint8 tensor (no copy)."""
+        f = self.bank[self.t % self.ring]
+        self.t += 1
+        for c in self:
+            c.t = self.t
+        return f
+
+
+class _MixedSlot:
+    def __init__(self, n, total, dev):
+        import torch
+        self.frames = torch.empty((total,), dtype=torch.uint8, device=dev)      # the tick's frames, camera after camera
+        self.out = torch.empty((n, 300, 6), dtype=torch.float32, device=dev)    # rows in GROUP order (each ragged batch writes one range)
+        self.host_out = torch.empty((n, 300, 6), dtype=torch.float32).pin_memory()
+        self.ups, self.done = [torch.cuda.Event()], torch.cuda.Event()
+        self.ticket = None
+        self.t_submit = 0.0
+
+
+class MixedStreamPipeline(StreamPipeline):
+    """StreamPipeline for cameras of different resolutions: frame_hws = (h, w) per camera.  The cameras are grouped by network shape
+    ONCE, here; a tick is one upload of the flat frame buffer (MixedCameraBank's layout) and one ragged batch per group
+    (YOLOv9.detect_ragged_device) on the one detector stream, `depth` ticks in flight - the many-camera regime of StreamPipeline.  A site
+    with 1080p, 720p and 4K cameras is one group; without this class it is one uniform pipeline, arena and small batch per source size.
+    collect() returns rows and trackers per camera, in camera order."""
+
+    def __init__(self, model, frame_hws: Sequence, depth: int = 2, det_thresh: float = 0.25, tracker_kwargs: Optional[dict] = None,
+                 n_threads: Optional[int] = None, track: bool = True):
+        import torch
+        self.torch = torch
+        self.model, self.hw = model, [(int(h), int(w)) for h, w in frame_hws]
+        self.n = n_cams = len(self.hw)
+        self.dev = torch.device("cuda", model.device)
+        key = (self.dev.index, 1)
+        if key not in _STREAMS:                                  # the process-wide streams of StreamPipeline
+            _STREAMS[key] = ([torch.cuda.Stream(self.dev, priority=-1)], torch.cuda.Stream(self.dev))
+        self.copy_streams, self.compute_stream = _STREAMS[key]
+        self.copy_stream = self.copy_streams[0]
+        nbytes = [h * w * 3 for h, w in self.hw]
+        self.offsets = [int(v) for v in np.concatenate([[0], np.cumsum(nbytes)[:-1]])]
+        self.total = int(sum(nbytes))
+        by_shape: Dict[tuple, List[int]] = {}
+        for i, (h, w) in enumerate(self.hw):
+            by_shape.setdefault(model.network_shape(h, w), []).append(i)
+        # group -> (cameras, offsets, heights, widths, first row); `order` = camera of every row of the grouped output
+        self.groups, self.order = [], []
+        for shape, cams in by_shape.items():
+            self.groups.append((cams, np.ascontiguousarray([self.offsets[i] for i in cams], np.int64), np.ascontiguousarray([self.hw[i][0] for i in cams], np.int32),
+                                np.ascontiguousarray([self.hw[i][1] for i in cams], np.int32), len(self.order)))
+            self.order += cams
+        self.row_of_cam = np.argsort(np.asarray(self.order))
+        self.depth, self.in_flight = depth, False
+        self.slots = [_MixedSlot(n_cams, self.total, self.dev) for _ in range(depth)]
+        users = getattr(model, "_pipelines", None)
+        if users is None:
+            users = model._pipelines = weakref.WeakSet()
+        users.add(self)
+        if n_threads is None:
+            try:
+                n_threads = len(os.sched_getaffinity(0))
+            except AttributeError:
+                n_threads = os.cpu_count() or 1
+            n_threads = max(1, min(32, n_threads, n_cams))
+        self.det_thresh, self.n_threads, self.track = det_thresh, n_threads, track
+        self.trackers = [OCSort(**(tracker_kwargs or {"max_age": 100})) for _ in range(n_cams)]   # per camera, in camera order
+        self.submitted = self.collected = 0
+        self.track_s = 0.0
+        self.n_dets = 0
+        self.latency: List[float] = []
+
+    def submit(self, frames=None) -> None:
+        """frames: the tick's pinned flat uint8 tensor (MixedCameraBank.read_all: one upload), or one pinned (h_i,w_i,3) uint8 tensor
+        per camera (one upload each); None = re-run the frames already resident in the slot."""
+        torch = self.torch
+        if self.submitted - self.collected >= self.depth:
+            raise RuntimeError("too many batches in flight: call collect() first")
+        s = self.slots[self.submitted % self.depth]
+        s.t_submit = time.perf_counter()
+        whole = frames is not None and hasattr(frames, "dim") and frames.dim() == 1
+        if frames is not None and not whole and len(frames) != self.n:
+            raise ValueError(f"expected {self.n} frames, got {len(frames)}")
+        if whole and frames.numel() != self.total:
+            raise ValueError(f"expected a flat buffer of {self.total} bytes, got {frames.numel()}")
+        st = self.compute_stream
+        if frames is not None:
+            with torch.cuda.stream(self.copy_stream):
+                if whole:
+                    s.frames.copy_(frames, non_blocking=True)
+                else:
+                    for i, f in enumerate(frames):
+                        if tuple(f.shape) != self.hw[i] + (3,):
+                            raise ValueError(f"camera {i}: expected a {self.hw[i] + (3,)} frame, got {tuple(f.shape)}")
+                        s.frames[self.offsets[i]:self.offsets[i] + f.numel()].copy_(f.reshape(-1), non_blocking=True)
+                s.ups[0].record(self.copy_stream)
+            st.wait_event(s.ups[0])
+        with torch.cuda.stream(st):
+            for cams, offs, hs, ws, r0 in self.groups:
+                self.model.detect_ragged_device(s.frames, offs, hs, ws, s.out[r0:r0 + len(cams)])
+            s.host_out.copy_(s.out, non_blocking=True)
+            s.done.record(st)
+        self.submitted += 1
+
+    def _wait(self, s) -> np.ndarray:
+        """-> (N,300,6) float32 rows in CAMERA order (a copy)."""
+        s.done.synchronize()
+        return s.host_out.numpy()[self.row_of_cam]
+
+    def _tick_bytes(self) -> int:
+        return self.total
+
+
+def parse_mix(spec: str) -> List[tuple]:
+    """"1080x1920:32,720x1280:16" -> [(1080, 1920)] * 32 + [(720, 1280)] * 16 (height x width : cameras)."""
+    out: List[tuple] = []
+    for part in spec.split(","):
+        hw, _, n = part.strip().partition(":")
+        h, _, w = hw.lower().partition("x")
+        if not (h.isdigit() and w.isdigit() and (n == "" or n.isdigit())) or int(h) < 1 or int(w) < 1:
+            raise ValueError(f"bad --mix entry {part!r}: HEIGHTxWIDTH:CAMERAS")
+        out += [(int(h), int(w))] * (int(n) if n else 1)
+    if not out:
+        raise ValueError("empty --mix")
+    return out
 
 
 def make_cameras(n: int, height: int = 1080, width: int = 1920, ring: Optional[int] = None, seed: int = 100, bank: bool = True) -> List[SyntheticCamera]:
@@ -333,10 +483,20 @@ def main() -> None:
     ap.add_argument("--thresh", type=float, default=0.25, help="tracker score threshold (clearcam's detection threshold setting)")
     ap.add_argument("--cls-bias-shift", type=float, default=0.0, help="move the synthetic class-logit biases (sparser detections)")
     ap.add_argument("--depth", type=int, default=None, help="batches in flight in the pipeline (default: 4 with detector slots, else 2)")
+    ap.add_argument("--mix", default=None, help="cameras of several resolutions in one pipeline, HEIGHTxWIDTH:CAMERAS,...  e.g. "
+                    "1080x1920:32,720x1280:16,2160x3840:8,480x640:8 (replaces --cams / --height / --width; grouped by network shape into ragged batches)")
     ap.add_argument("--in-flight", type=int, default=None, choices=[0, 1],
                     help="1: one detector slot per batch in flight (YOLOv9.submit: upload -> detect -> download chains that overlap); default: up to 8 cameras")
     a = ap.parse_args()
     model = YOLOv9(a.size, a.res, state_dict=shift_class_bias(synthetic_yolov9_state_dict(a.size, 1234), a.cls_bias_shift), dtype=a.dtype)
+    if a.mix:
+        sizes = parse_mix(a.mix)
+        pipe = MixedStreamPipeline(model, sizes, depth=a.depth or 2, det_thresh=a.thresh)
+        cams = None if a.resident else MixedCameraBank(sizes, ring=pipe.depth + 1)
+        stats = pipe.run(cams, a.batches)
+        stats["network_shapes"] = {f"{hn}x{wn}": sum(1 for hw in sizes if model.network_shape(*hw) == (hn, wn)) for hn, wn in sorted({model.network_shape(*hw) for hw in sizes})}
+        print(json.dumps(stats))
+        return
     pipe = StreamPipeline(model, a.cams, (a.height, a.width), depth=a.depth, det_thresh=a.thresh, in_flight=None if a.in_flight is None else bool(a.in_flight))
     cams = None if a.resident else make_cameras(a.cams, a.height, a.width, ring=pipe.depth + 1)   # a frame stays the source of an upload for `depth` ticks
     print(json.dumps(pipe.run(cams, a.batches)))

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -27,6 +27,97 @@ from .weights import load_safetensors
 # to 11 / 8 bits: speed modes.  "f32" is the exact-arithmetic parity mode.
 DTYPES = {"f32": 0, "float32": 0, "f16": 1, "float16": 1, "half": 1, "bf16": 2, "bfloat16": 2, "f16s": 3, "f16_split": 3, "f16h": 4, "f16c": 5}
 MAX_DET = 300
+
+
+# -- ragged batches: frames of different sizes that letterbox to one network shape ------------------------------------------------------
+def letterbox_geometry(h: int, w: int, res: int) -> Tuple[int, int, int, int]:
+    """(new_h, new_w, pad_y, pad_x) of an h x w frame letterboxed to `res` (yolov9.py:390-403), from the library's host-only helper: the
+    very values the ragged entry points group by."""
+    v = [C.c_int() for _ in range(4)]
+    _lib.check(_lib.lib().cc_letterbox_geometry(int(h), int(w), int(res), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def network_shape(h: int, w: int, res: int) -> Tuple[int, int]:
+    """(Hn, Wn): what the network sees of an h x w frame at `res`.  Frames with the same network shape can share a ragged batch."""
+    nh, nw, py, px = letterbox_geometry(h, w, res)
+    return nh + 2 * py, nw + 2 * px
+
+
+class RaggedGroup:
+    """The frames of a detect_frames call that run as ONE ragged batch: same network shape, same element type, same residency.
+    index: their positions in the caller's list; offsets / heights / widths: the three host tables of cc_yolo_detect_ragged for the
+    frames packed back to back in that order; nbytes: size of the packed buffer."""
+
+    def __init__(self, shape, f32, on_device):
+        self.shape, self.f32, self.on_device = shape, f32, on_device
+        self.index: List[int] = []
+        self.heights: List[int] = []
+        self.widths: List[int] = []
+
+    def finish(self):
+        es = 4 if self.f32 else 1
+        sizes = np.asarray(self.heights, np.int64) * np.asarray(self.widths, np.int64) * 3 * es
+        self.offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64))
+        self.nbytes = int(sizes.sum())
+        self.heights = np.ascontiguousarray(self.heights, np.int32)
+        self.widths = np.ascontiguousarray(self.widths, np.int32)
+        return self
+
+    def tables(self):
+        i32p = C.POINTER(C.c_int32)
+        return (self.offsets.ctypes.data_as(C.POINTER(C.c_int64)), self.heights.ctypes.data_as(i32p), self.widths.ctypes.data_as(i32p))
+
+
+def _frame_kind(i: int, f):
+    """(h, w, is_f32, on_device) of frame i, ValueError naming i otherwise."""
+    on_dev = bool(getattr(f, "is_cuda", False))
+    shape = tuple(getattr(f, "shape", ()))
+    if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"frame {i}: must be (H,W,3), got shape {shape}")
+    dt = str(f.dtype).replace("torch.", "")
+    if dt not in ("uint8", "float32"):
+        raise ValueError(f"frame {i}: must be uint8 or float32, got {dt}")
+    return int(shape[0]), int(shape[1]), dt == "float32", on_dev
+
+
+def group_frames(frames: Sequence, res: int) -> List[RaggedGroup]:
+    """The host part of detect_frames, a pure function of the frames' shapes and dtypes: one RaggedGroup per (network shape, element
+    type, residency) in order of first appearance, frames inside a group in input order.  ValueError (with the frame's index) for a
+    frame that is not (H,W,3) uint8 / float32 or whose letterbox is not a multiple of 32."""
+    groups: Dict[tuple, RaggedGroup] = {}
+    for i, f in enumerate(frames):
+        h, w, f32, on_dev = _frame_kind(i, f)
+        hn, wn = network_shape(h, w, res)
+        if hn <= 0 or wn <= 0 or hn % 32 or wn % 32:
+            raise ValueError(f"frame {i}: {h}x{w} letterboxes to {hn}x{wn} at res {res}, not a multiple of 32 (the reference graph cannot run this shape either)")
+        g = groups.setdefault((hn, wn, f32, on_dev), RaggedGroup((hn, wn), f32, on_dev))
+        g.index.append(i); g.heights.append(h); g.widths.append(w)
+    return [g.finish() for g in groups.values()]
+
+
+def pack_group(frames: Sequence, g: RaggedGroup, buf: np.ndarray) -> np.ndarray:
+    """Host frames of group g, back to back, into the uint8 buffer `buf` (>= g.nbytes; e.g. a view of pinned memory): one copy per frame."""
+    for i, off in zip(g.index, g.offsets):
+        a = np.ascontiguousarray(as_numpy(frames[i]))
+        n = a.nbytes
+        buf[off:off + n] = a.reshape(-1).view(np.uint8)
+    return buf
+
+
+def scatter_rows(groups: Sequence[RaggedGroup], outs: Sequence[np.ndarray], n: int) -> np.ndarray:
+    """Per-group (B_g,300,6) rows back into input order: (n,300,6)."""
+    out = np.empty((n, MAX_DET, 6), np.float32)
+    for g, o in zip(groups, outs):
+        out[g.index] = o
+    return out
+
+
+class RaggedTicket:
+    """submit_frames' handle: the library tickets of its groups plus everything that has to stay alive until wait()."""
+
+    def __init__(self, n, groups, tickets, bufs, outs):
+        self.n, self.groups, self.tickets, self.bufs, self.outs = n, groups, tickets, bufs, outs
 
 
 class YOLOv9:
@@ -117,6 +208,98 @@ class YOLOv9:
                                              _lib.ptr(out), 1, C.c_void_p(s)))
         return out
 
+    # -- ragged batches: cameras of different resolutions in one batch -----------------------------
+    def network_shape(self, h: int, w: int) -> Tuple[int, int]:
+        """(Hn, Wn) the network sees of an h x w frame at this model's res (needs nothing of the model but `res`)."""
+        return network_shape(h, w, self.res)
+
+    def _pinned(self, nbytes: int):
+        """A pinned uint8 torch tensor of at least nbytes from the model's free list (sizes rounded up to a power of two)."""
+        import torch
+        size = 1 << max(12, int(nbytes - 1).bit_length())
+        pool = self.__dict__.setdefault("_pin_pool", {})
+        free = pool.setdefault(size, [])
+        return free.pop() if free else torch.empty(size, dtype=torch.uint8).pin_memory()
+
+    def _unpin(self, t) -> None:
+        self._pin_pool[t.numel()].append(t)
+
+    def _pack(self, frames, g: RaggedGroup):
+        """Group g's packed pixels: (tensor to keep alive, pinned?) - device frames are concatenated on the device, host frames are
+        packed ONCE into pinned memory."""
+        if g.on_device:
+            import torch
+            return torch.cat([frames[i].contiguous().view(torch.uint8).reshape(-1) for i in g.index]), False
+        buf = self._pinned(g.nbytes)
+        pack_group(frames, g, buf.numpy())
+        return buf, True
+
+    def detect_frames(self, frames: Sequence) -> np.ndarray:
+        """A sequence of (H_i,W_i,3) BGR uint8 / float32 frames of ANY sizes (numpy arrays or torch tensors, host or device) ->
+        (N,300,6) float32 rows in input order.  Frames are grouped by network shape (and element type / residency); each group runs
+        as one ragged batch of that shape's plan (cc_yolo_detect_ragged).  Row i is bit-identical to `self(frames[i])`."""
+        L = _lib.lib()
+        groups = group_frames(frames, self.res)
+        outs = []
+        for g in groups:
+            pixels, pinned = self._pack(frames, g)
+            s = None
+            if g.on_device:
+                import torch
+                s = C.c_void_p(torch.cuda.current_stream(pixels.device).cuda_stream)
+            o = np.empty((len(g.index), MAX_DET, 6), np.float32)
+            try:
+                _lib.check(L.cc_yolo_detect_ragged(self._h, _lib.ptr(pixels), *g.tables(), len(g.index), int(g.f32), int(g.on_device), _lib.ptr(o), 0, s))
+            finally:
+                if pinned:
+                    self._unpin(pixels)
+            outs.append(o)
+        return scatter_rows(groups, outs, len(frames))
+
+    def detect_ragged_device(self, pixels, offsets: np.ndarray, heights: np.ndarray, widths: np.ndarray, out):
+        """Device-resident ragged batch for pipelines: `pixels` a uint8 CUDA tensor holding frame b (heights[b] x widths[b] x 3 uint8) at
+        byte offsets[b]; the tables are int64 / int32 / int32 numpy arrays; out a (B,300,6) float32 CUDA tensor.  All frames must share
+        one network shape.  Ordered on the current torch stream; no host copies, no sync."""
+        import torch
+        i32p = C.POINTER(C.c_int32)
+        s = torch.cuda.current_stream(pixels.device).cuda_stream
+        _lib.check(_lib.lib().cc_yolo_detect_ragged(self._h, _lib.ptr(pixels), offsets.ctypes.data_as(C.POINTER(C.c_int64)), heights.ctypes.data_as(i32p),
+                                                    widths.ctypes.data_as(i32p), len(offsets), 0, 1, _lib.ptr(out), 1, C.c_void_p(s)))
+        return out
+
+    def submit_frames(self, frames: Sequence) -> RaggedTicket:
+        """The ragged counterpart of submit(): queue the frames of detect_frames on the next detector slot(s) - one submission per
+        group - and return at once; wait(ticket, host=True) returns the (N,300,6) rows, bit-identical to detect_frames(frames).
+        Host frames are packed into pinned memory here, so the caller's arrays may be reused immediately; device frames are
+        concatenated on the current torch stream."""
+        import torch
+        L = _lib.lib()
+        groups = group_frames(frames, self.res)
+        tickets, bufs, outs = [], [], []
+        for g in groups:
+            pixels, pinned = self._pack(frames, g)
+            B = len(g.index)
+            ob = self._pinned(B * MAX_DET * 6 * 4)
+            s = C.c_void_p(torch.cuda.current_stream(pixels.device).cuda_stream) if g.on_device else None
+            t = C.c_longlong()
+            _lib.check(L.cc_yolo_submit_ragged(self._h, _lib.ptr(pixels), *g.tables(), B, int(g.f32), int(g.on_device), _lib.ptr(ob), 0, s, C.byref(t)))
+            tickets.append(t.value); bufs.append((pixels, pinned)); outs.append(ob)
+        return RaggedTicket(len(frames), groups, tickets, bufs, outs)
+
+    def _wait_frames(self, ticket: RaggedTicket) -> np.ndarray:
+        import torch
+        L = _lib.lib()
+        for t in ticket.tickets:
+            _lib.check(L.cc_yolo_wait(self._h, t, None))
+        outs = [o[:len(g.index) * MAX_DET * 6 * 4].view(torch.float32).numpy().reshape(len(g.index), MAX_DET, 6) for g, o in zip(ticket.groups, ticket.outs)]
+        rows = scatter_rows(ticket.groups, outs, ticket.n)          # copies: the pinned buffers go back to the free list
+        for (pixels, pinned), ob in zip(ticket.bufs, ticket.outs):
+            if pinned:
+                self._unpin(pixels)
+            self._unpin(ob)
+        ticket.bufs, ticket.outs = [], []
+        return rows
+
     # -- batches in flight (throughput mode: one GPU serving many cameras) --------------------------
     def set_in_flight(self, n: int) -> None:
         """n slots (own stream, arena and graph each): consecutive submit() calls overlap - the last layers of one batch run beside
@@ -149,8 +332,11 @@ class YOLOv9:
                                              _lib.ptr(out), int(out.is_cuda), C.c_void_p(s), C.byref(t)))
         return t.value
 
-    def wait(self, ticket: int, host: bool = False) -> None:
-        """Make the current torch stream (host=True: the calling thread) wait for a submission's result."""
+    def wait(self, ticket, host: bool = False):
+        """Make the current torch stream (host=True: the calling thread) wait for a submission's result.  A submit_frames ticket is
+        always waited for on the host and its (N,300,6) rows are returned."""
+        if isinstance(ticket, RaggedTicket):
+            return self._wait_frames(ticket)
         import torch
         s = None if host else C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
         _lib.check(_lib.lib().cc_yolo_wait(self._h, ticket, s))

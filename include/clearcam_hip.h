@@ -89,6 +89,26 @@ int cc_yolo_set_in_flight(cc_yolo* h, int n);
 int cc_yolo_submit(cc_yolo* h, const void* frames, int B, int H, int W, int frame_f32, int frames_on_device, float* out,
                    int out_on_device, void* stream, long long* ticket);
 int cc_yolo_wait(cc_yolo* h, long long ticket, void* stream);
+/* Ragged batch - one GPU serving cameras of DIFFERENT resolutions (the reference reads every stream's size separately,
+ * clearcam.py:145, :403).  The network only sees the letterboxed shape: at res 640, 1080x1920, 720x1280, 2160x3840 and 360x640 all become
+ * 384x640.  B frames of any source sizes that share ONE network shape run as one batch of that shape's plan; only the letterbox in front
+ * of the network and scale_boxes behind it read a per-frame record.  Packed-buffer convention of cc_crop_preprocess: frame b is
+ * heights[b] x widths[b] x 3 (BGR, all uint8 or all float32 - then offsets are multiples of 4), starting at byte offsets[b] of `pixels`;
+ * the three tables are HOST arrays and are consumed before the call returns.  Row b of `out` is bit-identical to what cc_yolo_detect
+ * returns for frame b alone.  -22 (EINVAL) with a message naming the frame when the frames do not share one network shape or that shape
+ * is not a multiple of 32.  The plan is keyed by (B, network shape, element type, slot): a camera that changes resolution reuses it.
+ * cc_yolo_submit_ragged / cc_yolo_wait are to cc_yolo_detect_ragged what cc_yolo_submit is to cc_yolo_detect (same rows, bit for bit);
+ * `pixels` must stay valid until the submission has completed.  cc_yolo_get_tensor, cc_yolo_last_gpu_ms and cc_yolo_nonfinite work
+ * after a ragged call as after a uniform one; cc_yolo_profile / cc_yolo_profile_graph refuse a ragged plan. */
+int cc_yolo_detect_ragged(cc_yolo* h, const void* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B,
+                          int frame_f32, int pixels_on_device, float* out, int out_on_device, void* stream);
+int cc_yolo_submit_ragged(cc_yolo* h, const void* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B,
+                          int frame_f32, int pixels_on_device, float* out, int out_on_device, void* stream, long long* ticket);
+/* Host-only helper (no GPU needed): the letterbox of an H x W frame at target `res` (yolov9.py:390-403) - resized size nh x nw and the
+ * padding per side; the network shape is (nh + 2 pad_y) x (nw + 2 pad_x).  What the ragged entry points group by. */
+int cc_letterbox_geometry(int H, int W, int res, int* nh, int* nw, int* pad_y, int* pad_x);
+/* Plans (tensor arena + captured graph) the handle has built so far: a call that finds its plan in the cache leaves it unchanged. */
+int cc_yolo_plans_built(cc_yolo* h, int* n);
 /* Parity taps: copy a named intermediate of the LAST detect call to host float32.
  * names: "input" (B,Hn,Wn,3) | "p3","p4","p5" (B,H,W,C) | "raw0","raw1","raw2" (B,H,W,144) |
  * "decoded" (B,A,6).  shape receives up to 4 dims; pass out=NULL to query the shape only.
