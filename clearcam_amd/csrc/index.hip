@@ -5,6 +5,13 @@
 // (N, dim) float32 matrix lives in HBM and one query costs one streaming pass over it (HBM-bound:
 // N*dim*4 bytes), followed by a two-stage radix-select top-k.  Scores are exact f32 dot products
 // (sequential fma per lane + wave tree), so ranking ties break by row id exactly as a stable sort would.
+//
+// cc_index_search_tracks also does the reference's tail (:378-390: best crop per track id, id-less crops kept, stable
+// sort) on the device.  Every row carries a track slot (-1: none).  Between the scan and the selection one pass over
+// scores + slots reduces each track to ordered(score) << 32 | ~row with a 64-bit integer atomic maximum and finds each
+// track's first allowed row with an atomic minimum; the selection then runs over one key per track (placed at that
+// first row, so equal scores order by first appearance like a dict does) plus one per slot-less row.  Integer max / min
+// do not depend on the arrival order: the answer is deterministic, ties included.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -19,6 +26,11 @@ struct cc_index {
   int storage = F32;                              // F32: exact f32 dot products; BF16: rows rounded to bf16 (half the scan bytes, scores within ~1e-3)
   float* emb = nullptr;                           // (capacity, dim) rows in the storage type
   int* grp = nullptr;                             // (capacity) group id of each row (camera/day bucket chosen by the caller); 0 by default
+  int* trk = nullptr;                             // (capacity) track slot of each row: dense per distinct track id, -1 = a crop without one (the default)
+  int n_slots = 0;                                // highest slot + 1
+  unsigned long long* best = nullptr; size_t best_cap = 0;   // (Q, n_slots) per-track maximum of the current track search: ordered(score) << 32 | ~row
+  unsigned* first = nullptr; size_t first_cap = 0;           // (n_slots) first allowed row of each track in the current track search
+  unsigned* key_hi = nullptr; size_t key_hi_cap = 0;         // (Q, n) high words of the selection keys of the current track search
   unsigned char* allowed = nullptr; int allowed_cap = 0;   // per-group filter of the current search (device copy)
   size_t row_bytes() const { return (size_t)dim * (storage == F32 ? 4 : 2); }
   hipStream_t stream = nullptr;
@@ -188,6 +200,9 @@ __device__ __forceinline__ float unordered(unsigned u) {
 
 // Block-wide exact top-K of `count` unique 64-bit keys (key(i) for i in [0,count)): MSB-first radix select of the
 // K-th largest key, then collection of every key >= it into `sel` (unsorted; K entries, zero padded).
+// Padding keys (zero) are never selected and stay out of the histogram: with fewer than K real keys no bucket reaches the
+// wanted count, the prefix stays zero and every real key is collected.  Counting them cost more than everything else in a
+// track search, where 19 of 20 keys are padding: thousands of LDS atomics of one block on the one address hist[0].
 template <class KeyFn>
 __device__ void block_topk(KeyFn key, long count, int K, unsigned long long* sel, unsigned* hist,
                            unsigned long long* s_prefix, int* s_k, unsigned* s_cnt) {
@@ -204,7 +219,7 @@ __device__ void block_topk(KeyFn key, long count, int K, unsigned long long* sel
     const int sh = 8 * (byte + 1);
     for (long i = tid; i < count; i += nt) {
       const unsigned long long k = key(i);
-      if (byte == 7 || (k >> sh) == (prefix >> sh)) atomicAdd(&hist[(unsigned)(k >> (8 * byte)) & 255u], 1u);
+      if (k != 0ull && (byte == 7 || (k >> sh) == (prefix >> sh))) atomicAdd(&hist[(unsigned)(k >> (8 * byte)) & 255u], 1u);
     }
     __syncthreads();
     if (tid < 64) {
@@ -236,17 +251,95 @@ __device__ void block_topk(KeyFn key, long count, int K, unsigned long long* sel
   __syncthreads();
 }
 
+__device__ __forceinline__ bool row_allowed(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, long r) {
+  if (!allowed) return true;
+  const unsigned g = (unsigned)grp[r];
+  return g < (unsigned)n_allowed && allowed[g];
+}
+
+// Track search, pass 1: every allowed row with a track slot t raises best[q][t] to ordered(score) << 32 | ~row (a 64-bit integer
+// maximum: the best score, and among equal scores the lowest row, whatever the arrival order) and lowers first[t] to its row id.
+// Thousands of rows of ONE track (a parked car: one crop every 10 s all day) would send thousands of atomics to one address, so a
+// block first reduces its contiguous kTrkRows rows in an LDS table keyed by slot & (kTrkTab - 1) and tagged with the slot; a row
+// whose entry belongs to another slot goes to global memory directly.  One global atomic per distinct track per block is left.
+// Measured on 1 M rows with one track owning 10 % of them (docs/measurement.md): 75 us, against 1.15 ms with one global atomic
+// per row (the scan of the same search: 0.50 ms).
+constexpr int kTrkRows = 2048, kTrkTab = 1024;
+
+__global__ __launch_bounds__(256) void track_reduce_kernel(const float* __restrict__ scores, long n, int T, const int* __restrict__ trk,
+                                                           const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed,
+                                                           unsigned long long* __restrict__ best, unsigned* __restrict__ first) {
+  __shared__ int tag[kTrkTab]; __shared__ unsigned long long val[kTrkTab]; __shared__ unsigned fst[kTrkTab];
+  const int q = blockIdx.y, tid = threadIdx.x;
+  const bool want_first = q == 0;                                // first[] depends on the filter only: the blocks of query 0 fill it
+  for (int i = tid; i < kTrkTab; i += 256) { tag[i] = -1; val[i] = 0ull; fst[i] = 0xffffffffu; }
+  __syncthreads();
+  const long base = (long)blockIdx.x * kTrkRows, end = min(n, base + kTrkRows);
+  const float* s = scores + (long)q * n;
+  unsigned long long* b = best + (size_t)q * T;
+  for (long r = base + tid; r < end; r += 256) {
+    const int t = trk[r];
+    if (t < 0 || t >= T || !row_allowed(grp, allowed, n_allowed, r)) continue;
+    const unsigned long long key = ((unsigned long long)ordered(s[r]) << 32) | (unsigned)(~(unsigned)r);
+    const int h = t & (kTrkTab - 1);
+    const int owner = atomicCAS(&tag[h], -1, t);
+    if (owner == -1 || owner == t) {
+      atomicMax(&val[h], key);
+      if (want_first) atomicMin(&fst[h], (unsigned)r);
+    } else {
+      atomicMax(&b[t], key);
+      if (want_first) atomicMin(&first[t], (unsigned)r);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < kTrkTab; i += 256) {
+    const int t = tag[i];
+    if (t < 0) continue;
+    atomicMax(&b[t], val[i]);
+    if (want_first) atomicMin(&first[t], fst[i]);
+  }
+}
+
 // stage 1: per (query, chunk of rows) top-K keys -> cand[q][chunk][K]
 // `allowed` (one byte per group) filters rows by their group id: a row of a group that is not allowed contributes the padding key.
+// TRACKS (pass 2 of the track search): a row without a slot carries its own score with ~(n + row) below it; the FIRST allowed row
+// of a track carries the track's best score with its own ~row; every other row is padding.  So one key per track is in the
+// running, tracks of equal score order by first appearance, and slot-less rows follow every track of the same score.
+// The select evaluates a key up to nine times and a block has only 16 waves to hide latency with, so the chain of dependent loads
+// behind a key (slot -> first[slot] -> best[q][slot]) is walked once: the block writes the high words of its chunk's keys to `hi`
+// (its own rows of a (Q, n) scratch, 0 = padding) and the select then reads one coalesced word per key, like the plain search
+// (1 M rows, 50 k tracks: 60 us against 104 us with the chain inside the key function; the plain stage 1: 26 us).
+template <bool TRACKS>
 __global__ __launch_bounds__(1024) void topk_stage1(const float* __restrict__ scores, long n, int K, unsigned long long* __restrict__ cand,
-                                                    const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed) {
+                                                    const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed,
+                                                    const int* __restrict__ trk, const unsigned long long* __restrict__ best,
+                                                    const unsigned* __restrict__ first, int T, unsigned* hi) {
   __shared__ unsigned hist[256]; __shared__ unsigned long long s_prefix; __shared__ int s_k; __shared__ unsigned s_cnt;
   __shared__ unsigned long long sel[kMaxK];
   const int chunk = blockIdx.x, q = blockIdx.y;
   const long base = (long)chunk * kChunk, count = min((long)kChunk, n - base);
   const float* s = scores + (long)q * n + base;
+  unsigned* h = TRACKS ? hi + (long)q * n + base : nullptr;
+  if (TRACKS) {
+#pragma unroll 4
+    for (long i = threadIdx.x; i < count; i += blockDim.x) {
+      unsigned u = 0;
+      if (row_allowed(grp, allowed, n_allowed, base + i)) {
+        const int t = trk[base + i];
+        if (t < 0) u = ordered(s[i]);
+        else if (t < T && first[t] == (unsigned)(base + i)) u = (unsigned)(best[(size_t)q * T + t] >> 32);
+      }
+      h[i] = u;
+    }
+    __syncthreads();                                               // h[] is read back by other threads of this block only
+  }
   auto key = [&](long i) -> unsigned long long {
-    if (allowed) { const unsigned g = (unsigned)grp[base + i]; if (g >= (unsigned)n_allowed || !allowed[g]) return 0ull; }
+    if (TRACKS) {
+      const unsigned u = h[i];
+      if (u == 0u) return 0ull;
+      return ((unsigned long long)u << 32) | (unsigned)(~(unsigned)((trk[base + i] < 0 ? n : 0) + base + i));
+    }
+    if (!row_allowed(grp, allowed, n_allowed, base + i)) return 0ull;
     return ((unsigned long long)ordered(s[i]) << 32) | (unsigned)(~(unsigned)(base + i));
   };
   block_topk(key, count, K, sel, hist, &s_prefix, &s_k, &s_cnt);
@@ -255,7 +348,11 @@ __global__ __launch_bounds__(1024) void topk_stage1(const float* __restrict__ sc
 }
 
 // stage 2: merge candidates of one query, sort descending, emit (row id, score)
-__global__ __launch_bounds__(1024) void topk_stage2(const unsigned long long* __restrict__ cand, long ncand, int K, int* __restrict__ idx, float* __restrict__ score) {
+// TRACKS: the low word is ~position; a position >= n is a slot-less row (position - n), any other the first row of a track,
+// whose answer is the row kept in best[q][slot].
+template <bool TRACKS>
+__global__ __launch_bounds__(1024) void topk_stage2(const unsigned long long* __restrict__ cand, long ncand, int K, int* __restrict__ idx, float* __restrict__ score,
+                                                    long n, const int* __restrict__ trk, const unsigned long long* __restrict__ best, int T) {
   __shared__ unsigned hist[256]; __shared__ unsigned long long s_prefix; __shared__ int s_k; __shared__ unsigned s_cnt;
   __shared__ unsigned long long sel[kMaxK];
   const int q = blockIdx.x, tid = threadIdx.x;
@@ -279,7 +376,11 @@ __global__ __launch_bounds__(1024) void topk_stage2(const unsigned long long* __
   if (tid < K) {
     const unsigned long long k = sel[tid];
     if (k == 0ull) { idx[(size_t)q * K + tid] = -1; score[(size_t)q * K + tid] = -INFINITY; }
-    else { idx[(size_t)q * K + tid] = (int)(~(unsigned)(k & 0xffffffffull)); score[(size_t)q * K + tid] = unordered((unsigned)(k >> 32)); }
+    else {
+      unsigned row = ~(unsigned)(k & 0xffffffffull);
+      if (TRACKS) row = row >= (unsigned)n ? row - (unsigned)n : ~(unsigned)(best[(size_t)q * T + trk[row]] & 0xffffffffull);
+      idx[(size_t)q * K + tid] = (int)row; score[(size_t)q * K + tid] = unordered((unsigned)(k >> 32));
+    }
   }
 }
 
@@ -390,6 +491,7 @@ int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int 
   x->dim = dim; x->capacity = capacity; x->device = device; x->storage = storage;
   CC_HIP(hipMalloc((void**)&x->emb, (size_t)capacity * x->row_bytes() + 256));
   CC_HIP(hipMalloc((void**)&x->grp, (size_t)capacity * 4 + 256));
+  CC_HIP(hipMalloc((void**)&x->trk, (size_t)capacity * 4 + 256));
   x->stream = pool_stream_get(device);
   *h = x.release();
   CC_API_END
@@ -397,24 +499,35 @@ int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int 
 
 int cc_index_create(cc_index** h, int dim, int64_t capacity, int device) { return cc_index_create_ex(h, dim, capacity, device, F32); }
 
-// Append n rows (f32 in; rounded to bf16 for a bf16 index) with their group ids (null: group 0).  The matrix grows
-// geometrically when it is full (new allocation, device-to-device copy, swap), so callers never see a capacity error.
-int cc_index_add_grouped(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups) {
+// Append n rows (f32 in; rounded to bf16 for a bf16 index) with their group ids (null: group 0) and track slots (null: -1, no
+// track).  The matrix grows geometrically when it is full (new allocation, device-to-device copy, swap), so callers never see a
+// capacity error.
+int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks) {
   CC_API_BEGIN
   CC_CHECK(h && (emb || n == 0) && n >= 0, "bad argument");
+  int n_slots = h->n_slots;
+  if (tracks)
+    for (int64_t i = 0; i < n; ++i) {
+      CC_CHECK(tracks[i] >= -1 && tracks[i] < (1 << 24), "track slots must be in [0, 2^24) or -1");
+      n_slots = std::max(n_slots, tracks[i] + 1);
+    }
   CC_HIP(hipSetDevice(h->device));
   CC_HIP(hipStreamSynchronize(h->stream));            // a search on our stream may still be reading the matrix
   if (h->n + n > h->capacity) {
     int64_t cap = h->capacity;
     while (cap < h->n + n) cap *= 2;
     CC_CHECK((size_t)cap * h->row_bytes() < ((size_t)1 << 40), "index would exceed 1 TiB");
-    float* emb2 = nullptr; int* grp2 = nullptr;
+    float* emb2 = nullptr; int* grp2 = nullptr; int* trk2 = nullptr;
     CC_HIP(hipMalloc((void**)&emb2, (size_t)cap * h->row_bytes() + 256));
-    if (hipMalloc((void**)&grp2, (size_t)cap * 4 + 256) != hipSuccess) { hipFree(emb2); throw cc::Error(-12, "out of device memory growing the index"); }
+    if (hipMalloc((void**)&grp2, (size_t)cap * 4 + 256) != hipSuccess || hipMalloc((void**)&trk2, (size_t)cap * 4 + 256) != hipSuccess) {
+      hipFree(emb2); if (grp2) hipFree(grp2);
+      throw cc::Error(-12, "out of device memory growing the index");
+    }
     CC_HIP(hipMemcpy(emb2, h->emb, (size_t)h->n * h->row_bytes(), hipMemcpyDeviceToDevice));
     CC_HIP(hipMemcpy(grp2, h->grp, (size_t)h->n * 4, hipMemcpyDeviceToDevice));
-    hipFree(h->emb); hipFree(h->grp);
-    h->emb = emb2; h->grp = grp2; h->capacity = cap;
+    CC_HIP(hipMemcpy(trk2, h->trk, (size_t)h->n * 4, hipMemcpyDeviceToDevice));
+    hipFree(h->emb); hipFree(h->grp); hipFree(h->trk);
+    h->emb = emb2; h->grp = grp2; h->trk = trk2; h->capacity = cap;
   }
   if (n) {
     char* dst = reinterpret_cast<char*>(h->emb) + (size_t)h->n * h->row_bytes();
@@ -434,9 +547,16 @@ int cc_index_add_grouped(cc_index* h, const float* emb, int64_t n, int on_device
     }
     if (groups) CC_HIP(hipMemcpy(h->grp + h->n, groups, (size_t)n * 4, hipMemcpyHostToDevice));
     else CC_HIP(hipMemset(h->grp + h->n, 0, (size_t)n * 4));
+    if (tracks) CC_HIP(hipMemcpy(h->trk + h->n, tracks, (size_t)n * 4, hipMemcpyHostToDevice));
+    else CC_HIP(hipMemset(h->trk + h->n, 0xff, (size_t)n * 4));
   }
   h->n += n;
+  h->n_slots = n_slots;
   CC_API_END
+}
+
+int cc_index_add_grouped(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups) {
+  return cc_index_add_tracked(h, emb, n, on_device, groups, nullptr);
 }
 
 int cc_index_add(cc_index* h, const float* emb, int64_t n, int on_device) { return cc_index_add_grouped(h, emb, n, on_device, nullptr); }
@@ -470,13 +590,19 @@ int cc_index_scores(cc_index* h, const float* q, int Q, float* scores, int on_de
   CC_API_END
 }
 
+}  // extern "C"
+
+namespace {
+
 // Top-k among the rows whose group is allowed (allowed: n_groups bytes on the HOST, one per group id, non-zero = keep;
-// null = every row).  Rows of a group id >= n_groups are filtered out.  Everything else as cc_index_search.
-int cc_index_search_groups(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
-                           int on_device, void* stream) {
+// null = every row).  Rows of a group id >= n_groups are filtered out.  tracks: the answers are tracks (their best row) and
+// slot-less rows instead of rows - one more pass over scores + trk between the scan and the selection.
+int search(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
+           int on_device, void* stream, bool tracks) {
   CC_API_BEGIN
   CC_CHECK(h && q && idx && score && Q > 0, "bad argument");
   CC_CHECK(k > 0 && k <= kMaxK, "k must be in [1, 1024]");
+  CC_CHECK(!tracks || h->n < (1LL << 31), "a track search needs fewer than 2^31 rows");   // keys hold ~row and ~(n + row) in 32 bits
   CC_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const size_t ob = (size_t)Q * k;
@@ -511,11 +637,26 @@ int cc_index_search_groups(cc_index* h, const float* q, int Q, int k, const uint
   if (h->n > 0) {
     upload_queries(h, q, Q, on_device, s);
     compute_scores(h, Q, s);
-    hipLaunchKernelGGL(topk_stage1, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap);
+    if (tracks) {
+      const int T = std::max(h->n_slots, 1);
+      ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
+      ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
+      CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
+      ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * h->n * 4);
+      CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
+      hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((h->n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, (long)h->n, T, h->trk, h->grp,
+                         allowed_dev, h->allowed_cap, h->best, h->first);
+      hipLaunchKernelGGL(topk_stage1<true>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
+                         h->trk, h->best, h->first, T, h->key_hi);
+    } else {
+      hipLaunchKernelGGL(topk_stage1<false>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
+                         nullptr, nullptr, nullptr, 0, nullptr);
+    }
   } else {
     CC_HIP(hipMemsetAsync(h->cand, 0, (size_t)Q * nchunk * k * 8, s));
   }
-  hipLaunchKernelGGL(topk_stage2, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out);
+  if (tracks) hipLaunchKernelGGL(topk_stage2<true>, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out, (long)h->n, h->trk, h->best, std::max(h->n_slots, 1));
+  else hipLaunchKernelGGL(topk_stage2<false>, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out, (long)h->n, nullptr, nullptr, 0);
   CC_HIP(hipGetLastError());
   if (zero_copy) {
     CC_HIP(hipStreamSynchronize(s));
@@ -530,6 +671,20 @@ int cc_index_search_groups(cc_index* h, const float* q, int Q, int k, const uint
   CC_API_END
 }
 
+}  // namespace
+
+extern "C" {
+
+int cc_index_search_groups(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
+                           int on_device, void* stream) {
+  return search(h, q, Q, k, allowed, n_groups, idx, score, on_device, stream, false);
+}
+
+int cc_index_search_tracks(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
+                           int on_device, void* stream) {
+  return search(h, q, Q, k, allowed, n_groups, idx, score, on_device, stream, true);
+}
+
 int cc_index_search(cc_index* h, const float* q, int Q, int k, int32_t* idx, float* score, int on_device, void* stream) {
   return cc_index_search_groups(h, q, Q, k, nullptr, 0, idx, score, on_device, stream);
 }
@@ -538,7 +693,7 @@ void cc_index_destroy(cc_index* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->allowed, (void*)h->q16, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev}) if (p) hipFree(p);
+  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)
   delete h;

@@ -158,9 +158,10 @@ class EmbeddingIndex:
         _lib.check(_lib.lib().cc_index_size(self._h, C.byref(n)))
         return n.value
 
-    def add(self, emb, groups=None) -> None:
+    def add(self, emb, groups=None, tracks=None) -> None:
         """Append rows: (n,dim) / (n,1,dim) / (dim,) float32, host array or CUDA torch tensor.  Rows of any other width are
-        rejected (a 512-d face row must never land in the 768-d crop matrix).  groups: one int per row (search filter unit)."""
+        rejected (a 512-d face row must never land in the 768-d crop matrix).  groups: one int per row (search filter unit).
+        tracks: one slot per row, a dense number per distinct track id or -1 for a crop without one (`search_tracks`)."""
         on_dev = bool(getattr(emb, "is_cuda", False))
         if on_dev:
             a = emb.contiguous().float()
@@ -177,7 +178,13 @@ class EmbeddingIndex:
             g = np.ascontiguousarray(np.asarray(groups, np.int32).reshape(-1))
             if g.shape[0] != a.shape[0] or (g.size and (g.min() < 0 or g.max() >= 1 << 24)):
                 raise ValueError("groups: one id in [0, 2^24) per row")
-        _lib.check(_lib.lib().cc_index_add_grouped(self._h, _lib.ptr(a), a.shape[0], int(on_dev), _lib.ptr(g) if g is not None else None))
+        t = None
+        if tracks is not None:
+            t = np.ascontiguousarray(np.asarray(tracks, np.int32).reshape(-1))
+            if t.shape[0] != a.shape[0] or (t.size and (t.min() < -1 or t.max() >= 1 << 24)):
+                raise ValueError("tracks: one slot in [0, 2^24) or -1 per row")
+        _lib.check(_lib.lib().cc_index_add_tracked(self._h, _lib.ptr(a), a.shape[0], int(on_dev), _lib.ptr(g) if g is not None else None,
+                                                   _lib.ptr(t) if t is not None else None))
 
     def scores(self, q) -> np.ndarray:
         qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
@@ -197,9 +204,29 @@ class EmbeddingIndex:
                                                      0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 0, None))
         return idx, sc
 
+    def search_tracks(self, q, k: int, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` with tracks as the answers (models/objects.py:378-390 on the device): among the allowed rows every track
+        slot counts once, with its best row (equal scores: the lower row), and rows of slot -1 count as themselves.  Descending
+        by score; equal scores: tracks by their first allowed row, then the slot-less rows by row id.  Fewer than k answers
+        leave -1/-inf at the end.  One call, exact for any data: no candidate list to widen."""
+        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
+        idx = np.empty((qa.shape[0], k), np.int32)
+        sc = np.empty((qa.shape[0], k), np.float32)
+        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_search_tracks(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
+                                                     0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 0, None))
+        return idx, sc
+
+    def search_tracks_device(self, q, k: int, allowed=None):
+        """`search_tracks` with the result left on the GPU, like `search_device` (allowed stays a host array)."""
+        return self._search_device("cc_index_search_tracks", q, k, allowed)
+
     def search_device(self, q, k: int):
-        """The same with the result left on the GPU: (idx int32, score f32) CUDA torch tensors on the current torch stream,
+        """`search` with the result left on the GPU: (idx int32, score f32) CUDA torch tensors on the current torch stream,
         for callers that keep going on the device (clearcam_amd.dist.ShardedIndex: all-gather + merge)."""
+        return self._search_device("cc_index_search_groups", q, k, None)
+
+    def _search_device(self, call: str, q, k: int, allowed):
         import torch
         dev = torch.device("cuda", self.device)
         if not bool(getattr(q, "is_cuda", False)):
@@ -210,8 +237,20 @@ class EmbeddingIndex:
         qa = q.contiguous().float().reshape(-1, self.dim)
         idx = torch.empty((qa.shape[0], k), dtype=torch.int32, device=dev)
         sc = torch.empty((qa.shape[0], k), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib().cc_index_search_groups(self._h, _lib.ptr(qa), qa.shape[0], k, None, 0, _lib.ptr(idx), _lib.ptr(sc), 1, C.c_void_p(stream)))
+        cur = run = torch.cuda.current_stream(dev)
+        if cur.cuda_stream == 0:
+            # torch's default stream has the handle 0, which the library reads as "no stream given" (it then runs on the index's own
+            # stream, which nothing orders against torch): run on a side stream fenced by the current one on both sides instead
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = torch.cuda.Stream(dev)
+            run = self._side_stream
+            run.wait_stream(cur)
+        # nothing waits for the stream here: the filter bytes stay referenced until the next call replaces them
+        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(getattr(_lib.lib(), call)(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
+                                              0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 1, C.c_void_p(run.cuda_stream)))
+        if run is not cur:
+            cur.wait_stream(run)
         return idx, sc
 
     def close(self):
@@ -243,6 +282,8 @@ class _RowTable:
         self.bad: List[bool] = [False]         # group has a *.jpg name event_img_info cannot parse (the reference raises on it)
         self.group: List[int] = []
         self.oid: List[Optional[int]] = []     # track id per row exactly as event_img_info returns it (any sign), None = no '_' in the name
+        self.slot_of: Dict[int, int] = {}      # track id -> dense slot, in order of first appearance (id 0 and negative ids are ids)
+        self.slot: List[int] = []              # slot per row, -1 where oid is None: what the device reduces by (EmbeddingIndex.search_tracks)
 
     def describe(self, path: str) -> Tuple[int, int]:
         norm = path.replace("\\", "/")
@@ -271,8 +312,12 @@ class _RowTable:
             g, oid = self.describe(p)
             groups[i] = g
             self.group.append(g); self.oid.append(oid)
+            self.slot.append(-1 if oid is None else self.slot_of.setdefault(oid, len(self.slot_of)))
         self.paths.extend(paths)
         return groups
+
+    def slots(self, start: int = 0) -> np.ndarray:
+        return np.asarray(self.slot[start:], np.int32)
 
     def allowed(self, cam_name, timestamp) -> np.ndarray:
         al = np.zeros(len(self.dirs), np.uint8)
@@ -478,6 +523,15 @@ class ObjectFinder:
     def _new_index(self, dim: int, rows: int) -> EmbeddingIndex:
         return EmbeddingIndex(dim, max(2 * rows, 1024), device=self.model.device if self.model else 0, storage=self.index_storage)
 
+    @staticmethod
+    def _add_rows(index: EmbeddingIndex, table: "_RowTable", rows, paths) -> None:
+        """Rows into the device matrix with their directory group and, where the index reduces per track, their track slot."""
+        groups = table.extend(paths)
+        if hasattr(index, "search_tracks"):
+            index.add(rows, groups, table.slots(len(table.paths) - len(paths)))
+        else:
+            index.add(rows, groups)
+
     def _replace(self, key: str, index: EmbeddingIndex, table: "_RowTable"):
         old = self._dev.pop(key, None)
         if old is not None:
@@ -494,7 +548,7 @@ class ObjectFinder:
                                storage=self.index_storage)
         table = _RowTable()
         if len(paths):
-            index.add(rows, table.extend(list(paths)))
+            self._add_rows(index, table, rows, list(paths))
         self._replace("store", index, table)
         self._attached = True
         return len(paths)
@@ -515,7 +569,7 @@ class ObjectFinder:
         self._version["image"] += 1
         if getattr(self, "_attached", False):
             index, table = self._dev["store"]
-            index.add(e, table.extend([path]))
+            self._add_rows(index, table, e, [path])
 
     def _device_index(self, embeddings: Dict[str, np.ndarray], key: str = "image") -> Tuple[EmbeddingIndex, "_RowTable"]:
         """(Re)build the HBM-resident matrix of one of the reference's dicts when it changed (the reference reloads before
@@ -526,7 +580,7 @@ class ObjectFinder:
             dim = int(np.asarray(embeddings[paths[0]]).size) if paths else (512 if key == "face" else 768)
             index, table = self._new_index(dim, len(paths)), _RowTable()
             if paths:
-                index.add(np.stack([np.asarray(embeddings[p], np.float32).reshape(-1) for p in paths]), table.extend(paths))
+                self._add_rows(index, table, np.stack([np.asarray(embeddings[p], np.float32).reshape(-1) for p in paths]), paths)
             self._replace(key, index, table)
             self._dev_sig[key] = sig
         return self._dev[key]
@@ -569,6 +623,11 @@ class ObjectFinder:
             return []
         exact_loop = any(table.bad[g] for g in live)
         grouped = any(table.truthy[g] for g in live)
+        if grouped and not exact_loop and top_k <= 1024 and hasattr(index, "search_tracks"):
+            # the device reduces per track id and selects (one call, exact whatever the data: thousands of crops of one track, ties)
+            idx, sc = index.search_tracks(q, int(top_k), allowed)
+            return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
+        # No track ids among the allowed rows, top_k > 1024 or an index without search_tracks:
         # GPU: filtered top-K' (one HBM pass + radix select); host: the reference's best-per-track-id tail on K' rows.
         # The answer is exact once the top_k-th result scores strictly above the weakest candidate (no unseen row can
         # enter or change it) or every allowed row has been seen; otherwise K' grows, and past 1024 the full score vector

@@ -252,7 +252,8 @@ void cc_ocsort_destroy(cc_ocsort* h);
 /* ---------------------------------------------------------------------------------------------
  * Embedding index — stands behind the scoring loop of `ObjectFinder.search`
  * (models/objects.py:365-376: sim = img_emb @ text_emb.T per item) over a device-resident matrix.
- * Path filtering / best-per-track-id / sorting of the reference stay in the Python shim.
+ * Path filtering stays in the Python shim (one byte per directory group); best-per-track-id and the sort run on the
+ * device in cc_index_search_tracks.
  * ------------------------------------------------------------------------------------------- */
 typedef struct cc_index cc_index;
 int cc_index_create(cc_index** h, int dim, int64_t capacity, int device);        /* f32 rows */
@@ -272,6 +273,16 @@ int cc_index_search(cc_index* h, const float* q, int Q, int k, int32_t* idx, flo
 /* top-k restricted to rows whose group is allowed: `allowed` = n_groups bytes on the HOST (non-zero keeps the group),
  * NULL = no filter; fewer than k allowed rows -> -1/-inf padding */
 int cc_index_search_groups(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
+                           int on_device, void* stream);
+/* cc_index_add_grouped plus one track slot per row on the HOST: a dense number in [0, 2^24) the caller assigns to each
+ * distinct track id, or -1 for a crop without one.  NULL = all -1, which is also what the other add calls store. */
+int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks);
+/* The tail of `ObjectFinder.search` (models/objects.py:378-390) on the device: among the allowed rows every track slot
+ * is reduced to its best row (equal scores: the lower row), rows of slot -1 stand for themselves, and the top k of
+ * those answers come back by descending score.  Equal scores: tracks in the order of their first allowed row, then the
+ * slot-less rows by row id (a dict in insertion order + a stable sort).  idx is the row of the track's best crop.
+ * Arguments, k in [1, 1024] and the -1/-inf padding as in cc_index_search_groups; the index must hold < 2^31 rows. */
+int cc_index_search_tracks(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
                            int on_device, void* stream);
 void cc_index_destroy(cc_index* h);
 
