@@ -229,12 +229,6 @@ BPlan* get_plan(cc_blaze* h, int H, int W, int f32) {
 
 }  // namespace
 
-#define CC_API_BEGIN try {
-#define CC_API_END                                                         \
-  return 0; }                                                              \
-  catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
-  catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
-
 extern "C" {
 
 int cc_blaze_create(cc_blaze** h, int dtype, int device) {

@@ -223,12 +223,6 @@ CPlan* text_plan(cc_clip* h, int B) {
 
 }  // namespace
 
-#define CC_API_BEGIN try {
-#define CC_API_END                                                         \
-  return 0; }                                                              \
-  catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
-  catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
-
 extern "C" {
 
 int cc_clip_create(cc_clip** h, const cc_clip_config* cfg, int dtype, int device) {
@@ -342,10 +336,7 @@ int cc_clip_set_in_flight(cc_clip* h, int n) {
   CC_HIP(hipStreamSynchronize(h->stream));
   for (hipStream_t t : h->slot_stream) CC_HIP(hipStreamSynchronize(t));
   if (n == (int)h->slot_stream.size() + 1) return 0;   // same depth: slots and tickets stay valid
-  while ((int)h->slot_stream.size() > n - 1) { pool_stream_put(h->device, h->slot_stream.back()); h->slot_stream.pop_back(); }
-  grow_slot_streams(h->device, h->stream, h->slot_stream, n - 1);
-  while ((int)h->slot_done.size() > n) { hipEventDestroy(h->slot_done.back()); h->slot_done.pop_back(); }
-  while ((int)h->slot_done.size() < n) { hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->slot_done.push_back(e); }
+  resize_slots(h->device, h->stream, h->slot_stream, h->slot_done, n);
   h->submitted = 0;
   CC_API_END
 }

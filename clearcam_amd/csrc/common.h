@@ -31,7 +31,7 @@ inline int storage_dtype(int dt) { return dt == F16S || dt == F16H || dt == F16C
 inline size_t dtype_size(int dt) { return dt == F32 ? 4 : 2; }
 
 // ---- error plumbing -------------------------------------------------------------------------
-void set_error(const std::string& msg);          // api.cpp (thread-local)
+void set_error(const std::string& msg);          // runtime.hip (thread-local, read by cc_last_error)
 struct Error : std::runtime_error { int code; Error(int c, const std::string& m) : std::runtime_error(m), code(c) {} };
 
 #define CC_HIP(expr)                                                                              \
@@ -45,6 +45,13 @@ struct Error : std::runtime_error { int code; Error(int c, const std::string& m)
   do {                                                                                            \
     if (!(cond)) throw cc::Error(-22, std::string(msg) + " [" #cond "] @" + __FILE__ + ":" + std::to_string(__LINE__)); \
   } while (0)
+
+// Body of every extern "C" entry point that returns a status: 0, or the error's code with its text behind cc_last_error
+#define CC_API_BEGIN try {
+#define CC_API_END                                                         \
+  return 0; }                                                              \
+  catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
+  catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
 
 // ---- 16-bit storage types -------------------------------------------------------------------
 struct bf16_t { uint16_t v; };

@@ -49,7 +49,7 @@ struct ConvChoice {
 ConvChoice choose_conv(int dt, const ConvP& p);
 
 // conv_tile64.hip takes a 3x3 64 -> 64 layer of B frames of H x W (eligible shape assumed): CLEARCAM_TILE64 on, one full round of its
-// 256-pixel tiles and the better of 16 x 16 / 8 x 32 tiles within 1.25x of the map.  yolo.hip's RepNCSP fusion asks the same question.
+// 256-pixel tiles and the better of 16 x 16 / 8 x 32 tiles within 1.25x of the map.  yolo.hip's RepNCSP fusion (Builder::fuse_csp) asks the same question.
 bool conv_tile64_takes(int B, int H, int W);
 
 // CLEARCAM_* selection switches, read from the environment once per process (thread-safe static initialisation)

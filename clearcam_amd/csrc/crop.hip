@@ -147,12 +147,6 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const WarpP p) {
 }  // namespace
 }  // namespace cc
 
-#define CC_API_BEGIN try {
-#define CC_API_END                                                         \
-  return 0; }                                                              \
-  catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
-  catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
-
 extern "C" int cc_crop_preprocess(const uint8_t* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths,
                                   int B, int pixels_on_device, int out_size, float* out_dev, int device, void* stream) {
   using namespace cc;

@@ -200,12 +200,6 @@ FPlan* get_plan(cc_face* h, int B, int img_f32) {
 
 }  // namespace
 
-#define CC_API_BEGIN try {
-#define CC_API_END                                                         \
-  return 0; }                                                              \
-  catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
-  catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
-
 extern "C" {
 
 int cc_face_create(cc_face** h, int dtype, int device) {

@@ -471,12 +471,6 @@ void compute_scores(cc_index* h, int Q, hipStream_t s) {
 
 }  // namespace
 
-#define CC_API_BEGIN try {
-#define CC_API_END                                                         \
-  return 0; }                                                              \
-  catch (const cc::Error& e) { cc::set_error(e.what()); return e.code; }   \
-  catch (const std::exception& e) { cc::set_error(e.what()); return -1; }
-
 extern "C" {
 
 int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int storage) {

@@ -130,7 +130,7 @@ void launch_stem_fused(int dt, const StemP& p, hipStream_t stream);
 // of the batch (each block still tests whether ITS tile's source rectangle fits the stage and reads the frame directly where it does not).
 bool stem_needs_big(int H, int W, int nh, int nw, int frame_f32);
 void launch_stem_fused_ragged(int dt, const StemP& p, const FrameDesc* desc, size_t packed_bytes, bool big, hipStream_t stream);
-// tinygrad `interpolate(mode='linear', align_corners=False)` index tables for one axis, evaluated in float32 (yolo.hip)
+// tinygrad `interpolate(mode='linear', align_corners=False)` index tables for one axis, evaluated in float32 (yolo_run.hip)
 void axis_tables(int n_in, int n_out, std::vector<int>& lo, std::vector<int>& hi, std::vector<float>& fr);
 
 struct DecodeP {              // DDetect decode + class max: detection/yolov9.py:209-220,440-448
@@ -161,14 +161,19 @@ struct HeadTailP {
 };
 bool head_tail_supported(int dt, int ch, int split = 0);
 void launch_head_tail(int dt, const HeadTailP& p, hipStream_t stream);
+// ---- shared runtime (runtime.hip) ---------------------------------------------------------------
 // Streams of handles come from a process-wide pool per device and go back to it when a handle dies - they are NEVER destroyed.
 // Destroying streams makes the runtime re-deal its few hardware queues, and a handle created afterwards has been seen replaying
 // its captured graph 3x slower for its whole life ("Uploads"); parked streams keep the queue assignment stable.
 hipStream_t pool_stream_get(int device);                 // a non-blocking stream of `device` (the device must be current)
 void pool_stream_put(int device, hipStream_t s);         // idle it and park it for the next handle
-// batches in flight (yolo.hip): streams for the extra slots of a handle, probed until kernels on them overlap with `base` and each other
+// batches in flight: streams for the extra slots of a handle, probed until kernels on them overlap with `base` and each other
 bool streams_overlap(hipStream_t a, hipStream_t b);
 void grow_slot_streams(int device, hipStream_t base, std::vector<hipStream_t>& slots, int n_extra);
+// a handle's slots resized to n batches in flight (slot_stream: n - 1 probed streams, slot_done: n events); the caller idles the streams first
+void resize_slots(int device, hipStream_t base, std::vector<hipStream_t>& slot_stream, std::vector<hipEvent_t>& slot_done, int n);
+// what is enqueued on `waiter` from now on runs after what `signaller` holds now
+void order_after(hipStream_t waiter, hipStream_t signaller);
 
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;
