@@ -12,6 +12,9 @@
 // track's first allowed row with an atomic minimum; the selection then runs over one key per track (placed at that
 // first row, so equal scores order by first appearance like a dict does) plus one per slot-less row.  Integer max / min
 // do not depend on the arrival order: the answer is deterministic, ties included.
+//
+// cc_index_remove_rows / cc_index_remove_groups take rows out by stable compaction in place ("Removing rows"):
+// keep flags -> per-granule counts -> one-block scan -> one mover launch per slab, ordered by the stream alone.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -40,6 +43,12 @@ struct cc_index {
   unsigned long long* cand = nullptr; size_t cand_cap = 0;
   int* idx_dev = nullptr; float* sc_dev = nullptr; size_t out_cap = 0;
   char* pin = nullptr; size_t pin_cap = 0;      // pinned, device-visible host staging: queries in, small results out
+  // removal (cc_index_remove_*): scratch of the current call, kept for the next one
+  unsigned char* keep = nullptr; size_t keep_cap = 0;          // (n) in: the caller's drop bytes (row removal); out: 1 = the row survives
+  unsigned char* drop_grp = nullptr; size_t drop_grp_cap = 0;  // per-group drop table (group removal)
+  unsigned* gcnt = nullptr; size_t gcnt_cap = 0;               // survivors per granule of kGran rows
+  unsigned long long* goff = nullptr; size_t goff_cap = 0;     // survivors before each granule, and the total behind the last one
+  char* bounce = nullptr; size_t bounce_cap = 0;               // one slab of survivors: rows, then their groups, then their slots
 };
 
 namespace {
@@ -384,6 +393,116 @@ __global__ __launch_bounds__(1024) void topk_stage2(const unsigned long long* __
   }
 }
 
+// ---- removal: stable compaction in place -------------------------------------------------------------------------------------
+// Row r moves to pos(r) = the survivors before it, and pos(r) <= r.  Positions come from three passes: keep flags and survivor
+// counts per granule of kGran rows, an exclusive scan of the counts by ONE block (64-bit), and the place inside the granule from a
+// ballot in the mover.  No block waits for another one anywhere: what orders the passes and the slabs is the stream.
+constexpr int kGran = 64;                 // rows per granule = rows per mover block (four waves x 16 rows)
+constexpr int kSlabRows = 32768;          // rows of a bounced slab (cc_dev_set("index_slab_rows") overrides; docs/measurement.md has the sweep)
+
+// keep[r] = 1 where row r survives, gcnt[g] = survivors of granule g.  drop set: group removal (a row goes when drop[its group] is
+// non-zero; groups >= n_groups stay); otherwise keep[] holds the caller's drop bytes on entry.  One wave per granule.
+__global__ __launch_bounds__(256) void keep_count_kernel(unsigned char* __restrict__ keep, const int* __restrict__ grp, const unsigned char* __restrict__ drop,
+                                                         int n_groups, long n, unsigned* __restrict__ gcnt) {
+  const int lane = threadIdx.x & 63;
+  const long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6), r = g * kGran + lane;
+  bool k = false;
+  if (r < n) {
+    if (drop) { const unsigned gi = (unsigned)grp[r]; k = !(gi < (unsigned)n_groups && drop[gi]); }
+    else k = keep[r] == 0;
+    keep[r] = k ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(k);
+  if (lane == 0 && g * kGran < n) gcnt[g] = (unsigned)__popcll(m);
+}
+
+// goff[g] = sum of gcnt[0..g), goff[nb] = the number of survivors.  One block of 1024 threads walks the counts 1024 at a time.
+__global__ __launch_bounds__(1024) void granule_offsets_kernel(const unsigned* __restrict__ gcnt, long nb, unsigned long long* __restrict__ goff) {
+  __shared__ unsigned long long wsum[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  unsigned long long carry = 0;
+  for (long base = 0; base < nb; base += 1024) {
+    const long i = base + tid;
+    const unsigned long long c = i < nb ? gcnt[i] : 0ull;
+    unsigned long long inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    unsigned long long before = 0, total = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { const unsigned long long v = wsum[j]; if (j < w) before += v; total += v; }
+    if (i < nb) goff[i] = carry + before + inc - c;
+    carry += total;
+    __syncthreads();
+  }
+  if (tid == 0) goff[nb] = carry;
+}
+
+// The mover: block b takes granule g0 + b.  Every wave ballots the granule's 64 keep flags and moves the survivors among its own
+// 16 rows to goff[granule] - dst_sub + (survivors before the row in the granule): whole rows, `chunks` 16-byte pieces each, one
+// piece per lane and load, four rows in flight per wave (a pure HBM kernel, like scan_kernel: 16 waves per CU with four
+// independent 16-byte loads each).  grp / trk ride along.  dst is the matrix itself (direct: the caller guarantees that the
+// destinations of this launch lie below its first source row) or the bounce buffer (dst_sub = survivors before the slab); either
+// way no byte is both read and written by one launch, which is what __restrict__ says.
+__global__ __launch_bounds__(256) void compact_kernel(const uint4* __restrict__ src, const int* __restrict__ sgrp, const int* __restrict__ strk,
+                                                      uint4* __restrict__ dst, int* __restrict__ dgrp, int* __restrict__ dtrk,
+                                                      const unsigned char* __restrict__ keep, const unsigned long long* __restrict__ goff,
+                                                      long g0, long n, long dst_sub, int chunks) {
+  const long g = g0 + blockIdx.x, r0 = g * kGran;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(r0 + lane < n && keep[r0 + lane] != 0);
+  const long dbase = (long)goff[g] - dst_sub;
+  if (lane < 16) {
+    const int row = 16 * w + lane;
+    if ((m >> row) & 1ull) {
+      const long d = dbase + __popcll(m & ((1ull << row) - 1ull));
+      dgrp[d] = sgrp[r0 + row]; dtrk[d] = strk[r0 + row];
+    }
+  }
+  unsigned mine = (unsigned)((m >> (16 * w)) & 0xffffull);                   // the survivors among this wave's rows (wave-uniform)
+  long d = dbase + __popcll(m & ((1ull << (16 * w)) - 1ull));
+  const long s0 = (r0 + 16 * w) * chunks;
+  while (mine) {
+    long so[4]; int k = 0;                                                    // piece offsets of the next (up to) four survivors
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      so[u] = s0;
+      if (mine) { so[u] = s0 + (long)(__ffs((int)mine) - 1) * chunks; mine &= mine - 1; ++k; }
+    }
+    const long o = d * chunks;
+    if (k == 4) {
+      for (int c = lane; c < chunks; c += 64) {
+        uint4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = src[so[u] + c];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dst[o + (long)u * chunks + c] = v[u];
+      }
+    } else {
+      for (int c = lane; c < chunks; c += 64)
+        for (int u = 0; u < k; ++u) dst[o + (long)u * chunks + c] = src[so[u] + c];
+    }
+    d += k;
+  }
+}
+
+// A bounced slab back into the matrix: rows (n16 16-byte pieces) and their groups / slots, four loads in flight per thread.
+__global__ __launch_bounds__(256) void copy_down_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16,
+                                                        const int* __restrict__ sgrp, int* __restrict__ dgrp, const int* __restrict__ strk, int* __restrict__ dtrk, long rows) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nt = (size_t)gridDim.x * 256;
+  size_t i = tid;
+  for (; i + 3 * nt < n16; i += 4 * nt) {
+    uint4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = src[i + u * nt];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) dst[i + u * nt] = v[u];
+  }
+  for (; i < n16; i += nt) dst[i] = src[i];
+  for (size_t i = tid; i < (size_t)rows; i += nt) { dgrp[i] = sgrp[i]; dtrk[i] = strk[i]; }
+}
+
 void ensure(void** p, size_t* cap, size_t bytes) {
   if (*cap >= bytes) return;
   if (*p) hipFree(*p);
@@ -586,7 +705,93 @@ int cc_index_scores(cc_index* h, const float* q, int Q, float* scores, int on_de
 
 }  // extern "C"
 
+namespace cc { std::atomic<int> g_index_slab_rows{-1}; }
+
 namespace {
+
+// Removal behind cc_index_remove_rows (by_rows; drop: one byte per row) and cc_index_remove_groups (drop: one byte per group id).
+// The launches, all on the index's stream:
+//   keep flags + granule counts, the scan, and the granule offsets back to the host (8 bytes per 64 rows), which cuts the slabs;
+//   nothing for the granules before the first removed row (they stay where they are);
+//   from there on, with a = the first row not yet moved and gap = a - pos(a) the rows removed before it:
+//     gap >= T / 4: a DIRECT slab [a, b), b the last granule boundary with pos(b) <= a.  It writes [pos(a), pos(b)), all below a,
+//       so neither its own sources nor those of any later slab; everything before a has been moved by earlier launches.
+//     otherwise a BOUNCED slab of T rows: survivors gathered into the handle's bounce buffer, then copied down to
+//       [pos(a), pos(a) + survivors), which ends at or below a + T, the start of the next slab.
+// Direct slabs grow with the gap, so once the removed rows before a slab outnumber T / 4 no row is moved twice.
+int remove_impl(cc_index* h, bool by_rows, const uint8_t* drop, int64_t n_rows, int n_groups, int64_t* removed) {
+  CC_API_BEGIN
+  CC_CHECK(h, "null index");
+  if (removed) *removed = 0;
+  if (by_rows) CC_CHECK(n_rows == h->n, "the drop mask must have one byte per row of the index");
+  else CC_CHECK(n_groups > 0 && n_groups <= (1 << 24), "bad group count");
+  CC_HIP(hipSetDevice(h->device));
+  CC_HIP(hipStreamSynchronize(h->stream));            // a search on our stream may still be reading the matrix
+  const int64_t n = h->n;
+  if (n == 0) return 0;
+  CC_CHECK(drop, "null drop table");
+  if (std::all_of(drop, drop + (by_rows ? (size_t)n : (size_t)n_groups), [](uint8_t b) { return b == 0; })) return 0;
+  hipStream_t s = h->stream;
+  const int64_t nb = (n + kGran - 1) / kGran;
+  ensure((void**)&h->keep, &h->keep_cap, (size_t)n);
+  ensure((void**)&h->gcnt, &h->gcnt_cap, (size_t)nb * 4);
+  ensure((void**)&h->goff, &h->goff_cap, (size_t)(nb + 1) * 8);
+  const unsigned char* drop_dev = nullptr;
+  if (by_rows) CC_HIP(hipMemcpyAsync(h->keep, drop, (size_t)n, hipMemcpyHostToDevice, s));
+  else {
+    ensure((void**)&h->drop_grp, &h->drop_grp_cap, (size_t)n_groups);
+    CC_HIP(hipMemcpyAsync(h->drop_grp, drop, (size_t)n_groups, hipMemcpyHostToDevice, s));
+    drop_dev = h->drop_grp;
+  }
+  hipLaunchKernelGGL(keep_count_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, h->keep, h->grp, drop_dev, n_groups, (long)n, h->gcnt);
+  hipLaunchKernelGGL(granule_offsets_kernel, dim3(1), dim3(1024), 0, s, h->gcnt, (long)nb, h->goff);
+  CC_HIP(hipGetLastError());
+  std::vector<unsigned long long> off((size_t)nb + 1);
+  CC_HIP(hipMemcpyAsync(off.data(), h->goff, off.size() * 8, hipMemcpyDeviceToHost, s));
+  CC_HIP(hipStreamSynchronize(s));
+  const int64_t total = (int64_t)off[nb];
+  if (total == n) return 0;                          // group removal that met no row
+  int64_t T = g_index_slab_rows.load();
+  T = T > 0 ? (T + kGran - 1) / kGran * kGran : kSlabRows;
+  const int64_t direct_min = std::max<int64_t>(kGran, T / 4);
+  const size_t rb = h->row_bytes();
+  const int chunks = (int)(rb / 16);                 // dim % 4 == 0 (f32) / dim % 256 == 0 (bf16): whole 16-byte pieces
+  char* emb = reinterpret_cast<char*>(h->emb);
+  int64_t ga = 0;                                    // granules before the first removed row stay where they are
+  while (ga < nb && (int64_t)off[ga + 1] - (int64_t)off[ga] == std::min<int64_t>(kGran, n - ga * kGran)) ++ga;
+  while (ga < nb) {
+    const int64_t a = ga * kGran, pa = (int64_t)off[ga];
+    int64_t gb;
+    if (a - pa >= direct_min) {
+      // the last boundary whose position is <= a; the next granule qualifies because it holds at most kGran <= gap survivors
+      gb = (std::upper_bound(off.begin() + ga + 1, off.end(), (unsigned long long)a) - off.begin()) - 1;
+      CC_CHECK(gb > ga, "index compaction made no progress");
+      if ((int64_t)off[gb] > pa)
+        hipLaunchKernelGGL(compact_kernel, dim3((unsigned)(gb - ga)), dim3(256), 0, s, reinterpret_cast<const uint4*>(emb), h->grp, h->trk,
+                           reinterpret_cast<uint4*>(emb), h->grp, h->trk, h->keep, h->goff, (long)ga, (long)n, 0L, chunks);
+    } else {
+      gb = std::min<int64_t>(nb, ga + T / kGran);
+      const int64_t ns = (int64_t)off[gb] - pa;
+      if (ns > 0) {
+        const size_t emb_bytes = ((size_t)T * rb + 255) & ~(size_t)255, ids_bytes = ((size_t)T * 4 + 255) & ~(size_t)255;
+        ensure((void**)&h->bounce, &h->bounce_cap, emb_bytes + 2 * ids_bytes);
+        int* bgrp = reinterpret_cast<int*>(h->bounce + emb_bytes); int* btrk = reinterpret_cast<int*>(h->bounce + emb_bytes + ids_bytes);
+        hipLaunchKernelGGL(compact_kernel, dim3((unsigned)(gb - ga)), dim3(256), 0, s, reinterpret_cast<const uint4*>(emb), h->grp, h->trk,
+                           reinterpret_cast<uint4*>(h->bounce), bgrp, btrk, h->keep, h->goff, (long)ga, (long)n, (long)pa, chunks);
+        const size_t n16 = (size_t)ns * chunks;
+        const unsigned blocks = (unsigned)std::min<size_t>((n16 + 1023) / 1024, 256 * 16);
+        hipLaunchKernelGGL(copy_down_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const uint4*>(h->bounce),
+                           reinterpret_cast<uint4*>(emb + (size_t)pa * rb), n16, bgrp, h->grp + pa, btrk, h->trk + pa, (long)ns);
+      }
+    }
+    ga = gb;
+  }
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipStreamSynchronize(s));
+  h->n = total;
+  if (removed) *removed = n - total;
+  CC_API_END
+}
 
 // Top-k among the rows whose group is allowed (allowed: n_groups bytes on the HOST, one per group id, non-zero = keep;
 // null = every row).  Rows of a group id >= n_groups are filtered out.  tracks: the answers are tracks (their best row) and
@@ -683,11 +888,16 @@ int cc_index_search(cc_index* h, const float* q, int Q, int k, int32_t* idx, flo
   return cc_index_search_groups(h, q, Q, k, nullptr, 0, idx, score, on_device, stream);
 }
 
+int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
+
+int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed) { return remove_impl(h, false, drop, 0, n_groups, removed); }
+
 void cc_index_destroy(cc_index* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev}) if (p) hipFree(p);
+  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)
   delete h;

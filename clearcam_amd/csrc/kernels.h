@@ -1,5 +1,6 @@
 // Kernel launchers (one translation unit per family).  All launches are asynchronous on `stream`.
 #pragma once
+#include <atomic>
 #include <vector>
 #include "common.h"
 
@@ -174,6 +175,8 @@ void grow_slot_streams(int device, hipStream_t base, std::vector<hipStream_t>& s
 void resize_slots(int device, hipStream_t base, std::vector<hipStream_t>& slot_stream, std::vector<hipEvent_t>& slot_done, int n);
 // what is enqueued on `waiter` from now on runs after what `signaller` holds now
 void order_after(hipStream_t waiter, hipStream_t signaller);
+// cc_dev_set("index_slab_rows"): rows per bounced slab of cc_index_remove_* (index.hip); -1 = the default
+extern std::atomic<int> g_index_slab_rows;
 
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;

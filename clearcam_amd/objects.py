@@ -186,6 +186,35 @@ class EmbeddingIndex:
         _lib.check(_lib.lib().cc_index_add_tracked(self._h, _lib.ptr(a), a.shape[0], int(on_dev), _lib.ptr(g) if g is not None else None,
                                                    _lib.ptr(t) if t is not None else None))
 
+    def remove(self, rows) -> int:
+        """Take rows out; the survivors keep their order and are renumbered densely (new id = survivors before the row), so
+        every search answers as an index built from the survivors would.  rows: a bool / uint8 mask with one entry per row
+        (non-zero removes), or an array of row numbers.  Compaction in place on the device (cc_index_remove_rows): capacity
+        and track slots stay.  Returns the number of rows removed."""
+        a = np.asarray(rows)
+        if a.dtype == np.bool_ or a.dtype == np.uint8:
+            mask = np.ascontiguousarray(a.reshape(-1), dtype=np.uint8)
+        else:
+            ids = a.reshape(-1).astype(np.int64)
+            n = len(self)
+            if ids.size and (ids.min() < 0 or ids.max() >= n):
+                raise IndexError(f"row numbers must be in [0, {n})")
+            mask = np.zeros(n, np.uint8)
+            mask[ids] = 1
+        removed = C.c_int64()
+        _lib.check(_lib.lib().cc_index_remove_rows(self._h, _lib.ptr(mask), int(mask.size), C.byref(removed)))
+        return removed.value
+
+    def remove_groups(self, drop) -> int:
+        """`remove` for every row whose group id g has drop[g] != 0 (uint8, one byte per group; groups past the end of `drop`
+        stay).  The keep flags are computed on the device from the stored group ids: no per-row work on the host."""
+        d = np.ascontiguousarray(np.asarray(drop).reshape(-1), dtype=np.uint8)
+        if d.size == 0:
+            return 0
+        removed = C.c_int64()
+        _lib.check(_lib.lib().cc_index_remove_groups(self._h, _lib.ptr(d), int(d.size), C.byref(removed)))
+        return removed.value
+
     def scores(self, q) -> np.ndarray:
         qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
         out = np.empty((qa.shape[0], len(self)), np.float32)
@@ -318,6 +347,40 @@ class _RowTable:
 
     def slots(self, start: int = 0) -> np.ndarray:
         return np.asarray(self.slot[start:], np.int32)
+
+    @staticmethod
+    def dir_of(path: str) -> str:
+        """The directory part `describe` groups by: '/'-normalised, with its trailing '/'."""
+        norm = path.replace("\\", "/")
+        return norm[:norm.rfind("/") + 1]
+
+    def remove(self, mask) -> int:
+        """Forget the rows with a non-zero entry in `mask` (one per row), in step with EmbeddingIndex.remove on the device: the
+        survivors keep their order.  Directory group ids and track slots are stable (`dirs` / `dir_id` / `slot_of` keep their
+        entries, the device keeps its ids), so a later crop of the same folder or track reuses them; `truthy` / `bad` are
+        recomputed for the groups that lost rows.  Returns the number of rows forgotten."""
+        drop = np.asarray(mask).reshape(-1) != 0
+        if drop.size != len(self.paths):
+            raise ValueError(f"expected one entry per row ({len(self.paths)}), got {drop.size}")
+        gone = np.flatnonzero(drop)
+        if gone.size == 0:
+            return 0
+        lost = {self.group[r] for r in gone.tolist()} - {0}
+        keep = np.flatnonzero(~drop).tolist()
+        self.paths = [self.paths[r] for r in keep]
+        self.group = [self.group[r] for r in keep]
+        self.oid = [self.oid[r] for r in keep]
+        self.slot = [self.slot[r] for r in keep]
+        for g in lost:
+            self.truthy[g] = self.bad[g] = False
+        for r, g in enumerate(self.group):
+            if g in lost:
+                oid = self.oid[r]
+                if oid:
+                    self.truthy[g] = True
+                elif oid is None and "_" in os.path.basename(self.paths[r]):   # a name `describe` could not parse
+                    self.bad[g] = True
+        return int(gone.size)
 
     def allowed(self, cam_name, timestamp) -> np.ndarray:
         al = np.zeros(len(self.dirs), np.uint8)
@@ -570,6 +633,61 @@ class ObjectFinder:
         if getattr(self, "_attached", False):
             index, table = self._dev["store"]
             self._add_rows(index, table, e, [path])
+
+    # -- retention: the NVR deletes day folders (clearcam.py:1347-1381, :574-578); the matrix has to forget their crops ------------
+    def _forget_dirs(self, gone) -> int:
+        """Drop every crop whose directory string satisfies `gone` from image_embeddings and from the attached matrix.
+        Returns the crops dropped: rows of the attached matrix, or dict entries when no store is attached."""
+        stale = [k for k in self.image_embeddings if gone(_RowTable.dir_of(k))]
+        for k in stale:
+            del self.image_embeddings[k]
+        if stale:
+            self._version["image"] += 1
+        if not getattr(self, "_attached", False):
+            return len(stale)
+        index, table = self._dev["store"]
+        drop = np.zeros(len(table.dirs), np.uint8)
+        for g in range(1, len(table.dirs)):
+            drop[g] = gone(table.dirs[g])
+        group = np.asarray(table.group, np.int64)
+        mask = drop[group] != 0 if group.size else np.zeros(0, bool)
+        loose = [r for r in np.flatnonzero(group == 0).tolist() if gone(_RowTable.dir_of(table.paths[r]))]   # names that are no *.jpg
+        if loose:                                     # group 0 mixes folders: these rows go by number
+            mask[loose] = True
+            n = index.remove(mask)
+        elif drop.any():
+            n = index.remove_groups(drop)             # flags from the group ids on the device: one call, no per-row upload
+        else:
+            return 0
+        table.remove(mask)
+        assert n == int(mask.sum()) and len(index) == len(table.paths)
+        return n
+
+    def forget(self, cam_name=None, timestamp=None) -> int:
+        """Drop every crop whose directory contains `/cameras/<cam_name>/` and / or `/objects/<timestamp>/` (both given: both
+        must match) from `image_embeddings` and, when a store is attached, from the device matrix, which is compacted in
+        place.  Nothing is deleted on disk: that is the NVR's job (clearcam.py:1347-1381, :574-578).  Returns the number of
+        crops dropped."""
+        if not cam_name and not timestamp:
+            raise ValueError("forget() needs cam_name and / or timestamp")
+
+        def gone(d: str) -> bool:
+            return (not cam_name or f"/cameras/{cam_name}/" in d) and (not timestamp or f"/objects/{timestamp}/" in d)
+        return self._forget_dirs(gone)
+
+    def sync_store(self) -> int:
+        """The reference's stale-key rule (models/objects.py:414-415) for the attached matrix: drop the crops whose day folder
+        no longer exists on disk, which is what `_cleanup_oldest_files` leaves behind.  Returns the rows dropped; 0 when no
+        store is attached."""
+        if not getattr(self, "_attached", False):
+            return 0
+        exists: Dict[str, bool] = {}
+
+        def gone(d: str) -> bool:
+            if d not in exists:
+                exists[d] = os.path.isdir(d) if d else True
+            return not exists[d]
+        return self._forget_dirs(gone)
 
     def _device_index(self, embeddings: Dict[str, np.ndarray], key: str = "image") -> Tuple[EmbeddingIndex, "_RowTable"]:
         """(Re)build the HBM-resident matrix of one of the reference's dicts when it changed (the reference reloads before

@@ -158,7 +158,9 @@ int cc_round_weights(int dtype, const float* w, int64_t cout, int64_t cin, int64
  * key "stream": the weights-resident streaming 1x1 kernel off (0) / on (1) / as CLEARCAM_STREAM says (-1);
  * key "tile64_w": tile geometry of the 3x3 64 -> 64 tile kernel, 32 (8 x 32 pixels) / 16 (16 x 16) / -1 (its own rule);
  * key "stream_flags": the CLEARCAM_STREAM_FLAGS bit set of the streaming 1x1 kernel (-1 = back to the environment / default);
- * keys "stream_abl", "tile64_abl": timing ablations of development builds (no effect otherwise).
+ * keys "stream_abl", "tile64_abl": timing ablations of development builds (no effect otherwise);
+ * key "index_slab_rows": rows per bounced slab of cc_index_remove_* (-1 = the measured default), so that a test can force many
+ *     slabs on a small index; rounded up to a multiple of 64.
  * Plans already built keep the launches they were built with.  Not part of the drop-in surface. */
 int cc_dev_set(const char* key, int value);
 
@@ -284,6 +286,12 @@ int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device
  * Arguments, k in [1, 1024] and the -1/-inf padding as in cc_index_search_groups; the index must hold < 2^31 rows. */
 int cc_index_search_tracks(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
                            int on_device, void* stream);
+/* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
+ * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
+ * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
+int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed);
+/* The same for every row whose group id g has drop[g] != 0; groups >= n_groups are kept. */
+int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed);
 void cc_index_destroy(cc_index* h);
 
 #ifdef __cplusplus
