@@ -17,7 +17,8 @@ SYMBOLS = [
     "cc_clip_create", "cc_clip_load", "cc_clip_finalize", "cc_clip_encode_image", "cc_clip_encode_text",
     "cc_clip_set_in_flight", "cc_clip_submit_image", "cc_clip_wait",
     "cc_clip_last_gpu_ms", "cc_clip_destroy", "cc_crop_preprocess", "cc_cv_resize_linear_u8", "cc_cv_warp_affine_u8",
-    "cc_blaze_create", "cc_blaze_load", "cc_blaze_finalize", "cc_blaze_detect", "cc_blaze_destroy",
+    "cc_blaze_create", "cc_blaze_load", "cc_blaze_finalize", "cc_blaze_detect", "cc_blaze_detect_batch", "cc_blaze_destroy",
+    "cc_face_locate", "cc_face_align",
     "cc_face_create", "cc_face_load", "cc_face_finalize", "cc_face_embed", "cc_face_destroy",
     "cc_ocsort_create", "cc_ocsort_update", "cc_ocsort_update_many", "cc_ocsort_num_tracks", "cc_ocsort_destroy",
     "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores",
@@ -29,6 +30,13 @@ SYMBOLS = [
 class ClipConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "v_width", "v_layers", "v_heads", "v_mlp",
                                        "t_ctx", "t_vocab", "t_width", "t_layers", "t_heads", "t_mlp", "embed")]
+
+
+class FaceAlignRec(C.Structure):
+    """cc_face_align_rec: one face of cc_face_align (crop, cut rectangle, the two forward warpAffine matrices)."""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("cx1", C.c_int32), ("cy1", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("rot", C.c_double * 6), ("place", C.c_double * 6)]
 
 
 class CCError(RuntimeError):
@@ -100,6 +108,9 @@ def lib() -> C.CDLL:
         "cc_blaze_load": [vp, C.c_char_p, vp, i64p, C.c_int],
         "cc_blaze_finalize": [vp],
         "cc_blaze_detect": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp],
+        "cc_blaze_detect_batch": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp],
+        "cc_face_locate": [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp],
+        "cc_face_align": [vp, C.c_int64, C.c_int, vp, C.c_int, vp, C.c_int, vp],
         "cc_face_create": [C.POINTER(vp), C.c_int, C.c_int],
         "cc_face_load": [vp, C.c_char_p, vp, i64p, C.c_int],
         "cc_face_finalize": [vp],

@@ -53,6 +53,31 @@ class ADAFACE:
         _lib.check(_lib.lib().cc_face_embed(self._h, _lib.ptr(f), f.shape[0], int(f.dtype == np.float32), 0, _lib.ptr(out), 0, None))
         return out
 
+    def embed_batch_device(self, faces_dev):
+        """`embed_batch` for faces that are already on the GPU: CUDA uint8 / float32 tensor (n,112,112,3) -> CUDA float32 (n,512),
+        ordered on the current torch stream.  No host copy on either side (cc_face_embed with both device flags set)."""
+        import torch
+        f = faces_dev
+        if not getattr(f, "is_cuda", False) or f.dim() != 4 or tuple(f.shape[1:]) != (112, 112, 3) or f.shape[0] == 0:
+            raise ValueError(f"faces must be a CUDA tensor (n,112,112,3) with n > 0, got {type(f).__name__} {tuple(getattr(f, 'shape', ()))}")
+        if f.dtype != torch.uint8:
+            f = f.float()
+        f = f.contiguous()
+        out = torch.empty((f.shape[0], 512), dtype=torch.float32, device=f.device)
+        cur = run = torch.cuda.current_stream(f.device)
+        if cur.cuda_stream == 0:
+            # torch's default stream has the handle 0, which the library reads as "no stream given": run on a side stream fenced by the
+            # current one on both sides instead (as EmbeddingIndex._search_device does)
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = torch.cuda.Stream(f.device)
+            run = self._side_stream
+            run.wait_stream(cur)
+        _lib.check(_lib.lib().cc_face_embed(self._h, _lib.ptr(f), f.shape[0], int(f.dtype == torch.float32), 1, _lib.ptr(out), 1,
+                                            C.c_void_p(run.cuda_stream)))
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
     def __call__(self, x) -> Tensor:
         f = as_numpy(x)
         if f.shape != (112, 112, 3):

@@ -50,6 +50,20 @@ class BlazeFace:
         _lib.check(_lib.lib().cc_blaze_detect(self._h, _lib.ptr(f), f.shape[0], f.shape[1], int(f.dtype == np.float32), 0, _lib.ptr(out), 0, None))
         return Tensor(out)
 
+    def detect_batch(self, imgs) -> np.ndarray:
+        """(B,H,W,3) uint8 / float32 images of one size -> (B,896,17) float32: row block b is what `__call__` returns for image b.
+        One captured graph per (H, W, B) instead of B passes of ~75 launches."""
+        f = as_numpy(imgs)
+        if f.ndim != 4 or f.shape[3] != 3 or f.shape[0] == 0:
+            raise ValueError(f"images must be (B,H,W,3) with B > 0, got {f.shape}")
+        if f.dtype != np.uint8:
+            f = f.astype(np.float32, copy=False)
+        f = np.ascontiguousarray(f)
+        out = np.empty((f.shape[0], 896, 17), np.float32)
+        _lib.check(_lib.lib().cc_blaze_detect_batch(self._h, _lib.ptr(f), f.shape[0], f.shape[1], f.shape[2], int(f.dtype == np.float32), 0,
+                                                    _lib.ptr(out), 0, None))
+        return out
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             _lib.lib().cc_blaze_destroy(self._h)

@@ -7,8 +7,11 @@
 //    output size: the loaders read zeros outside the image, which is exactly asymmetric bottom/right padding;
 //  * BlazeBlock = depthwise conv -> 1x1 conv whose epilogue adds the shortcut and then applies ReLU (act 4);  a stride-2
 //    block's shortcut is a 2x2 max-pool written into the low channels of a zero-filled buffer (the channel zero-pad);
-//  * the four heads write float32; one 1024-thread block then decodes the 896 anchors, orders them by score (bitonic sort
+//  * the four heads write float32; one 1024-thread block per image then decodes the 896 anchors, orders them by score (bitonic sort
 //    keyed on (score, index) = the stable descending order), applies the reference's overlap rule and maps boxes back.
+//  * a plan holds B images of one size (key {H, W, f32, B}; cc_blaze_detect is B = 1): the convs and pools run over the batch,
+//    the post kernel one block per image.  It also picks, per image, the first row the caller's filter keeps - what the batched
+//    face path (cc_face_locate: ragged letterbox of B crops straight into the plan's input) downloads instead of (896,17) rows.
 #include <cmath>
 #include <map>
 #include <memory>
@@ -36,15 +39,18 @@ struct PostP {                 // decode (:194-226), postprocess (:228-238), bac
   float scale; int pad_top, pad_left;
   float* rows;                 // (896,17) scratch: decoded, unsorted
   float* out;                  // (896,17)
-};
+  float* first; int* first_idx;   // (17) the first row of `out` whose ymin is not 0 (zeros when none), and its number or -1
+};                             // every pointer but `anchors` is image 0's; one block per image steps them by the image's size
 
 struct BOp { int kind; ConvP conv; PoolP pool; PreP pre; PostP post; };   // 0 conv, 1 pool, 2 preprocess, 3 decode+postprocess
 
 struct BPlan {
-  int H = 0, W = 0, f32 = 0;
+  int H = 0, W = 0, f32 = 0, B = 1;
   std::vector<void*> allocs;
   std::vector<BOp> ops;
   void* in_dev = nullptr; float* out_dev = nullptr;
+  float* first_dev = nullptr; int* first_idx_dev = nullptr;        // (B,17), (B): blaze_post_kernel's pick per image
+  FaceBoxRec* box_dev = nullptr;                                   // (B) letterbox records of cc_face_locate
   hipGraphExec_t exec = nullptr;
   ~BPlan() { if (exec) hipGraphExecDestroy(exec); for (void* p : allocs) hipFree(p); }
   char* alloc(size_t bytes, bool zero = false) {
@@ -54,11 +60,19 @@ struct BPlan {
   }
 };
 
-__global__ __launch_bounds__(1024) void blaze_post_kernel(const PostP p) {
+__global__ __launch_bounds__(1024) void blaze_post_kernel(const PostP p0) {
   __shared__ float box[kAnchors][4];                             // sorted boxes for the 896 x 896 overlap pass
   __shared__ float key[1024];
   __shared__ short ord[1024];
+  __shared__ int first_row;
   const int i = threadIdx.x;
+  PostP p = p0;                                                  // this block's image
+  {
+    const size_t b = blockIdx.x;
+    p.r8 += b * (16 * 16 * 32); p.r16 += b * (8 * 8 * 96); p.c8 += b * (16 * 16 * 2); p.c16 += b * (8 * 8 * 6);
+    p.rows += b * ((size_t)kAnchors * 17); p.out += b * ((size_t)kAnchors * 17); p.first += b * 17; p.first_idx += b;
+  }
+  if (i == 0) first_row = kAnchors;
   if (i < kAnchors) {
     const float* raw = i < 512 ? p.r8 + (size_t)i * 16 : p.r16 + (size_t)(i - 512) * 16;
     const float sraw = i < 512 ? p.c8[i] : p.c16[i - 512];
@@ -96,6 +110,7 @@ __global__ __launch_bounds__(1024) void blaze_post_kernel(const PostP p) {
     box[i][0] = r[0]; box[i][1] = r[1]; box[i][2] = r[2]; box[i][3] = r[3];
   }
   __syncthreads();
+  float ymin = 0.0f;                                             // this thread's row of `out`, column 0
   if (i < kAnchors) {
     const float x1 = box[i][0], y1 = box[i][1], x2 = box[i][2], y2 = box[i][3];
     const float area = (x2 - x1) * (y2 - y1);
@@ -116,8 +131,15 @@ __global__ __launch_bounds__(1024) void blaze_post_kernel(const PostP p) {
       if (k == 0 || k == 2) v -= (float)p.pad_top;
       if (k == 1 || k == 3) v -= (float)p.pad_left;
       o[k] = v / p.scale;                                        // every column, as the reference writes it (:192)
+      if (k == 0) ymin = o[0];
     }
   }
+  // The caller's filter in ObjectFinder.img_to_face, `found[found[:, 0] != 0][0]`, done here: the first row whose ymin is not 0.  As
+  // there, a surviving row whose ymin is exactly 0 is passed over, and a suppressed row counts when the back-map moved its 0.
+  if (i < kAnchors && ymin != 0.0f) atomicMin(&first_row, i);
+  __syncthreads();                                               // the rows of `out` above are visible to the whole block too
+  if (i < 17) p.first[i] = first_row < kAnchors ? p.out[(size_t)first_row * 17 + i] : 0.0f;
+  if (i == 0) *p.first_idx = first_row < kAnchors ? first_row : -1;
 }
 
 }  // namespace
@@ -150,7 +172,7 @@ void run_ops(cc_blaze* h, BPlan* P, hipStream_t s) {
     if (op.kind == 0) launch_conv(h->dtype, op.conv, s);
     else if (op.kind == 1) launch_pool(h->dtype, op.pool, s);
     else if (op.kind == 2) launch_preprocess(h->dtype, op.pre, s);
-    else hipLaunchKernelGGL(blaze_post_kernel, dim3(1), dim3(1024), 0, s, op.post);
+    else hipLaunchKernelGGL(blaze_post_kernel, dim3(P->B), dim3(1024), 0, s, op.post);
   }
   CC_HIP(hipGetLastError());
 }
@@ -161,15 +183,15 @@ template <class T> T* to_dev(BPlan* P, const std::vector<T>& v) {
   return d;
 }
 
-BPlan* get_plan(cc_blaze* h, int H, int W, int f32) {
-  const std::vector<int> key{H, W, f32};
+BPlan* get_plan(cc_blaze* h, int H, int W, int f32, int B) {
+  const std::vector<int> key{H, W, f32, B};
   if (BPlan* hit = h->plans.find(key)) return hit;
-  std::unique_ptr<BPlan> P(new BPlan()); P->H = H; P->W = W; P->f32 = f32;
+  std::unique_ptr<BPlan> P(new BPlan()); P->H = H; P->W = W; P->f32 = f32; P->B = B;
   const size_t es = dtype_size(h->dtype);
-  auto act = [&](int hh, int ww, int c, bool zero = false) { return P->alloc((size_t)hh * ww * c * es, zero); };
+  auto act = [&](int hh, int ww, int c, bool zero = false) { return P->alloc((size_t)B * hh * ww * c * es, zero); };
   auto add_conv = [&](const PConv& pc, const void* x, int hh, int ww, int stride, void* out, int out_f32, int actv, const void* res,
                       int pad = -1, int Ho = 0) {
-    BOp op{}; op.kind = 0; op.conv = conv_params(pc, x, 1, hh, ww, stride, out, pc.cout, out_f32, actv, res, pc.cout, pad, Ho, Ho);
+    BOp op{}; op.kind = 0; op.conv = conv_params(pc, x, B, hh, ww, stride, out, pc.cout, out_f32, actv, res, pc.cout, pad, Ho, Ho);
     P->ops.push_back(op);
   };
   // ---- preprocess geometry (:166-179)
@@ -180,13 +202,15 @@ BPlan* get_plan(cc_blaze* h, int H, int W, int f32) {
   const int pad_top = (kIn - new_h) / 2, pad_left = (kIn - new_w) / 2;
   std::vector<int> xlo, xhi, ylo, yhi; std::vector<float> xfr, yfr;
   axis_tables(W, new_w, xlo, xhi, xfr); axis_tables(H, new_h, ylo, yhi, yfr);
-  P->in_dev = P->alloc((size_t)H * W * 3 * (f32 ? 4 : 1));
-  P->out_dev = (float*)P->alloc((size_t)kAnchors * 17 * 4);
+  P->in_dev = P->alloc((size_t)B * H * W * 3 * (f32 ? 4 : 1));
+  P->out_dev = (float*)P->alloc((size_t)B * kAnchors * 17 * 4);
+  P->first_dev = (float*)P->alloc((size_t)B * 17 * 4); P->first_idx_dev = (int*)P->alloc((size_t)B * 4);
+  P->box_dev = (FaceBoxRec*)P->alloc((size_t)B * sizeof(FaceBoxRec));
   const int cp = h->stem.cin;
   char* x0 = act(kIn, kIn, cp);
   {
     BOp op{}; op.kind = 2; PreP& q = op.pre;
-    q.frames = P->in_dev; q.frame_f32 = f32; q.B = 1; q.H = H; q.W = W; q.nh = new_h; q.nw = new_w; q.pad_y = pad_top; q.pad_x = pad_left;
+    q.frames = P->in_dev; q.frame_f32 = f32; q.B = B; q.H = H; q.W = W; q.nh = new_h; q.nw = new_w; q.pad_y = pad_top; q.pad_x = pad_left;
     q.Hn = kIn; q.Wn = kIn; q.xlo = to_dev(P.get(), xlo); q.xhi = to_dev(P.get(), xhi); q.xfr = to_dev(P.get(), xfr);
     q.ylo = to_dev(P.get(), ylo); q.yhi = to_dev(P.get(), yhi); q.yfr = to_dev(P.get(), yfr);
     q.out = x0; q.out_c = cp; q.flip = 0; q.div = 127.5f; q.sub = 1.0f; q.pad_val = -1.0f;      // x / 127.5 - 1 over the padded image
@@ -203,7 +227,7 @@ BPlan* get_plan(cc_blaze* h, int H, int W, int f32) {
     const char* sc = x;
     if (b.stride == 2) {                                                    // max_pool2d(2,2) and the channel zero-pad
       char* s2 = act(So, So, b.cout, true);
-      BOp op{}; op.kind = 1; op.pool = PoolP{x, b.cin, 0, s2, b.cout, 0, 1, S, S, b.cin, So, So, 2, 2, 0, 1};
+      BOp op{}; op.kind = 1; op.pool = PoolP{x, b.cin, 0, s2, b.cout, 0, B, S, S, b.cin, So, So, 2, 2, 0, 1};
       P->ops.push_back(op); sc = s2;
     }
     char* y = act(So, So, b.cout);
@@ -215,13 +239,13 @@ BPlan* get_plan(cc_blaze* h, int H, int W, int f32) {
   add_conv(h->fdw, x, 16, 16, 2, ft, 0, 0, nullptr, 0, 8);
   char* hf = act(8, 8, 96);
   add_conv(h->fpw, ft, 8, 8, 1, hf, 0, 4, nullptr);
-  float* c8 = (float*)P->alloc(16 * 16 * 2 * 4); float* c16 = (float*)P->alloc(8 * 8 * 6 * 4);
-  float* r8 = (float*)P->alloc(16 * 16 * 32 * 4); float* r16 = (float*)P->alloc(8 * 8 * 96 * 4);
+  float* c8 = (float*)P->alloc((size_t)B * 16 * 16 * 2 * 4); float* c16 = (float*)P->alloc((size_t)B * 8 * 8 * 6 * 4);
+  float* r8 = (float*)P->alloc((size_t)B * 16 * 16 * 32 * 4); float* r16 = (float*)P->alloc((size_t)B * 8 * 8 * 96 * 4);
   add_conv(h->cls8, x, 16, 16, 1, c8, 1, 0, nullptr);
   add_conv(h->cls16, hf, 8, 8, 1, c16, 1, 0, nullptr);
   add_conv(h->reg8, x, 16, 16, 1, r8, 1, 0, nullptr);
   add_conv(h->reg16, hf, 8, 8, 1, r16, 1, 0, nullptr);
-  { BOp op{}; op.kind = 3; op.post = PostP{r8, r16, c8, c16, h->anchors, scale, pad_top, pad_left, (float*)P->alloc((size_t)kAnchors * 17 * 4), P->out_dev}; P->ops.push_back(op); }
+  { BOp op{}; op.kind = 3; op.post = PostP{r8, r16, c8, c16, h->anchors, scale, pad_top, pad_left, (float*)P->alloc((size_t)B * kAnchors * 17 * 4), P->out_dev, P->first_dev, P->first_idx_dev}; P->ops.push_back(op); }
   BPlan* pp = P.get();
   P->exec = capture_graph(h->stream, [&]() { run_ops(h, pp, h->stream); });
   return h->plans.insert(key, std::move(P), h->stream);
@@ -281,30 +305,59 @@ int cc_blaze_finalize(cc_blaze* h) {
   CC_API_END
 }
 
-int cc_blaze_detect(cc_blaze* h, const void* img, int H, int W, int img_f32, int img_on_device, float* out, int out_on_device, void* stream) {
+// what is enqueued on the handle's stream from now on runs after what the caller's stream holds now (no stream given: nothing to order)
+static void after_caller(cc_blaze* h, void* stream) {
+  if (stream) order_after(h->stream, (hipStream_t)stream);
+}
+
+int cc_blaze_detect_batch(cc_blaze* h, const void* imgs, int B, int H, int W, int img_f32, int imgs_on_device, float* out, int out_on_device, void* stream) {
   CC_API_BEGIN
-  CC_CHECK(h && img && out && H > 0 && W > 0, "bad argument");
+  CC_CHECK(h && imgs && out && B > 0 && H > 0 && W > 0, "bad argument");
   CC_CHECK(h->finalized, "cc_blaze_detect before cc_blaze_finalize");
   CC_HIP(hipSetDevice(h->device));
-  BPlan* P = get_plan(h, H, W, img_f32 ? 1 : 0);
+  BPlan* P = get_plan(h, H, W, img_f32 ? 1 : 0, B);
   hipStream_t s = h->stream;
-  if (stream) {
-    hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    CC_HIP(hipEventRecord(e, (hipStream_t)stream)); CC_HIP(hipStreamWaitEvent(s, e, 0)); CC_HIP(hipEventDestroy(e));
-  }
-  CC_HIP(hipMemcpyAsync(P->in_dev, img, (size_t)H * W * 3 * (img_f32 ? 4 : 1), img_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  after_caller(h, stream);
+  CC_HIP(hipMemcpyAsync(P->in_dev, imgs, (size_t)B * H * W * 3 * (img_f32 ? 4 : 1), imgs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   CC_HIP(hipGraphLaunch(P->exec, s));
-  const size_t ob = (size_t)kAnchors * 17 * 4;
+  const size_t ob = (size_t)B * kAnchors * 17 * 4;
   if (out_on_device) {
     CC_HIP(hipMemcpyAsync(out, P->out_dev, ob, hipMemcpyDeviceToDevice, s));
-    if (stream) {
-      hipEvent_t e; CC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      CC_HIP(hipEventRecord(e, s)); CC_HIP(hipStreamWaitEvent((hipStream_t)stream, e, 0)); CC_HIP(hipEventDestroy(e));
-    }
+    if (stream) order_after((hipStream_t)stream, s);
   } else {
     CC_HIP(hipMemcpyAsync(out, P->out_dev, ob, hipMemcpyDeviceToHost, s));
     CC_HIP(hipStreamSynchronize(s));
   }
+  CC_API_END
+}
+
+int cc_blaze_detect(cc_blaze* h, const void* img, int H, int W, int img_f32, int img_on_device, float* out, int out_on_device, void* stream) {
+  return cc_blaze_detect_batch(h, img, 1, H, W, img_f32, img_on_device, out, out_on_device, stream);
+}
+
+int cc_face_locate(cc_blaze* h, const uint8_t* pixels, int64_t pixels_bytes, const int64_t* offsets, const int32_t* heights, const int32_t* widths,
+                   int B, int pixels_on_device, float* first, int32_t* first_idx, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && pixels && offsets && heights && widths && first && first_idx && B > 0 && pixels_bytes > 0, "bad argument");
+  CC_CHECK(h->finalized, "cc_face_locate before cc_blaze_finalize");
+  CC_HIP(hipSetDevice(h->device));
+  std::vector<FaceBoxRec> rec;
+  face_box_records(offsets, heights, widths, B, (size_t)pixels_bytes, rec);          // refuses bad crops before any GPU work
+  BPlan* P = get_plan(h, kFaceBox, kFaceBox, 0, B);
+  hipStream_t s = h->stream;
+  after_caller(h, stream);
+  uint8_t* dpix = nullptr;
+  if (!pixels_on_device) {
+    CC_HIP(hipMallocAsync((void**)&dpix, (size_t)pixels_bytes, s));
+    CC_HIP(hipMemcpyAsync(dpix, pixels, (size_t)pixels_bytes, hipMemcpyHostToDevice, s));
+  }
+  CC_HIP(hipMemcpyAsync(P->box_dev, rec.data(), sizeof(FaceBoxRec) * B, hipMemcpyHostToDevice, s));
+  launch_face_letterbox(dpix ? dpix : pixels, P->box_dev, B, (uint8_t*)P->in_dev, s);   // straight into the plan's input: no copy
+  CC_HIP(hipGraphLaunch(P->exec, s));
+  CC_HIP(hipMemcpyAsync(first, P->first_dev, (size_t)B * 17 * 4, hipMemcpyDeviceToHost, s));
+  CC_HIP(hipMemcpyAsync(first_idx, P->first_idx_dev, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  if (dpix) CC_HIP(hipFreeAsync(dpix, s));
+  CC_HIP(hipStreamSynchronize(s));          // `rec` and the caller's host buffers may go away on return
   CC_API_END
 }
 

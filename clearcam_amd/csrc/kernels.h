@@ -162,6 +162,15 @@ struct HeadTailP {
 };
 bool head_tail_supported(int dt, int ch, int split = 0);
 void launch_head_tail(int dt, const HeadTailP& p, hipStream_t stream);
+// ---- batched face path (crop.hip) ----------------------------------------------------------------
+// One record per crop of a packed uint8 HWC buffer: ObjectFinder.img_to_face's letterbox to kFaceBox (resize_linear to dh x dw, centred
+// in zeros).  face_box_records computes them on the host exactly as the Python does (double arithmetic) and refuses a crop that lies
+// outside the buffer or whose letterboxed side would be 0; launch_face_letterbox writes (B, kFaceBox, kFaceBox, 3) uint8.
+constexpr int kFaceBox = 640;
+struct FaceBoxRec { long long off; int h, w, dh, dw, top, left, area2, reserved; };
+void face_box_records(const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B, size_t pix_bytes, std::vector<FaceBoxRec>& rec);
+void launch_face_letterbox(const uint8_t* pix_dev, const FaceBoxRec* rec_dev, int B, uint8_t* out_dev, hipStream_t stream);
+
 // ---- shared runtime (runtime.hip) ---------------------------------------------------------------
 // Streams of handles come from a process-wide pool per device and go back to it when a handle dies - they are NEVER destroyed.
 // Destroying streams makes the runtime re-deal its few hardware queues, and a handle created afterwards has been seen replaying

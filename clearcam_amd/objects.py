@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import pickle
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -394,29 +394,58 @@ class _RowTable:
         return al
 
 
-def preprocess_crops(crops, size: int = 224, device: int = 0):
-    """cc_crop_preprocess over a list of (H,W,3) uint8 arrays (host) -> torch device tensor (B,3,size,size) f32."""
-    import torch
+def pack_crops(crops, tail: int = 0):
+    """List of (H,W,3) uint8 arrays -> (packed bytes, offsets int64, heights int32, widths int32): the packed-buffer convention of
+    cc_crop_preprocess / cc_face_locate / cc_face_align.  `tail` zero bytes are appended behind the last crop."""
     crops = [np.ascontiguousarray(c, dtype=np.uint8) for c in crops]
     for c in crops:
         if c.ndim != 3 or c.shape[2] != 3 or c.size == 0:
             raise ValueError(f"crop must be a non-empty (H,W,3) uint8 array, got {c.shape}")
-    B = len(crops)
-    if B == 0:
+    if len(crops) == 0:
         raise ValueError("no crops")
     sizes = np.array([c.size for c in crops], np.int64)
     offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    packed = np.concatenate([c.reshape(-1) for c in crops])
+    packed = np.concatenate([c.reshape(-1) for c in crops] + ([np.zeros(tail, np.uint8)] if tail else []))
     hs = np.array([c.shape[0] for c in crops], np.int32)
     ws = np.array([c.shape[1] for c in crops], np.int32)
+    return packed, offsets, hs, ws
+
+
+def preprocess_crops(crops, size: int = 224, device: int = 0):
+    """cc_crop_preprocess over a list of (H,W,3) uint8 arrays (host) -> torch device tensor (B,3,size,size) f32."""
+    import torch
+    packed, offsets, hs, ws = pack_crops(crops)
+    B = len(hs)
     out = torch.empty((B, 3, size, size), dtype=torch.float32, device=torch.device("cuda", device))
     _lib.check(_lib.lib().cc_crop_preprocess(_lib.ptr(packed), _lib.ptr(offsets), _lib.ptr(hs), _lib.ptr(ws), B, 0, size, _lib.ptr(out), device,
                                    torch.cuda.current_stream(device).cuda_stream))
     return out
 
 
+class FaceGeometry(NamedTuple):
+    """What `ObjectFinder._face_geometry` hands to the two warps: the cut rectangle inside the crop, the forward matrix that levels
+    it into an out_w x out_h image (float64), and the forward matrix that places the eyes in the 112 x 112 face (float32)."""
+    cx1: int
+    cy1: int
+    cw: int
+    ch: int
+    rot: np.ndarray
+    out_w: int
+    out_h: int
+    place: np.ndarray
+
+
+class _PackedCrops(NamedTuple):
+    buf: object                # CUDA uint8 tensor: the packed crops + three zero bytes
+    nbytes: int
+    offsets: np.ndarray
+    hs: np.ndarray
+    ws: np.ndarray
+
+
 class ObjectFinder:
-    """``models/objects.py:188-422`` minus the face pipeline (out of scope)."""
+    """``models/objects.py:188-422``.  The face pipeline per crop as in the reference (`img_to_face`, `preprocess_face`) and
+    for batches of crops (`faces_from_crops`, `embed_faces`, `index_faces`: two device passes, the same pixels)."""
 
     def __init__(self, base_path: str = "data/cameras"):
         self.base_path = base_path
@@ -491,7 +520,22 @@ class ObjectFinder:
         found = found[found[:, 0] != 0]
         if found.shape[0] == 0:
             return None
-        first = found[0]
+        g = self._face_geometry(found[0], h, w)
+        if g is None:
+            return None
+        cut = full[g.cy1:g.cy1 + g.ch, g.cx1:g.cx1 + g.cw]
+        level = cvops.warp_affine(cut, g.rot, (g.out_w, g.out_h), dev)
+        face = cvops.warp_affine(level, g.place, (self.FACE_SIZE, self.FACE_SIZE), dev)
+        return np.ascontiguousarray(face[:, :, ::-1])
+
+    @classmethod
+    def _face_geometry(cls, first, h: int, w: int) -> Optional[FaceGeometry]:
+        """The arithmetic of `img_to_face` between the detector and the two warps, in float64 on the host, shared by the per-crop
+        and the batched path so that both cut, rotate and place the same pixels.  first: the first surviving BlazeFace row
+        (17 values in the coordinates of the 640 letterbox of an h x w crop).  None: face narrower than 50 px, or an empty cut."""
+        scale = 640 / max(h, w)
+        gap_w, gap_h = 640 - int(w * scale), 640 - int(h * scale)
+        top, left = gap_h // 2, gap_w // 2
         offset = np.array([left, top])
         y1, x1, y2, x2 = ((float(first[0]) - top) / scale, (float(first[1]) - left) / scale,
                           (float(first[2]) - top) / scale, (float(first[3]) - left) / scale)
@@ -499,30 +543,174 @@ class ObjectFinder:
         eye_b = (np.array([first[6], first[7]]) - offset) / scale
         if (x2 - x1) < 50:
             return None
-        goal_a, goal_b = np.array(self.EYE_LEFT), np.array(self.EYE_RIGHT)
+        goal_a, goal_b = np.array(cls.EYE_LEFT), np.array(cls.EYE_RIGHT)
         mid = (eye_a + eye_b) / 2
         tilt = np.degrees(np.arctan2(eye_b[1] - eye_a[1], eye_b[0] - eye_a[0]))
         side = max(x2 - x1, y2 - y1) * 2.0
-        H, W = full.shape[:2]
+        H, W = h, w
         cx1, cy1 = max(0, int(mid[0] - side / 2)), max(0, int(mid[1] - side / 2))
         cx2, cy2 = min(W, int(mid[0] + side / 2)), min(H, int(mid[1] + side / 2))
         if cx2 <= cx1 or cy2 <= cy1:
             return None
-        cut = full[cy1:cy2, cx1:cx2]
-        ch, cw = cut.shape[:2]
+        ch, cw = cy2 - cy1, cx2 - cx1
         corner = np.array([cx1, cy1])
-        rot = cvops.rotation_matrix_2d((cw / 2, ch / 2), float(tilt), 1.0)
+        from .cvops import rotation_matrix_2d
+        rot = rotation_matrix_2d((cw / 2, ch / 2), float(tilt), 1.0)
         c, s_ = abs(rot[0, 0]), abs(rot[0, 1])
         out_w, out_h = int(ch * s_ + cw * c), int(ch * c + cw * s_)
         rot[0, 2] += out_w / 2 - cw / 2
         rot[1, 2] += out_h / 2 - ch / 2
-        level = cvops.warp_affine(cut, rot, (out_w, out_h), dev)
         a_rot = rot[:, :2] @ (eye_a - corner) + rot[:, 2]
         b_rot = rot[:, :2] @ (eye_b - corner) + rot[:, 2]
         zoom = np.linalg.norm(goal_b - goal_a) / np.linalg.norm(b_rot - a_rot)
         place = np.array([[zoom, 0, goal_a[0] - a_rot[0] * zoom], [0, zoom, goal_a[1] - a_rot[1] * zoom]], np.float32)
-        face = cvops.warp_affine(level, place, (self.FACE_SIZE, self.FACE_SIZE), dev)
-        return np.ascontiguousarray(face[:, :, ::-1])
+        return FaceGeometry(cx1, cy1, cw, ch, rot, out_w, out_h, place)
+
+    # -- the same for a batch of crops: two device passes, one small download between them ---------------------------------
+    FACE_CHUNK = 32                # crops per BlazeFace pass; tails are padded to a power of two: six plans at the most
+
+    def _upload_crops(self, crops) -> "_PackedCrops":
+        """Pack the crops as `preprocess_crops` does and upload them once; both passes read that buffer.  Three zero bytes behind the
+        last crop are the blank 1 x 1 image that pads a tail chunk."""
+        import torch
+        packed, offsets, hs, ws = pack_crops(crops, tail=3)
+        for i, (h, w) in enumerate(zip(hs.tolist(), ws.tolist())):
+            scale = 640 / max(h, w)
+            if int(h * scale) == 0 or int(w * scale) == 0:
+                raise ValueError(f"crop {i} ({h} x {w}): a side of its 640 letterbox would be 0")
+        dev = torch.device("cuda", self.blazeface.device)
+        buf = torch.as_tensor(packed).to(dev)
+        torch.cuda.current_stream(dev).synchronize()          # the library's own streams read the buffer: it has to be there
+        return _PackedCrops(buf, int(packed.size), offsets, hs, ws)
+
+    def _locate(self, pk: "_PackedCrops"):
+        """-> (rows (B,17), found (B,), geometry per crop or None)"""
+        B = len(pk.hs)
+        rows, idx = np.zeros((B, 17), np.float32), np.full(B, -1, np.int32)
+        L = _lib.lib()
+        for lo in range(0, B, self.FACE_CHUNK):
+            n = min(self.FACE_CHUNK, B - lo)
+            nb = 1 << (n - 1).bit_length()                     # next power of two
+            off = np.full(nb, pk.nbytes - 3, np.int64); off[:n] = pk.offsets[lo:lo + n]
+            hs = np.ones(nb, np.int32); hs[:n] = pk.hs[lo:lo + n]
+            ws = np.ones(nb, np.int32); ws[:n] = pk.ws[lo:lo + n]
+            first, fidx = np.empty((nb, 17), np.float32), np.empty(nb, np.int32)
+            _lib.check(L.cc_face_locate(self.blazeface._h, _lib.ptr(pk.buf), pk.nbytes, _lib.ptr(off), _lib.ptr(hs), _lib.ptr(ws), nb, 1,
+                                        _lib.ptr(first), _lib.ptr(fidx), None))
+            rows[lo:lo + n], idx[lo:lo + n] = first[:n], fidx[:n]
+        geos = self._geometries(pk, rows, idx >= 0)
+        return rows, np.array([g is not None for g in geos], bool), geos
+
+    def _geometries(self, pk: "_PackedCrops", rows, found) -> List[Optional[FaceGeometry]]:
+        rows, found = np.asarray(rows), np.asarray(found, bool)
+        B = len(pk.hs)
+        if rows.shape != (B, 17) or found.shape != (B,):
+            raise ValueError(f"expected rows ({B},17) and found ({B},), got {rows.shape} and {found.shape}")
+        geos: List[Optional[FaceGeometry]] = [None] * B
+        for i in np.flatnonzero(found).tolist():
+            g = geos[i] = self._face_geometry(rows[i], int(pk.hs[i]), int(pk.ws[i]))
+            if g is not None and (g.out_w <= 0 or g.out_h <= 0):
+                raise ValueError(f"crop {i}: empty destination size")         # what cvops.warp_affine says in img_to_face
+        return geos
+
+    def _align(self, pk: "_PackedCrops", geos, device_out: bool):
+        import torch
+        B = len(pk.hs)
+        pos = [i for i in range(B) if geos[i] is not None]
+        geo = [geos[i] for i in pos]
+        dev = pk.buf.device
+        faces = torch.empty((len(pos), self.FACE_SIZE, self.FACE_SIZE, 3), dtype=torch.uint8, device=dev)
+        if pos:
+            rec = (_lib.FaceAlignRec * len(pos))()
+            for r, i, g in zip(rec, pos, geo):
+                r.offset, r.h, r.w = int(pk.offsets[i]), int(pk.hs[i]), int(pk.ws[i])
+                r.cx1, r.cy1, r.cw, r.ch, r.out_w, r.out_h = g.cx1, g.cy1, g.cw, g.ch, g.out_w, g.out_h
+                r.rot[:] = np.asarray(g.rot, np.float64).reshape(-1).tolist()
+                r.place[:] = np.asarray(g.place, np.float64).reshape(-1).tolist()
+            _lib.check(_lib.lib().cc_face_align(_lib.ptr(pk.buf), pk.nbytes, 1, C.byref(rec), len(pos), _lib.ptr(faces), dev.index,
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        if device_out:
+            return faces, np.asarray(pos, np.int64)
+        out: List[Optional[np.ndarray]] = [None] * B
+        host = faces.cpu().numpy()
+        for k, i in enumerate(pos):
+            out[i] = host[k]
+        return out
+
+    def locate_faces(self, crops) -> Tuple[np.ndarray, np.ndarray]:
+        """First pass of the batched `img_to_face`: every crop letterboxed to 640 on the GPU (ragged, one launch), BlazeFace over
+        the batch, and per crop the first surviving detection -> (rows (B,17) float32, found (B,) bool).  rows[i] is the row
+        `img_to_face` names `first` for crop i (zeros when nothing was detected); found[i] says that crop i yields a face: a
+        detection that also passes `_face_geometry` (at least 50 px wide, a cut inside the crop)."""
+        return self._locate(self._upload_crops(crops))[:2]
+
+    def faces_from_rows(self, crops, rows, found, device_out: bool = False):
+        """Second pass: `_face_geometry` per found row on the host, then cut, level and place every face in one launch (the
+        levelled image is never written).  Returns a list with one (112,112,3) uint8 array or None per crop - bit for bit what
+        `img_to_face` returns for that row - or, with device_out=True, a CUDA uint8 tensor (n,112,112,3) and the positions of
+        its rows among the crops."""
+        pk = self._upload_crops(crops)
+        return self._align(pk, self._geometries(pk, rows, found), device_out)
+
+    def faces_from_crops(self, crops, device_out: bool = False):
+        """`img_to_face` for a batch: `locate_faces` then `faces_from_rows` over ONE upload of the packed crops."""
+        pk = self._upload_crops(crops)
+        return self._align(pk, self._locate(pk)[2], device_out)
+
+    def embed_faces(self, crops) -> Tuple[np.ndarray, np.ndarray]:
+        """Crops -> (emb (B,512) float32, valid (B,) bool): aligned faces stay on the GPU and go straight into AdaFace.  Rows of
+        crops without a face are zero.  AdaFace runs on at most FACE_CHUNK faces at a time, in power-of-two pieces (a plan per
+        batch size: six at the most)."""
+        import torch
+        faces, pos = self.faces_from_crops(crops, device_out=True)
+        emb, valid = np.zeros((len(crops), 512), np.float32), np.zeros(len(crops), bool)
+        n, lo, parts = int(faces.shape[0]), 0, []
+        while lo < n:
+            step = min(self.FACE_CHUNK, 1 << ((n - lo).bit_length() - 1))
+            parts.append(self.adaface.embed_batch_device(faces[lo:lo + step]))
+            lo += step
+        if parts:
+            emb[pos] = torch.cat(parts).cpu().numpy()
+            valid[pos] = True
+        return emb, valid
+
+    def add_face_embeddings(self, paths, embs) -> None:
+        """The face twin of `add_embedding`, what clearcam.py:1233-1241 does per crop: 512-d rows keyed by the crop paths, appended
+        to the store of <cam>/faces/<day>/ (the crop's <cam>/objects/<day>/ folder with `objects` replaced), entered in
+        `face_embeddings`, face version bumped (the next face search rebuilds its device matrix)."""
+        from .store import EmbeddingStore
+        paths = [str(p) for p in paths]
+        e = np.asarray(as_numpy(embs), np.float32)
+        if e.ndim == 0 or e.shape[-1] != 512:
+            raise ValueError(f"expected 512-d face embeddings, got {e.shape}")
+        e = e.reshape(-1, 512)
+        if e.shape[0] != len(paths):
+            raise ValueError(f"{len(paths)} paths for {e.shape[0]} rows")
+        by_folder: Dict[str, List[int]] = {}
+        for i, p in enumerate(paths):
+            day = os.path.dirname(p)
+            by_folder.setdefault(os.path.join(os.path.dirname(os.path.dirname(day)), "faces", os.path.basename(day)), []).append(i)
+        for folder, rows in by_folder.items():
+            st = self._stores.get(folder)
+            if st is None:
+                st = self._stores[folder] = EmbeddingStore(folder, 512)
+            st.append([paths[i] for i in rows], e[rows])
+        for i, p in enumerate(paths):
+            self.face_embeddings[p] = e[i:i + 1].copy()
+        if paths:
+            self._version["face"] += 1
+
+    def index_faces(self, paths, crops) -> np.ndarray:
+        """Re-index person crops for face search: `embed_faces`, then `add_face_embeddings` for the crops that show a face.
+        Returns valid (B,) bool."""
+        paths = list(paths)
+        if len(paths) != len(crops):
+            raise ValueError(f"{len(paths)} paths for {len(crops)} crops")
+        emb, valid = self.embed_faces(crops)
+        keep = np.flatnonzero(valid).tolist()
+        if keep:
+            self.add_face_embeddings([paths[i] for i in keep], emb[keep])
+        return valid
 
     def preprocess_face(self, img):
         """:232-241 for an already decoded RGB array: a 112x112x3 image is taken as is, anything else is aligned."""

@@ -233,6 +233,33 @@ int cc_blaze_load(cc_blaze* h, const char* name, const float* data, const int64_
 int cc_blaze_finalize(cc_blaze* h);
 int cc_blaze_detect(cc_blaze* h, const void* img, int H, int W, int img_f32, int img_on_device, float* out, int out_on_device, void* stream);
 void cc_blaze_destroy(cc_blaze* h);
+/* B images of one size: imgs (B,H,W,3) -> out (B,896,17), row block b = what cc_blaze_detect returns for image b.  One plan (buffers +
+ * captured graph) per (H, W, dtype of the images, B); cc_blaze_detect is its B = 1 case. */
+int cc_blaze_detect_batch(cc_blaze* h, const void* imgs, int B, int H, int W, int img_f32, int imgs_on_device, float* out, int out_on_device, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched face path — `ObjectFinder.img_to_face` (models/objects.py:243-354) for B crops in two device passes.  The crops are packed as
+ * for cc_crop_preprocess (crop b = heights[b] x widths[b] x 3 uint8 at byte offsets[b] of `pixels`, `pixels_bytes` long; host tables).
+ *
+ * cc_face_locate: every crop letterboxed to 640 x 640 (bit-equal to cc_cv_resize_linear_u8 + a zero border), BlazeFace over the batch,
+ * and per crop the FIRST row whose ymin is not 0 - the caller's own filter in img_to_face - to first[b] (17 floats, zeros when there is
+ * none) and its row number, or -1, to first_idx[b].  Both are HOST arrays, complete on return.  -22 with a message naming the crop when
+ * a letterboxed side would be 0.
+ *
+ * cc_face_align: n faces cut, levelled and placed in one launch -> out_dev (n,112,112,3) uint8 on `device`, channels reversed like
+ * img_to_face's result.  Record i: the crop (offset, h, w), the cut rectangle inside it, the two FORWARD matrices exactly as
+ * cv2.warpAffine is given them (rot: cut -> levelled image of out_w x out_h, place: levelled -> 112 x 112).  Bit-equal to two
+ * cc_cv_warp_affine_u8 calls with the uint8 image between them, which is never written.  Synchronises `stream` before returning. */
+typedef struct cc_face_align_rec {
+  int64_t offset; int32_t h, w;
+  int32_t cx1, cy1, cw, ch;
+  int32_t out_w, out_h;
+  double rot[6], place[6];
+} cc_face_align_rec;
+int cc_face_locate(cc_blaze* h, const uint8_t* pixels, int64_t pixels_bytes, const int64_t* offsets, const int32_t* heights, const int32_t* widths,
+                   int B, int pixels_on_device, float* first, int32_t* first_idx, void* stream);
+int cc_face_align(const uint8_t* pixels, int64_t pixels_bytes, int pixels_on_device, const cc_face_align_rec* records, int n,
+                  uint8_t* out_dev, int device, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * OC-SORT tracker (host code, no GPU) — stands behind `OCSort(...)` / `OCSort.update(preds, thresh)`
