@@ -13,7 +13,7 @@ SYMBOLS = [
     "cc_yolo_create", "cc_yolo_load", "cc_yolo_calibrate", "cc_yolo_calibration_info", "cc_gptq_round_f16", "cc_yolo_finalize", "cc_yolo_detect", "cc_yolo_set_in_flight", "cc_yolo_submit", "cc_yolo_wait",
     "cc_yolo_detect_ragged", "cc_yolo_submit_ragged", "cc_letterbox_geometry", "cc_yolo_plans_built",
     "cc_yolo_get_tensor", "cc_yolo_get_tensor_frames", "cc_yolo_nonfinite",
-    "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
+    "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv2d_ex", "cc_route_log_take", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
     "cc_clip_create", "cc_clip_load", "cc_clip_finalize", "cc_clip_encode_image", "cc_clip_encode_text",
     "cc_clip_set_in_flight", "cc_clip_submit_image", "cc_clip_wait",
     "cc_clip_last_gpu_ms", "cc_clip_destroy", "cc_crop_preprocess", "cc_cv_resize_linear_u8", "cc_cv_warp_affine_u8",
@@ -30,6 +30,15 @@ SYMBOLS = [
 class ClipConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "v_width", "v_layers", "v_heads", "v_mlp",
                                        "t_ctx", "t_vocab", "t_width", "t_layers", "t_heads", "t_mlp", "embed")]
+
+
+class ConvDesc(C.Structure):
+    """cc_conv_desc: the launch cc_conv2d_ex runs (include/clearcam_hip.h)."""
+    _fields_ = [(n, C.c_int) for n in ("dtype", "B", "H", "W", "Cin", "Cout", "k", "stride", "groups", "act", "pad", "Ho", "Wo",
+                                       "out_f32", "out_cstride", "out_coff", "res_f32", "res_cstride", "res_coff", "variant")]
+
+
+ROUTE_REC_INTS = 18                                   # ints per cc_route_log_take record
 
 
 class FaceAlignRec(C.Structure):
@@ -88,6 +97,8 @@ def lib() -> C.CDLL:
         "cc_yolo_profile_graph": [vp, C.c_int, C.c_int, fp],
         "cc_conv2d_nhwc": [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                            C.c_int, vp, C.c_int, vp],
+        "cc_conv2d_ex": [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, ip, vp],
+        "cc_route_log_take": [ip, C.c_int, ip],
         "cc_conv_bench": [C.c_int] * 11 + [fp],
         "cc_dev_set": [C.c_char_p, C.c_int],
         "cc_round_weights": [C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, vp],

@@ -31,6 +31,8 @@
 //   conv_mfma_kernel     the generic one described above (every shape, every dtype)
 //   conv_big_kernel      256x256 or 128x128 tile / 4 waves / one barrier per K step, for deep GEMM-shaped 16-bit layers
 //   conv3x3_ws_kernel    3x3 s1 for narrow layers: persistent blocks, all nine taps of the weights resident in LDS
+#include <algorithm>
+#include <vector>
 #include "conv_select.h"
 #include "conv_tile.h"
 
@@ -815,8 +817,35 @@ template <class T> static void launch_t(const ConvP& p, const ConvAux& a, const 
   if (c.simple) launch_generic<T, true>(p, a, c, stream); else launch_generic<T, false>(p, a, c, stream);
 }
 
-void launch_conv_mfma(int dt, const ConvP& p, hipStream_t stream) {
+// ---- route log -----------------------------------------------------------------------------------------------------------------
+std::atomic<int> g_route_log{0};
+static std::mutex g_route_mutex;
+static std::vector<int> g_route_recs;
+
+void route_log_append(const ConvP& p, const ConvChoice& c) {
+  const int sym_ho = (p.Hin + 2 * p.pad - p.ks) / p.stride + 1, sym_wo = (p.Win + 2 * p.pad - p.ks) / p.stride + 1;
+  const int rec[ROUTE_REC_INTS] = {(int)c.kernel, c.sched, c.bm, c.bn, p.ks, p.stride, (p.Ho > sym_ho || p.Wo > sym_wo) ? 1 : 0, p.act,
+                                   p.res ? (p.res_f32 ? 2 : 1) : 0, p.out_f32 ? 1 : 0,
+                                   (p.Cout % 8 == 0 && p.out_coff % 8 == 0 && p.out_cstride % 8 == 0) ? 1 : 0,
+                                   p.B, p.Hin, p.Win, p.Cin, p.Cout, p.Ho, p.Wo};
+  std::lock_guard<std::mutex> lock(g_route_mutex);
+  g_route_recs.insert(g_route_recs.end(), rec, rec + ROUTE_REC_INTS);
+}
+
+int route_log_take(int* recs, int cap) {
+  std::lock_guard<std::mutex> lock(g_route_mutex);
+  const int n = (int)(g_route_recs.size() / ROUTE_REC_INTS), take = std::min(n, std::max(cap, 0));
+  if (recs && take > 0) std::copy(g_route_recs.begin(), g_route_recs.begin() + (size_t)take * ROUTE_REC_INTS, recs);
+  g_route_recs.erase(g_route_recs.begin(), g_route_recs.begin() + (size_t)take * ROUTE_REC_INTS);   // what did not fit stays for the next call
+  return n;
+}
+
+void launch_conv_mfma(int dt, const ConvP& p, hipStream_t stream) { launch_conv_chosen(dt, p, stream, nullptr); }
+
+void launch_conv_chosen(int dt, const ConvP& p, hipStream_t stream, ConvChoice* chosen) {
   const ConvChoice c = choose_conv(dt, p);
+  if (chosen) *chosen = c;
+  if (g_route_log.load(std::memory_order_relaxed)) route_log_append(p, c);
   ConvAux a{};
   a.nt = (p.Cout + c.bn - 1) / c.bn;
   a.inv_hw = 1.0f / (float)(p.Ho * p.Wo); a.inv_wo = 1.0f / (float)p.Wo;

@@ -52,6 +52,19 @@ ConvChoice choose_conv(int dt, const ConvP& p);
 // 256-pixel tiles and the better of 16 x 16 / 8 x 32 tiles within 1.25x of the map.  yolo.hip's RepNCSP fusion (Builder::fuse_csp) asks the same question.
 bool conv_tile64_takes(int B, int H, int W);
 
+// launch_conv_mfma, handing back the choice it launched with (`chosen` may be null): the same choose_conv call serves both.
+void launch_conv_chosen(int dt, const ConvP& p, hipStream_t stream, ConvChoice* chosen);
+
+// Route log (development, tests): with cc_dev_set("route_log", 1) every launch through launch_conv_chosen appends one record to a
+// process-wide, mutex-guarded list; cc_route_log_take reads and clears it.  Off by default: one relaxed load per launch.
+// A record is ROUTE_REC_INTS ints: kernel, sched, bm, bn, ks, stride, asym (Ho / Wo exceed the symmetric formula), act, residual kind
+// (0 none, 1 storage type, 2 f32), out_f32, aligned8 (Cout, out_coff, out_cstride all multiples of 8), then the layer's shape
+// B, Hin, Win, Cin, Cout, Ho, Wo.
+constexpr int ROUTE_REC_INTS = 18;
+extern std::atomic<int> g_route_log;
+void route_log_append(const ConvP& p, const ConvChoice& c);
+int route_log_take(int* recs, int cap);                // moves up to `cap` records out (the rest stay), returns how many the list held
+
 // CLEARCAM_* selection switches, read from the environment once per process (thread-safe static initialisation)
 struct ConvSwitches {
   int stream, stream_min_pix, stream_flags;   // CLEARCAM_STREAM (1), CLEARCAM_STREAM_MIN_PIX (200000), CLEARCAM_STREAM_FLAGS (10)

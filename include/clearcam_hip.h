@@ -142,6 +142,30 @@ void cc_yolo_destroy(cc_yolo* h);
 int cc_conv2d_nhwc(int dtype, const void* x_dev, int B, int H, int W, int Cin, const float* w_oihw,
                    const float* bias, int Cout, int k, int stride, int groups, int act, void* out_dev,
                    int force_direct, void* stream);
+/* Single-layer entry of the epilogue tests: ONE launch of any conv the CLIP, AdaFace and BlazeFace plans describe.
+ * dtype 0 / 1 / 2 (f32 / f16 / bf16 storage); x (B,H,W,Cin) in the storage type; w OIHW float32 host (Cout, Cin/groups, k, k), packed
+ * as the face nets pack theirs (groups densified, converted to the storage type: values already representable there are kept as they
+ * are); bias, slope: host float32[Cout] or null (slope is required for act 3).
+ * act: 0 none, 1 SiLU, 2 tanh-GELU, 3 PReLU (before the residual), 4 ReLU (after the residual).
+ * pad < 0: k/2.  Ho / Wo <= 0: (H + 2 pad - k) / stride + 1; larger values add zero rows / columns at the bottom / right.
+ * out: pixels of out_cstride channels (<= 0: Cout), the result in channels [out_coff, out_coff + Cout), float32 if out_f32 else the
+ * storage type.  res (null: none): the same pixel grid, res_cstride (<= 0: Cout) / res_coff, float32 if res_f32; it may be `out` itself.
+ * variant: as cc_conv2d_nhwc's force_direct.  choice (int[4] or null) receives the kernel that ran: ConvKernel, phase schedule, tile
+ * pixels, tile channels (csrc/conv_select.h).  Synchronises the stream. */
+typedef struct {
+  int dtype, B, H, W, Cin, Cout, k, stride, groups, act;
+  int pad, Ho, Wo;
+  int out_f32, out_cstride, out_coff;
+  int res_f32, res_cstride, res_coff;
+  int variant;
+} cc_conv_desc;
+int cc_conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
+                 const void* res_dev, void* out_dev, int* choice, void* stream);
+/* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 18 ints each into `records` and sets *n to the number of records
+ * the log held; records that did not fit (*n > cap) stay in the log for the next call.  A record: kernel, schedule, tile pixels, tile channels, k, stride, Ho / Wo beyond the symmetric formula,
+ * act, residual (0 none / 1 storage type / 2 float32), out_f32, Cout / out_coff / out_cstride all multiples of 8, then B, H, W, Cin,
+ * Cout, Ho, Wo of the layer. */
+int cc_route_log_take(int* records, int cap, int* n);
 /* Diagnostic (kernel tuning, tools/dev/stream_ab.py, variant_sweep.py): average device milliseconds of one launch of the conv above on random
  * 16-bit data resident in HBM, weights packed once, `iters` launches between two events.  Not part of the drop-in surface. */
 int cc_conv_bench(int dtype, int B, int H, int W, int Cin, int Cout, int k, int stride, int act, int variant, int iters, float* ms);
@@ -161,6 +185,7 @@ int cc_round_weights(int dtype, const float* w, int64_t cout, int64_t cin, int64
  * keys "stream_abl", "tile64_abl": timing ablations of development builds (no effect otherwise);
  * key "index_slab_rows": rows per bounced slab of cc_index_remove_* (-1 = the measured default), so that a test can force many
  *     slabs on a small index; rounded up to a multiple of 64.
+ * key "route_log": 1 = every conv / GEMM launch appends one record to a process-wide list (cc_route_log_take), 0 = off (default).
  * Plans already built keep the launches they were built with.  Not part of the drop-in surface. */
 int cc_dev_set(const char* key, int value);
 

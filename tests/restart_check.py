@@ -116,6 +116,56 @@ def conv64(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], stride: 
     return y
 
 
+GELU_C0, GELU_C1 = 0.7978845608028654, 0.044715     # clearcam_amd/csrc/conv_tile.h activate<T, 2>: 0.5 x (1 + tanh(C0 (x + C1 x^3)))
+
+
+def pads_for(H: int, W: int, k: int, stride: int, pad: int, Ho: int, Wo: int):
+    """(top, bottom, left, right) zero padding that a ConvP with `pad` and an explicit Ho x Wo reads (conv_params, net_common.h): `pad`
+    rows / columns before the input, whatever the last window needs behind it (negative: trailing rows no window reaches)."""
+    return pad, (Ho - 1) * stride + k - pad - H, pad, (Wo - 1) * stride + k - pad - W
+
+
+def _conv_padded(x, w, stride, groups, pad4):
+    t, b, l, r = pad4
+    return F.conv2d(F.pad(x, (l, r, t, b)), w, None, stride=stride, padding=0, groups=groups)
+
+
+def conv64_ex(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], stride: int = 1, groups: int = 1, act: int = 0,
+              slope: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, pad4=None) -> torch.Tensor:
+    """conv64 with every epilogue of ConvP (common.h), in the kernels' order, all in float64 and NOT rounded: explicit zero padding per
+    side (pad4 = (top, bottom, left, right); None = k // 2 all round), groups, bias, then act 1 SiLU / 2 tanh-GELU / 3 PReLU with
+    slope[channel], then the residual (NCHW, same grid as the output), then act 4's ReLU."""
+    k = w.shape[-1]
+    pad4 = (k // 2,) * 4 if pad4 is None else pad4
+    y = _conv_padded(x.to(torch.float64), w.to(torch.float64), stride, groups, pad4)
+    if b is not None:
+        y = y + b.to(torch.float64).view(1, -1, 1, 1)
+    if act == 1:
+        y = y * torch.sigmoid(y)
+    elif act == 2:
+        y = 0.5 * y * (1.0 + torch.tanh(GELU_C0 * (y + GELU_C1 * y * y * y)))
+    elif act == 3:
+        y = torch.where(y > 0, y, slope.to(torch.float64).view(1, -1, 1, 1) * y)
+    if res is not None:
+        y = y + res.to(torch.float64)
+    if act == 4:
+        y = torch.clamp(y, min=0.0)
+    return y
+
+
+def conv_abs64(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], stride: int = 1, groups: int = 1,
+               res: Optional[torch.Tensor] = None, pad4=None) -> torch.Tensor:
+    """A = sum |x| |w| + |bias| + |res| per output element in float64: the magnitude an f32 evaluation's rounding errors scale with."""
+    k = w.shape[-1]
+    pad4 = (k // 2,) * 4 if pad4 is None else pad4
+    a = _conv_padded(x.to(torch.float64).abs(), w.to(torch.float64).abs(), stride, groups, pad4)
+    if b is not None:
+        a = a + b.to(torch.float64).abs().view(1, -1, 1, 1)
+    if res is not None:
+        a = a + res.to(torch.float64).abs()
+    return a
+
+
 # -- the comparison -----------------------------------------------------------------------------------------------------------
 def _cell_rates(flip: torch.Tensor):
     """(N, C, H, W) bool -> (flips, elements) per (frame, 32-channel, 16x16-pixel) cell."""
@@ -160,14 +210,23 @@ def check(gpu: torch.Tensor, y64: torch.Tensor, sdt: str, name: str = "", R: flo
         "nonfinite": int((~finite).sum()),
     }
     if enforce:
-        if ulps is None:
-            assert st["not_faithful"] == 0, (name, "elements neither of the two storage values that bracket y64 (nor within FLOOR)", st)
-        else:
-            assert st["nonfinite"] == 0 and st["max_ulp"] <= ulps, (name, f"elements further than {ulps} ulps from y64", st)
-        assert st["differ"] <= R, (name, f"share differing from round(y64) above {R}", st)
-        assert st["cell_excess"] <= 0, (name, f"a 16x16x32 cell differs on more than {R_cell} of its elements", st)
-        assert st["p99_boundary"] <= D, (name, f"flips away from the rounding midpoints (p99 above {D} ulp)", st)
+        assert_bars(st, name, R, R_cell, D, ulps)
     return st
+
+
+def assert_bars(st: Dict[str, float], name: str = "", R: float = None, R_cell: float = None, D: float = None,
+                ulps: Optional[float] = None) -> None:
+    """The assertions of `check` on statistics it returned (with the same R_cell: cell_excess is relative to it)."""
+    R = BARS["R"] if R is None else R
+    R_cell = BARS["R_cell"] if R_cell is None else R_cell
+    D = BARS["D"] if D is None else D
+    if ulps is None:
+        assert st["not_faithful"] == 0, (name, "elements neither of the two storage values that bracket y64 (nor within FLOOR)", st)
+    else:
+        assert st["nonfinite"] == 0 and st["max_ulp"] <= ulps, (name, f"elements further than {ulps} ulps from y64", st)
+    assert st["differ"] <= R, (name, f"share differing from round(y64) above {R}", st)
+    assert st["cell_excess"] <= 0, (name, f"a 16x16x32 cell differs on more than {R_cell} of its elements", st)
+    assert st["p99_boundary"] <= D, (name, f"flips away from the rounding midpoints (p99 above {D} ulp)", st)
 
 
 def fmt(name: str, st: Dict[str, float]) -> str:

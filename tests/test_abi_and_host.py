@@ -184,3 +184,16 @@ def test_calibration_aware_rounding_generalises_to_held_out_pixels(lib_path):
     gains = {k: err(near, xs) / err(q, xs) for k, xs in (("calibration", cal), ("held-out pixels", held), ("another frame", other))}
     print(gains)
     assert gains["calibration"] > 3.0 and gains["held-out pixels"] > 0.8 * gains["calibration"] and gains["another frame"] > 0.6 * gains["calibration"], gains
+
+
+def test_route_record_width_matches_the_library_source():
+    """The route-log record is 18 ints in three places: the C++ constant, the header's comment and the Python binding."""
+    src = open(os.path.join(ROOT, "clearcam_amd", "csrc", "conv_select.h")).read()
+    width = int(re.search(r"constexpr int ROUTE_REC_INTS = (\d+);", src).group(1))
+    hdr = open(os.path.join(ROOT, "include", "clearcam_hip.h")).read()
+    assert _lib.ROUTE_REC_INTS == width
+    assert f"records of {width} ints each" in hdr
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import epilogue_cases as ec
+    assert len(ec.KEY_FIELDS) + 7 == width               # the key, then B, H, W, Cin, Cout, Ho, Wo
