@@ -361,6 +361,29 @@ int cc_face_locate(cc_blaze* h, const uint8_t* pixels, int64_t pixels_bytes, con
   CC_API_END
 }
 
+// Development entry: ONE launch of blaze_post_kernel, as run_ops launches it, on head outputs the caller crafts (no handle, no plan).
+int cc_dev_blaze_post(const float* r8_dev, const float* r16_dev, const float* c8_dev, const float* c16_dev, int B, const float* anchors,
+                      float scale, int pad_top, int pad_left, float* out_dev, float* first_dev, int32_t* first_idx_dev, void* stream) {
+  std::vector<void*> owner;
+  auto release = [&]() { for (void* q : owner) hipFree(q); owner.clear(); };
+  try {
+    CC_CHECK(r8_dev && r16_dev && c8_dev && c16_dev && anchors && out_dev && first_dev && first_idx_dev, "null argument");
+    CC_CHECK(B > 0 && B <= 65535, "bad batch size");
+    CC_CHECK(scale > 0.0f && std::isfinite(scale) && pad_top >= 0 && pad_top < kIn && pad_left >= 0 && pad_left < kIn, "bad back-map (scale, pad_top, pad_left)");
+    float* anc = upload_f32(owner, std::vector<float>(anchors, anchors + (size_t)kAnchors * 4));
+    float* rows = nullptr;
+    CC_HIP(hipMalloc((void**)&rows, (size_t)B * kAnchors * 17 * 4 + 256));
+    owner.push_back(rows);
+    const PostP post{r8_dev, r16_dev, c8_dev, c16_dev, anc, scale, pad_top, pad_left, rows, out_dev, first_dev, (int*)first_idx_dev};
+    hipLaunchKernelGGL(blaze_post_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, post);
+    CC_HIP(hipGetLastError());
+    CC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    release();
+    return 0;
+  } catch (const cc::Error& e) { release(); cc::set_error(e.what()); return e.code; }
+  catch (const std::exception& e) { release(); cc::set_error(e.what()); return -1; }
+}
+
 void cc_blaze_destroy(cc_blaze* h) {
   if (!h) return;
   hipSetDevice(h->device);

@@ -161,6 +161,29 @@ typedef struct {
 } cc_conv_desc;
 int cc_conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
                  const void* res_dev, void* out_dev, int* choice, void* stream);
+/* Single-launch entries of the post-processing tests: ONE launch of a detector / face post-processing kernel through its production
+ * launcher, on inputs the caller crafts.  Device pointers end in _dev; everything else is host memory.  Each validates its arguments
+ * (an error, and no launch, on null pointers, B <= 0, an empty level, an unsupported dtype / ch, or a misaligned map), synchronises
+ * `stream` and frees what it allocated.  H, W: int[3], the three levels' map sizes (strides 8, 16, 32), A = sum H*W.
+ *
+ * cc_dev_decode: decode_kernel.  raw_dev[3]: float32 (B,H_l,W_l,144) maps, 16-byte aligned; dfl_w16: the 16 DFL weights; det_dev
+ * (B,A,6) rows [x1,y1,x2,y2,score (0 below conf),class]; *nonfinite: anchors whose logits were not finite.
+ * cc_dev_head_tail: head_tail_kernel.  dtype 1 / 2 / 3 (f16 / bf16 / f16s), ch 128 or 256; per level bx_dev (B,H,W,64) and cl_dev
+ * (B,H,W,ch) in the storage type, 16-byte aligned, and the OIHW float32 weights of cv2[l][2] (64,16,1,1: four groups) and cv3[l][2]
+ * (80,ch,1,1) with their biases, packed as the detector packs them (groups densified, controlled rounding, two planes for f16s).
+ * cc_dev_topk_nms: topk_nms_kernel over rows_dev (B,A,6) -> out_dev (B,300,6).  geometry = (pad_x, pad_y, gain, src_w, src_h) of
+ * scale_boxes: 5 floats (ragged = 0), or B x 5 (ragged = 1: the ragged launcher, frame records with only these fields filled).
+ * cc_dev_blaze_post: blaze_post_kernel over float32 head outputs r8 (B,16,16,32), r16 (B,8,8,96), c8 (B,16,16,2), c16 (B,8,8,6) and
+ * host anchors (896,4) -> out_dev (B,896,17), first_dev (B,17), first_idx_dev (B) as cc_blaze_detect_batch / cc_face_locate produce
+ * them. */
+int cc_dev_decode(const float* const* raw_dev, const int* H, const int* W, int B, const float* dfl_w16, float conf, float* det_dev,
+                  int* nonfinite, void* stream);
+int cc_dev_head_tail(int dtype, int ch, const void* const* bx_dev, const void* const* cl_dev, const float* const* w2, const float* const* b2,
+                     const float* const* w3, const float* const* b3, const int* H, const int* W, int B, const float* dfl_w16, float conf,
+                     float* det_dev, int* nonfinite, void* stream);
+int cc_dev_topk_nms(const float* rows_dev, int B, int A, float iou_thr, const float* geometry, int ragged, float* out_dev, void* stream);
+int cc_dev_blaze_post(const float* r8_dev, const float* r16_dev, const float* c8_dev, const float* c16_dev, int B, const float* anchors,
+                      float scale, int pad_top, int pad_left, float* out_dev, float* first_dev, int32_t* first_idx_dev, void* stream);
 /* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 18 ints each into `records` and sets *n to the number of records
  * the log held; records that did not fit (*n > cap) stay in the log for the next call.  A record: kernel, schedule, tile pixels, tile channels, k, stride, Ho / Wo beyond the symmetric formula,
  * act, residual (0 none / 1 storage type / 2 float32), out_f32, Cout / out_coff / out_cstride all multiples of 8, then B, H, W, Cin,

@@ -119,7 +119,12 @@ class BlazeFaceOracle:
         """(H,W,3) uint8/float image -> (896,17) float32 [ymin,xmin,ymax,xmax, 6 x (kx,ky), score] in source pixels."""
         x, scale, pad_top, pad_left = self.network_input(img)
         r, c = self.forward(x)
-        det = self.postprocess(self.decode(r[0], c[0, :, 0])) * 256
+        return self.back_map(self.postprocess(self.decode(r[0], c[0, :, 0])), scale, pad_top, pad_left).numpy()
+
+    @staticmethod
+    def back_map(det: torch.Tensor, scale: float, pad_top: int, pad_left: int) -> torch.Tensor:
+        """Network coordinates -> source pixels (models/blazeface.py:188-192): every column * 256, the box minus the padding, / scale."""
+        det = det * 256
         det[:, [0, 2]] -= pad_top
         det[:, [1, 3]] -= pad_left
-        return (det / scale).numpy()
+        return det / scale

@@ -287,9 +287,16 @@ class YOLOv9Oracle:
         cls = scores.argmax(1)
         probs = scores.max(1).values
         probs = torch.where(probs >= conf, probs, torch.zeros_like(probs))
-        boxes = torch.stack((x1, y1, x2, y2, probs, cls.float()), 2)
+        return YOLOv9Oracle.postprocess_rows(torch.stack((x1, y1, x2, y2, probs, cls.float()), 2), max_det, iou_thr)
+
+    @staticmethod
+    def postprocess_rows(rows: torch.Tensor, max_det=MAX_DET, iou_thr=IOU_THRESHOLD) -> torch.Tensor:
+        """The discrete half of ``postprocess`` (:449-458) on its (B,A,6) rows [x1,y1,x2,y2,score (0 below conf),class]: stable
+        top-``max_det`` by score, then the mask NMS.  -> (B,max_det,6); with A < max_det the missing rows are zero rows, which
+        ``scale_boxes`` then treats like every other zeroed row."""
+        probs = rows[..., 4]
         order = torch.sort(probs, dim=1, descending=True, stable=True).indices[:, :max_det]
-        boxes = torch.gather(boxes, 1, order.unsqueeze(-1).expand(-1, -1, 6))
+        boxes = torch.gather(rows, 1, order.unsqueeze(-1).expand(-1, -1, 6))
         bx1, by1, bx2, by2 = boxes[..., 0], boxes[..., 1], boxes[..., 2], boxes[..., 3]
         areas = (bx2 - bx1) * (by2 - by1)
         ix1 = torch.maximum(bx1[:, :, None], bx1[:, None, :])
@@ -301,7 +308,10 @@ class YOLOv9Oracle:
         ious = torch.triu(ious, diagonal=1)
         same = boxes[..., 5][:, :, None] == boxes[..., 5][:, None, :]
         keep = ((ious > iou_thr) & same).sum(1) == 0
-        return boxes * keep.unsqueeze(-1)
+        out = boxes * keep.unsqueeze(-1)
+        if out.shape[1] < max_det:
+            out = torch.cat((out, out.new_zeros(out.shape[0], max_det - out.shape[1], 6)), 1)
+        return out
 
     @staticmethod
     def scale_boxes(lb_hw: Tuple[int, int], preds: torch.Tensor, src_hw: Tuple[int, int]) -> torch.Tensor:

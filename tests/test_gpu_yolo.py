@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from clearcam_amd import _lib
 from conftest import noise_frames
+from postprocess_cases import split_value
 from oracle import yolov9_oracle as yo
 
 pytestmark = pytest.mark.gpu
@@ -155,16 +156,6 @@ def test_small_pixel_tiles_match_generic(case, dtype, variant):
     got = conv_hip(x, w, b, stride, 1, 1, dtype, force_direct=variant)
     assert float((got - ref).abs().max() / ref.abs().max()) <= TOL[dtype]
     assert torch.equal(got, conv_hip(x, w, b, stride, 1, 1, dtype, force_direct=2))
-
-
-def split_value(w: torch.Tensor) -> torch.Tensor:
-    """The value the two f16 planes of the "f16s" mode hold for a weight tensor (yolo.hip pack_convs): w 2^e = hi + lo with 2^e
-    putting the largest magnitude in [2^14, 2^15)."""
-    e = 14 - int(np.floor(np.log2(float(w.abs().max()))))
-    ws = w * (2.0 ** e)
-    hi = ws.to(torch.float16).float()
-    lo = (ws - hi).to(torch.float16).float()
-    return (hi + lo) * (2.0 ** -e)
 
 
 # (name, B, Cin, H, W, Cout, k, stride, groups, variant): every kernel family the split-weight mode selects from
