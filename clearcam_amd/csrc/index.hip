@@ -49,6 +49,7 @@ struct cc_index {
   unsigned* gcnt = nullptr; size_t gcnt_cap = 0;               // survivors per granule of kGran rows
   unsigned long long* goff = nullptr; size_t goff_cap = 0;     // survivors before each granule, and the total behind the last one
   char* bounce = nullptr; size_t bounce_cap = 0;               // one slab of survivors: rows, then their groups, then their slots
+  char* rank_ws = nullptr; size_t rank_ws_cap = 0;             // cc_index_rank: per query and select the state, a 256-bin table and a window counter; per query the total
 };
 
 namespace {
@@ -391,6 +392,186 @@ __global__ __launch_bounds__(1024) void topk_stage2(const unsigned long long* __
       idx[(size_t)q * K + tid] = (int)row; score[(size_t)q * K + tid] = unordered((unsigned)(k >> 32));
     }
   }
+}
+
+// ---- ranking: any window of the whole descending order (cc_index_rank) ---------------------------------------------------------
+// The answers' keys are those of topk_stage1 / topk_stage2: ordered(score) << 32 | ~position, position = the row (a track: its
+// first allowed row; without CC_RANK_TRACKS every allowed row is its own answer) or n + row for a slot-less row of a track search,
+// 0 = padding, so keys are distinct and their descending order is the reference's dict order + stable sort.  Only the high words
+// are stored (key_hi, as in the track search); the low word follows from the row number and its slot.
+// A window of at most kMaxK answers is cut out by two boundary keys, the keys of rank `start` and of rank `end`: everything below
+// the first and at or above the second.  A boundary is found by an MSB-first radix select over ALL keys, the multi-block form of
+// block_topk: per key byte one launch in which every block counts its rows in an LDS histogram and adds the non-empty bins to a
+// 256-bin table in global memory (integer atomics: the sums do not depend on the arrival order), and a one-wave launch that picks
+// the digit.  Up to kRankSel boundaries - 16 consecutive windows - go through the same launches side by side (blockIdx.y).
+// No block ever waits for another block: there is no flag to spin on, no ticket and no look-back anywhere in these kernels.
+constexpr int kRankSel = 17;      // boundaries per batch of launches
+constexpr int kRankRows = 4096;   // rows per block of the multi-block passes
+
+struct RankSel { unsigned long long prefix; unsigned k, done; };   // a select: the key bytes fixed so far, the rank left inside them, finished
+
+__device__ __forceinline__ unsigned long long rank_key(unsigned hi, long r, long n, const int* __restrict__ trk) {
+  return ((unsigned long long)hi << 32) | (unsigned)(~(unsigned)((trk && trk[r] < 0 ? n : 0) + r));
+}
+
+// hi[q][row] = the high word of the row's key (0: filtered out, not the first row of its track, or below the cut), and
+// total[q] += the number of keys.  TRACKS: behind track_reduce_kernel, like the first loop of topk_stage1<true>.
+template <bool TRACKS>
+__global__ __launch_bounds__(256) void rank_keys_kernel(const float* __restrict__ scores, long n, const int* __restrict__ grp,
+                                                        const unsigned char* __restrict__ allowed, int n_allowed, const int* __restrict__ trk,
+                                                        const unsigned long long* __restrict__ best, const unsigned* __restrict__ first, int T,
+                                                        float min_score, unsigned* __restrict__ hi, unsigned* __restrict__ total) {
+  __shared__ unsigned s_cnt[4];
+  const int q = blockIdx.y, tid = threadIdx.x;
+  const long base = (long)blockIdx.x * kRankRows, end = min(n, base + kRankRows);
+  const float* s = scores + (long)q * n;
+  unsigned* h = hi + (long)q * n;
+  unsigned cnt = 0;
+  for (long r = base + tid; r < end; r += 256) {
+    unsigned u = 0;
+    if (row_allowed(grp, allowed, n_allowed, r)) {
+      if (TRACKS) {
+        const int t = trk[r];
+        if (t < 0) u = ordered(s[r]);
+        else if (t < T && first[t] == (unsigned)r) u = (unsigned)(best[(size_t)q * T + t] >> 32);
+      } else u = ordered(s[r]);
+      if (u != 0u && unordered(u) < min_score) u = 0u;             // the cut: score >= min_score stays (-inf: everything)
+    }
+    h[r] = u;
+    cnt += u != 0u;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid == 0) { const unsigned c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]; if (c) atomicAdd(&total[q], c); }
+}
+
+// The selects of one batch: boundary j is the key of rank min(r0 + j * kMaxK, r_last) (rank 0: nothing to find, the window is
+// open at the top).  Clears the batch's bin tables and window counters.  One block per query.
+__global__ __launch_bounds__(256) void rank_init_kernel(long r0, long r_last, RankSel* __restrict__ sel, unsigned* __restrict__ ghist, unsigned* __restrict__ wcnt) {
+  const int q = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < kRankSel * 256; i += 256) ghist[(size_t)q * kRankSel * 256 + i] = 0u;
+  if (tid < kRankSel) {
+    const long r = min(r0 + (long)tid * kMaxK, r_last);
+    RankSel st; st.prefix = 0ull; st.k = (unsigned)r; st.done = r == 0;
+    sel[q * kRankSel + tid] = st;
+    wcnt[q * kRankSel + tid] = 0u;
+  }
+}
+
+// One byte of select (blockIdx.y) of query (blockIdx.z): the digits of the keys that agree with the prefix above that byte.
+__global__ __launch_bounds__(256) void rank_hist_kernel(const unsigned* __restrict__ hi, long n, const int* __restrict__ trk, int byte,
+                                                        const RankSel* __restrict__ sel, unsigned* __restrict__ ghist) {
+  __shared__ unsigned hist[256];
+  const int j = blockIdx.y, q = blockIdx.z, tid = threadIdx.x;
+  const RankSel st = sel[q * kRankSel + j];
+  if (st.done) return;                                             // the same for every thread of every block of this select
+  hist[tid] = 0u;
+  __syncthreads();
+  const long base = (long)blockIdx.x * kRankRows, end = min(n, base + kRankRows);
+  const unsigned* h = hi + (long)q * n;
+  const int sh = 8 * (byte + 1);
+  for (long r = base + tid; r < end; r += 256) {
+    const unsigned u = h[r];
+    if (u == 0u) continue;
+    const unsigned long long k = byte >= 4 ? (unsigned long long)u << 32 : rank_key(u, r, n, trk);   // the score bytes need no slot
+    if (byte == 7 || (k >> sh) == (st.prefix >> sh)) atomicAdd(&hist[(unsigned)(k >> (8 * byte)) & 255u], 1u);
+  }
+  __syncthreads();
+  const unsigned c = hist[tid];
+  if (c) atomicAdd(&ghist[((size_t)q * kRankSel + j) * 256 + tid], c);
+}
+
+// One wave per select: walk the 256 bins from the top as block_topk does, fix the digit that holds the wanted rank, clear the bins.
+// A select is finished when the whole bucket is wanted (every key at or above the prefix, lower bytes zero, then has a rank of at
+// most the wanted one, and nothing else has: the prefix is as good a boundary as the key itself) or when fewer keys exist than
+// the rank asks for (the prefix stays 0: every key lies at or above the boundary).
+__global__ __launch_bounds__(64) void rank_pick_kernel(int byte, RankSel* __restrict__ sel, unsigned* __restrict__ ghist) {
+  const int j = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+  RankSel* st = sel + q * kRankSel + j;
+  if (st->done) return;
+  const unsigned kk = st->k;
+  const unsigned long long prefix = st->prefix;
+  unsigned* g = ghist + ((size_t)q * kRankSel + j) * 256 + 4 * tid;
+  const unsigned hh[4] = {g[0], g[1], g[2], g[3]};
+  g[0] = g[1] = g[2] = g[3] = 0u;
+  const unsigned s = hh[0] + hh[1] + hh[2] + hh[3];
+  unsigned suf = s;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const unsigned t = __shfl_down(suf, off, 64); if (tid + off < 64) suf += t; }
+  const unsigned all = __shfl(suf, 0, 64), above = suf - s;
+  if (all < kk) { if (tid == 0) st->done = 1u; return; }
+  if (above < kk && kk <= suf) {
+    unsigned cum = above; int v = 0;
+    for (int qd = 3; qd >= 0; --qd) { if (cum + hh[qd] >= kk) { v = qd; break; } cum += hh[qd]; }
+    st->prefix = prefix | ((unsigned long long)(4 * tid + v) << (8 * byte));
+    st->k = kk - cum;
+    if (hh[v] == kk - cum) st->done = 1u;
+  }
+}
+
+// Every key below boundary 0 (open_top: no upper end) and at or above boundary S - 1 goes to the buffer of its window w, the one
+// with boundary w > key >= boundary w + 1.  The place inside the buffer comes from an integer counter; the emit kernel sorts, so the
+// result does not depend on it.  A window holds at most kMaxK keys by construction; the bound check only guards the buffer.
+__global__ __launch_bounds__(256) void rank_collect_kernel(const unsigned* __restrict__ hi, long n, const int* __restrict__ trk, int S, int open_top,
+                                                           const RankSel* __restrict__ sel, unsigned* __restrict__ wcnt, unsigned long long* __restrict__ wbuf) {
+  __shared__ unsigned long long thr[kRankSel];
+  const int q = blockIdx.y, tid = threadIdx.x;
+  if (tid < S) thr[tid] = sel[q * kRankSel + tid].prefix;
+  __syncthreads();
+  const unsigned long long lo = thr[S - 1], top = thr[0];
+  const long base = (long)blockIdx.x * kRankRows, end = min(n, base + kRankRows);
+  const unsigned* h = hi + (long)q * n;
+  for (long r = base + tid; r < end; r += 256) {
+    const unsigned u = h[r];
+    if (u == 0u) continue;
+    const unsigned long long k = rank_key(u, r, n, trk);
+    if (k < lo || (!open_top && k >= top)) continue;
+    int w = 0;
+    while (w < S - 2 && k < thr[w + 1]) ++w;
+    const unsigned pos = atomicAdd(&wcnt[q * kRankSel + w], 1u);
+    if (pos < (unsigned)kMaxK) wbuf[((size_t)q * kRankSel + w) * kMaxK + pos] = k;
+  }
+}
+
+// One block per window: sort its keys descending with the bitonic network of topk_stage2 and emit (row, score) as it does, at
+// answers out0 + window * kMaxK ... of the (Q, count) result; what lies past the last key is padding.
+template <bool TRACKS>
+__global__ __launch_bounds__(1024) void rank_emit_kernel(const unsigned long long* __restrict__ wbuf, const unsigned* __restrict__ wcnt, long out0, long count,
+                                                         int* __restrict__ idx, float* __restrict__ score, long n, const int* __restrict__ trk,
+                                                         const unsigned long long* __restrict__ best, int T) {
+  __shared__ unsigned long long sel[kMaxK];
+  const int w = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+  const int c = (int)min(wcnt[q * kRankSel + w], (unsigned)kMaxK);
+  sel[tid] = tid < c ? wbuf[((size_t)q * kRankSel + w) * kMaxK + tid] : 0ull;
+  __syncthreads();
+  int P = 2;
+  while (P < c) P <<= 1;
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int ixj = tid ^ j;
+      if (ixj > tid && ixj < P) {
+        const unsigned long long x = sel[tid], y = sel[ixj];
+        const bool desc = (tid & k) == 0;
+        if (desc ? (x < y) : (x > y)) { sel[tid] = y; sel[ixj] = x; }
+      }
+      __syncthreads();
+    }
+  const long o = out0 + (long)w * kMaxK + tid;
+  if (o >= count) return;
+  const unsigned long long k = sel[tid];
+  int row = -1; float sc = -INFINITY;
+  if (k != 0ull) {
+    unsigned r = ~(unsigned)(k & 0xffffffffull);
+    if (TRACKS) r = r >= (unsigned)n ? r - (unsigned)n : ~(unsigned)(best[(size_t)q * T + trk[r]] & 0xffffffffull);
+    row = (int)r; sc = unordered((unsigned)(k >> 32));
+  }
+  idx[(size_t)q * count + o] = row; score[(size_t)q * count + o] = sc;
+}
+
+__global__ void rank_pad_kernel(int* __restrict__ idx, float* __restrict__ score, size_t cnt) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) { idx[i] = -1; score[i] = -INFINITY; }
 }
 
 // ---- removal: stable compaction in place -------------------------------------------------------------------------------------
@@ -870,6 +1051,113 @@ int search(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, in
   CC_API_END
 }
 
+// The per-group filter of a call on the device (h->allowed, zero beyond n_groups), or null without one.
+const unsigned char* upload_allowed(cc_index* h, const uint8_t* allowed, int n_groups, hipStream_t s) {
+  if (!allowed) return nullptr;
+  if (h->allowed_cap < n_groups) {
+    if (h->allowed) hipFree(h->allowed);
+    h->allowed = nullptr; h->allowed_cap = 0;
+    int cap = 1024; while (cap < n_groups) cap *= 2;
+    CC_HIP(hipMalloc((void**)&h->allowed, (size_t)cap)); h->allowed_cap = cap;
+  }
+  CC_HIP(hipMemsetAsync(h->allowed, 0, (size_t)h->allowed_cap, s));
+  CC_HIP(hipMemcpyAsync(h->allowed, allowed, (size_t)n_groups, hipMemcpyHostToDevice, s));
+  return h->allowed;
+}
+
+// cc_index_rank.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
+// init, eight times (histogram, pick), collect, emit.  Answers past the last row the index could give are padded by one fill.
+int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
+         int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && q && idx && score, "null argument");
+  CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
+  CC_CHECK(start >= 0, "start must not be negative");
+  CC_CHECK(count >= 1 && count <= (1LL << 40) / Q, "count must be positive (and Q * count below 2^40)");
+  CC_CHECK(min_score == min_score, "min_score is NaN");
+  CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
+  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");       // keys hold ~row and ~(n + row) in 32 bits
+  const bool tracks = (flags & CC_RANK_TRACKS) != 0;
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const long n = (long)h->n;
+  const size_t ob = (size_t)Q * (size_t)count;
+  const size_t qbytes = ((size_t)Q * h->dim * 4 + 255) & ~(size_t)255;
+  const bool zero_copy = !on_device && ob * 8 <= kPinResultBytes;            // small host results: written into pinned memory, as search() does
+  const size_t res_bytes = zero_copy ? (ob * 8 + 255) & ~(size_t)255 : 0;
+  ensure_pinned(h, qbytes + res_bytes + (size_t)Q * 4);
+  unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes + res_bytes);
+  int* idx_out = idx; float* sc_out = score;
+  if (zero_copy) { idx_out = reinterpret_cast<int*>(h->pin + qbytes); sc_out = reinterpret_cast<float*>(h->pin + qbytes + ob * 4); }
+  else if (!on_device) {
+    if (h->out_cap < ob) {
+      if (h->idx_dev) hipFree(h->idx_dev);
+      if (h->sc_dev) hipFree(h->sc_dev);
+      h->idx_dev = nullptr; h->sc_dev = nullptr; h->out_cap = 0;
+      CC_HIP(hipMalloc((void**)&h->idx_dev, ob * 4 + 256)); CC_HIP(hipMalloc((void**)&h->sc_dev, ob * 4 + 256)); h->out_cap = ob;
+    }
+    idx_out = h->idx_dev; sc_out = h->sc_dev;
+  }
+  const size_t sel_bytes = (size_t)Q * kRankSel * sizeof(RankSel), hist_bytes = (size_t)Q * kRankSel * 256 * 4, cnt_bytes = (size_t)Q * kRankSel * 4;
+  ensure((void**)&h->rank_ws, &h->rank_ws_cap, sel_bytes + hist_bytes + cnt_bytes + (size_t)Q * 4);
+  RankSel* sel = reinterpret_cast<RankSel*>(h->rank_ws);
+  unsigned* ghist = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes);
+  unsigned* wcnt = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes + hist_bytes);
+  unsigned* tot_dev = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes + hist_bytes + cnt_bytes);
+  CC_HIP(hipMemsetAsync(tot_dev, 0, (size_t)Q * 4, s));
+  // answers the index can give from `start` on: at most one per row.  What lies behind them is padding whatever the scores are.
+  const int64_t avail = std::max<int64_t>(0, std::min<int64_t>(count, (int64_t)n - start));
+  if (avail < count)
+    hipLaunchKernelGGL(rank_pad_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, sc_out, ob);
+  if (n > 0) {
+    const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
+    upload_queries(h, q, Q, on_device, s);
+    compute_scores(h, Q, s);
+    ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * n * 4);
+    const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
+    const int T = std::max(h->n_slots, 1);
+    if (tracks) {
+      ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
+      ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
+      CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
+      CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
+      hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, n, T, h->trk, h->grp,
+                         allowed_dev, h->allowed_cap, h->best, h->first);
+      hipLaunchKernelGGL(rank_keys_kernel<true>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, h->trk, h->best, h->first, T,
+                         min_score, h->key_hi, tot_dev);
+    } else {
+      hipLaunchKernelGGL(rank_keys_kernel<false>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, nullptr, nullptr, nullptr, 0,
+                         min_score, h->key_hi, tot_dev);
+    }
+    const int* trk = tracks ? h->trk : nullptr;
+    const int64_t nwin = (avail + kMaxK - 1) / kMaxK;
+    if (nwin) ensure((void**)&h->cand, &h->cand_cap, (size_t)Q * kRankSel * kMaxK * 8);
+    for (int64_t w0 = 0; w0 < nwin; w0 += kRankSel - 1) {
+      const int nw = (int)std::min<int64_t>(kRankSel - 1, nwin - w0), S = nw + 1;
+      const long r0 = (long)(start + w0 * kMaxK), r_last = (long)(start + std::min<int64_t>(avail, (w0 + nw) * kMaxK));
+      hipLaunchKernelGGL(rank_init_kernel, dim3(Q), dim3(256), 0, s, r0, r_last, sel, ghist, wcnt);
+      for (int byte = 7; byte >= 0; --byte) {
+        hipLaunchKernelGGL(rank_hist_kernel, dim3(nblk, S, Q), dim3(256), 0, s, h->key_hi, n, trk, byte, sel, ghist);
+        hipLaunchKernelGGL(rank_pick_kernel, dim3(S, Q), dim3(64), 0, s, byte, sel, ghist);
+      }
+      hipLaunchKernelGGL(rank_collect_kernel, dim3(nblk, Q), dim3(256), 0, s, h->key_hi, n, trk, S, r0 == 0 ? 1 : 0, sel, wcnt, h->cand);
+      if (tracks) hipLaunchKernelGGL(rank_emit_kernel<true>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, h->trk, h->best, T);
+      else hipLaunchKernelGGL(rank_emit_kernel<false>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, nullptr, nullptr, 0);
+    }
+  }
+  CC_HIP(hipGetLastError());
+  if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+  if (!on_device && !zero_copy) {
+    CC_HIP(hipMemcpyAsync(idx, h->idx_dev, ob * 4, hipMemcpyDeviceToHost, s));
+    CC_HIP(hipMemcpyAsync(score, h->sc_dev, ob * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (!on_device || total) CC_HIP(hipStreamSynchronize(s));
+  if (zero_copy) { memcpy(idx, idx_out, ob * 4); memcpy(score, sc_out, ob * 4); }
+  if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
+  CC_API_END
+}
+
 }  // namespace
 
 extern "C" {
@@ -888,6 +1176,11 @@ int cc_index_search(cc_index* h, const float* q, int Q, int k, int32_t* idx, flo
   return cc_index_search_groups(h, q, Q, k, nullptr, 0, idx, score, on_device, stream);
 }
 
+int cc_index_rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
+                  int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
+  return rank(h, q, Q, start, count, min_score, flags, allowed, n_groups, idx, score, total, on_device, stream);
+}
+
 int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
 
 int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed) { return remove_impl(h, false, drop, 0, n_groups, removed); }
@@ -897,7 +1190,7 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)
   delete h;

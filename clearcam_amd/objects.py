@@ -250,12 +250,50 @@ class EmbeddingIndex:
         """`search_tracks` with the result left on the GPU, like `search_device` (allowed stays a host array)."""
         return self._search_device("cc_index_search_tracks", q, k, allowed)
 
+    @staticmethod
+    def cut_f32(min_score) -> np.float32:
+        """The smallest float32 that is >= the caller's cut (a Python float; None: -inf, no cut).  Scores are float32 and the
+        reference tests `score < cut` in double, so `score >= cut_f32(cut)` in f32 keeps exactly what `not score < cut` keeps."""
+        if min_score is None:
+            return np.float32(-np.inf)
+        t = float(min_score)
+        with np.errstate(over="ignore"):
+            c = np.float32(t)
+        if float(c) < t:                                   # rounded down: one step up
+            c = np.nextafter(c, np.float32(np.inf))
+        return c
+
+    def rank(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Answers start .. start+count-1 of the WHOLE descending order -> (idx (Q,count) int32, score (Q,count) f32, total (Q,)
+        int64), at any depth and of any length, in one call (cc_index_rank).  tracks=True: the answers and their order are those of
+        `search_tracks`; False: every allowed row answers for itself, ordered as `search` orders them.  Only answers with
+        score >= min_score exist (`cut_f32` of the value given): ranks are counted among them and `total` is their number, so a
+        cut inside a run of equal scores keeps the whole run.  -1/-inf past the last answer."""
+        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
+        start, count = int(start), int(count)
+        if count < 1 or start < 0:
+            idx, sc = np.empty((1, 1), np.int32), np.empty((1, 1), np.float32)     # the library names the error
+        else:
+            idx, sc = np.empty((qa.shape[0], count), np.int32), np.empty((qa.shape[0], count), np.float32)
+        total = np.zeros(qa.shape[0], np.int64)
+        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_rank(self._h, _lib.ptr(qa), qa.shape[0], start, count, float(self.cut_f32(min_score)), 1 if tracks else 0,
+                                            _lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size),
+                                            _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 0, None))
+        return idx, sc, total
+
+    def rank_device(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, with_total: bool = True):
+        """`rank` with idx / score left on the GPU like `search_tracks_device`.  `total` still comes back as a host array, which
+        costs one wait for the stream; with_total=False returns None in its place and waits for nothing."""
+        args = (int(start), int(count), float(self.cut_f32(min_score)), 1 if tracks else 0)
+        return self._search_device("cc_index_rank", q, int(count), allowed, args, with_total)
+
     def search_device(self, q, k: int):
         """`search` with the result left on the GPU: (idx int32, score f32) CUDA torch tensors on the current torch stream,
         for callers that keep going on the device (clearcam_amd.dist.ShardedIndex: all-gather + merge)."""
         return self._search_device("cc_index_search_groups", q, k, None)
 
-    def _search_device(self, call: str, q, k: int, allowed):
+    def _search_device(self, call: str, q, k: int, allowed, rank_args=None, with_total: bool = False):
         import torch
         dev = torch.device("cuda", self.device)
         if not bool(getattr(q, "is_cuda", False)):
@@ -276,11 +314,17 @@ class EmbeddingIndex:
             run.wait_stream(cur)
         # nothing waits for the stream here: the filter bytes stay referenced until the next call replaces them
         al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(getattr(_lib.lib(), call)(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
-                                              0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 1, C.c_void_p(run.cuda_stream)))
+        total = np.zeros(qa.shape[0], np.int64) if with_total else None
+        if rank_args is not None:
+            _lib.check(_lib.lib().cc_index_rank(self._h, _lib.ptr(qa), qa.shape[0], *rank_args, _lib.ptr(al) if al is not None else None,
+                                                0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 1,
+                                                C.c_void_p(run.cuda_stream)))
+        else:
+            _lib.check(getattr(_lib.lib(), call)(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
+                                                  0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 1, C.c_void_p(run.cuda_stream)))
         if run is not cur:
             cur.wait_stream(run)
-        return idx, sc
+        return (idx, sc) if rank_args is None else (idx, sc, total)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -911,19 +955,51 @@ class ObjectFinder:
         results.sort(key=lambda x: x[1], reverse=True)
         return results
 
-    def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False):
+    def _search_setup(self, query, cam_name, timestamp, text_embedding, is_face):
+        """What `search` and `search_page` share: -> (q, index, table, allowed) or None when there is nothing to search."""
         embeddings = self.face_embeddings if is_face else self.image_embeddings
         attached = getattr(self, "_attached", False) and not is_face and len(self._dev["store"][1].paths) > 0
         if not embeddings and not attached:
             print("No embeddings available.")
-            return []
+            return None
         if text_embedding is None:
             text_embedding = self.model._encode_text(query).numpy()
         q = np.asarray(as_numpy(text_embedding), np.float32).reshape(-1)
         index, table = self._dev["store"] if attached else self._device_index(embeddings, "face" if is_face else "image")
         if q.size != index.dim:
             raise ValueError(f"query has {q.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
-        allowed = table.allowed(cam_name, timestamp)
+        return q, index, table, table.allowed(cam_name, timestamp)
+
+    def search_page(self, query=None, start=0, count=100, cam_name=None, timestamp=None, text_embedding=None, is_face=False, min_score=None):
+        """One page of the results, what the search endpoint computes (clearcam.py:1108-1118 + `send_results`, :686-705) by asking
+        for top_k = start + count, cutting at the first score below 0.21 and slicing: -> (results, total) with
+        results == [r for r in search(..., top_k=everything) if not r[1] < min_score][start:start+count] and total the length of
+        that filtered list.  One `EmbeddingIndex.rank` call at any depth; only `count` (path, score) pairs leave the GPU."""
+        start, count = int(start), int(count)
+        if start < 0 or count < 1:
+            raise ValueError("search_page needs start >= 0 and count >= 1")
+        if min_score is not None and min_score != min_score:
+            raise ValueError("min_score is NaN")
+        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
+        if setup is None:
+            return [], 0
+        q, index, table, allowed = setup
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return [], 0
+        if any(table.bad[g] for g in live) or not hasattr(index, "rank"):
+            # names the reference raises on (it raises here too), or an index that cannot rank: the whole list, cut on the host
+            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face)
+            kept = [r for r in full if min_score is None or not r[1] < min_score]
+            return kept[start:start + count], len(kept)
+        idx, sc, total = index.rank(q, start, min(count, len(table.paths)), allowed, min_score, tracks=any(table.truthy[g] for g in live))
+        return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
+
+    def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False):
+        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
+        if setup is None:
+            return []
+        q, index, table, allowed = setup
         live = np.flatnonzero(allowed)
         if live.size == 0 or top_k <= 0:
             return []
@@ -933,7 +1009,12 @@ class ObjectFinder:
             # the device reduces per track id and selects (one call, exact whatever the data: thousands of crops of one track, ties)
             idx, sc = index.search_tracks(q, int(top_k), allowed)
             return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
-        # No track ids among the allowed rows, top_k > 1024 or an index without search_tracks:
+        if not exact_loop and hasattr(index, "rank"):
+            # top_k > 1024, or no truthy track id among the allowed crops (the reference does not group then): the device ranks the
+            # whole order and hands back its head.  At most one answer per row: "everything" (top_k = 10**9) allocates no more.
+            idx, sc, _ = index.rank(q, 0, min(int(top_k), len(table.paths)), allowed, None, tracks=grouped)
+            return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
+        # An index without `rank` (no track ids among the allowed rows, top_k > 1024 or no search_tracks either):
         # GPU: filtered top-K' (one HBM pass + radix select); host: the reference's best-per-track-id tail on K' rows.
         # The answer is exact once the top_k-th result scores strictly above the weakest candidate (no unseen row can
         # enter or change it) or every allowed row has been seen; otherwise K' grows, and past 1024 the full score vector

@@ -361,6 +361,19 @@ int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device
  * Arguments, k in [1, 1024] and the -1/-inf padding as in cc_index_search_groups; the index must hold < 2^31 rows. */
 int cc_index_search_tracks(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
                            int on_device, void* stream);
+/* Any window of the WHOLE descending order: answers start .. start + count - 1 (0-based) of every query, at any depth and of any
+ * length, in one call.  With CC_RANK_TRACKS the answers are those of cc_index_search_tracks (one per track slot plus the
+ * slot-less rows, the same order); without it every allowed row is its own answer, ordered as cc_index_search_groups orders
+ * them.  Only answers with score >= min_score (compared in f32; -INFINITY: no cut) exist: ranks are taken among them, and
+ * total (Q int64 on the HOST, may be NULL; asking for it waits for the stream) receives their number per query.
+ * idx / score are (Q, count), -1 / -inf past the last answer; allowed, on_device and stream as in cc_index_search_tracks.
+ * For start 0 and count <= 1024 without a cut the result equals cc_index_search_tracks / cc_index_search_groups element for
+ * element.  Errors (-22, nothing changed): NaN min_score, start < 0, count < 1, Q < 1, unknown flag bits, a bad n_groups,
+ * an index of 2^31 rows or more. */
+#define CC_RANK_TRACKS 1   /* reduce per track slot exactly as cc_index_search_tracks; 0: every allowed row is its own answer */
+int cc_index_rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags,
+                  const uint8_t* allowed, int n_groups,
+                  int32_t* idx, float* score, int64_t* total, int on_device, void* stream);
 /* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
  * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
  * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
