@@ -26,8 +26,9 @@ using namespace cc;
 
 struct cc_index {
   int dim = 0, device = 0; int64_t capacity = 0, n = 0;
-  int storage = F32;                              // F32: exact f32 dot products; BF16: rows rounded to bf16 (half the scan bytes, scores within ~1e-3)
-  float* emb = nullptr;                           // (capacity, dim) rows in the storage type
+  int storage = F32;                              // F32: exact f32 dot products; BF16: rows rounded to bf16 (half the scan bytes, scores within ~1e-3);
+                                                  // CC_INDEX_I8: int8 codes + one f32 scale per 32 elements (dim * 9 / 8 bytes a row)
+  float* emb = nullptr;                           // (capacity, row_bytes()) rows in the storage type
   int* grp = nullptr;                             // (capacity) group id of each row (camera/day bucket chosen by the caller); 0 by default
   int* trk = nullptr;                             // (capacity) track slot of each row: dense per distinct track id, -1 = a crop without one (the default)
   int n_slots = 0;                                // highest slot + 1
@@ -35,7 +36,7 @@ struct cc_index {
   unsigned* first = nullptr; size_t first_cap = 0;           // (n_slots) first allowed row of each track in the current track search
   unsigned* key_hi = nullptr; size_t key_hi_cap = 0;         // (Q, n) high words of the selection keys of the current track search
   unsigned char* allowed = nullptr; int allowed_cap = 0;   // per-group filter of the current search (device copy)
-  size_t row_bytes() const { return (size_t)dim * (storage == F32 ? 4 : 2); }
+  size_t row_bytes() const { return storage == CC_INDEX_I8 ? (size_t)dim + dim / 8 : (size_t)dim * (storage == F32 ? 4 : 2); }
   hipStream_t stream = nullptr;
   float* q_dev = nullptr; int q_cap = 0;
   uint16_t* q16 = nullptr; int q16_cap = 0;     // bf16 copy of the queries (bf16 index, many queries: one MFMA GEMM pass)
@@ -198,6 +199,105 @@ template <int QB> void launch_scan_bf16(cc_index* h, const float* q, float* out,
 // f32 rows -> bf16 rows (round to nearest even), for cc_index_add on a bf16-stored index
 __global__ void to_bf16_kernel(const float* __restrict__ in, uint16_t* __restrict__ out, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = f32_to_bf16_bits(in[i]);
+}
+
+// int8-stored rows (CC_INDEX_I8): dim codes, then dim / 32 f32 scales, one per group of 32 consecutive elements (row_bytes = dim + dim / 8,
+// the rule is in include/clearcam_hip.h).  16 lanes x 16 codes per step of 256; a lane's 16 codes lie inside one group: 16 converts,
+// 16 fma into a group partial per query, then one fma by the group's scale from the row's trailer.  A 16-byte load carries four times
+// the elements of an f32 one, so a wave iteration takes FOUR groups of four rows (16 rows): four independent 16-byte loads per lane
+// in flight like scan_kernel, and every query value read from LDS serves four rows.  Per query the order of the additions is fixed
+// (steps ascending, codes ascending, then the 16-lane butterfly) and does not depend on QB: a batch scores the same however it is split.
+constexpr int kI8Pass = 8;                                        // queries per pass over int8 rows (compute_scores): the fastest of 1..8 measured
+constexpr int kI8Rows = 4;                                        // groups of four rows per wave iteration
+
+__device__ __forceinline__ float i8_code(unsigned w, int b) { return (float)((int)(w << (24 - 8 * b)) >> 24); }
+
+template <int QB>
+__global__ __launch_bounds__(256) void scan_i8_kernel(const char* __restrict__ emb, const float* __restrict__ q, float* __restrict__ out,
+                                                       long n, int dim) {
+  extern __shared__ float4 qs[];                                  // QB x dim/4
+  const int nchunk = dim >> 2;
+  for (int i = threadIdx.x; i < QB * nchunk; i += 256) qs[i] = reinterpret_cast<const float4*>(q)[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+  const int steps = dim >> 8;                                     // 16 lanes x 16 codes per step
+  const size_t rb = (size_t)dim + (dim >> 3);
+  for (long r0 = wave * (4 * kI8Rows); r0 < n; r0 += nwaves * (4 * kI8Rows)) {
+    const char* e[kI8Rows];
+    float acc[kI8Rows][QB];
+#pragma unroll
+    for (int r = 0; r < kI8Rows; ++r) {
+      const long row = r0 + r * 4 + grp;
+      e[r] = emb + (size_t)(row < n ? row : n - 1) * rb;
+#pragma unroll
+      for (int c = 0; c < QB; ++c) acc[r][c] = 0.f;
+    }
+    for (int t = 0; t < steps; ++t) {
+      uint4 v[kI8Rows]; float sc[kI8Rows];
+#pragma unroll
+      for (int r = 0; r < kI8Rows; ++r) {
+        v[r] = reinterpret_cast<const uint4*>(e[r])[t * 16 + sub];
+        sc[r] = reinterpret_cast<const float*>(e[r] + dim)[t * 8 + (sub >> 1)];
+      }
+      float f[kI8Rows][16];
+#pragma unroll
+      for (int r = 0; r < kI8Rows; ++r) {
+        const unsigned w[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) f[r][i] = i8_code(w[i >> 2], i & 3);
+      }
+#pragma unroll
+      for (int c = 0; c < QB; ++c) {
+        const float4* qc = qs + c * nchunk + (t * 16 + sub) * 4;
+        const float4 q0 = qc[0], q1 = qc[1], q2 = qc[2], q3 = qc[3];
+        const float qq[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+#pragma unroll
+        for (int r = 0; r < kI8Rows; ++r) {
+          float p = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) p = fmaf(f[r][i], qq[i], p);
+          acc[r][c] = fmaf(p, sc[r], acc[r][c]);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kI8Rows; ++r) {
+      const long row = r0 + r * 4 + grp;
+#pragma unroll
+      for (int c = 0; c < QB; ++c) {
+        float sum = acc[r][c];
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if (sub == 0 && row < n) out[(long)c * n + row] = sum;
+      }
+    }
+  }
+}
+
+template <int QB> void launch_scan_i8(cc_index* h, const float* q, float* out, hipStream_t s) {
+  const int blocks = (int)std::min<int64_t>((h->n + 16 * kI8Rows - 1) / (16 * kI8Rows), 256 * 8);
+  hipLaunchKernelGGL(scan_i8_kernel<QB>, dim3(blocks), dim3(256), (size_t)QB * h->dim * 4, s, reinterpret_cast<const char*>(h->emb), q, out, (long)h->n, h->dim);
+}
+
+// f32 rows -> int8 rows, for cc_index_add on an i8-stored index: one lane per element, a group of 32 elements is one half-wave.
+// dim % 256 == 0, so every wave is whole and a group never straddles two rows.  The rule (include/clearcam_hip.h): a = max |x| of the
+// group, s = a / 127 (correctly rounded f32 division), s zero or subnormal -> s = 0 and codes 0, else code = clamp(rint(x / s), +-127).
+__global__ __launch_bounds__(256) void quantise_i8_kernel(const float* __restrict__ in, char* __restrict__ out, size_t cnt, int dim) {
+  const size_t rb = (size_t)dim + (dim >> 3);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (size_t)gridDim.x * 256) {
+    const float x = in[i];
+    float a = fabsf(x);
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+    float s = a / 127.0f;
+    if (!(s >= 1.17549435e-38f)) s = 0.f;                         // zero or subnormal: nothing depends on the denormal mode
+    const float c = s > 0.f ? fminf(fmaxf(rintf(x / s), -127.f), 127.f) : 0.f;
+    const size_t row = i / (size_t)dim; const int j = (int)(i - row * dim);
+    char* o = out + row * rb;
+    o[j] = (char)(int)c;
+    if ((j & 31) == 0) reinterpret_cast<float*>(o + dim)[j >> 5] = s;
+  }
 }
 
 __device__ __forceinline__ unsigned ordered(float f) {          // monotone float -> uint
@@ -728,6 +828,24 @@ void compute_scores(cc_index* h, int Q, hipStream_t s) {
     const ConvP g = gemm_params(h->q16, h->dim, Q, h->dim, h->emb, h->dim, nullptr, (int)h->n, h->scores, (int)h->n, 1, 0, nullptr, 0, 0);
     if (conv_mfma_supported(BF16, g)) { launch_conv_mfma(BF16, g, s); return; }
   }
+  if (h->storage == CC_INDEX_I8) {
+    // int8 rows: there is no MFMA GEMM path for them, any number of queries goes through repeated scan passes.  The pass width is a
+    // measured choice (docs/measurement.md, "int8 rows"): one convert and QB fma per code keep a pass at HBM speed only while QB is
+    // small.  cc_dev_set("index_i8_pass") overrides it (1..8); the LDS copy of the queries caps it at 64 KB / (dim * 4).
+    int W = g_index_i8_pass.load();
+    W = std::max(1, std::min(std::min(W > 0 ? W : kI8Pass, 8), 16384 / h->dim));
+    for (int q0 = 0; q0 < Q; q0 += W) {
+      const float* q = h->q_dev + (size_t)q0 * h->dim; float* out = h->scores + (size_t)q0 * h->n;
+      switch (std::min(W, Q - q0)) {
+        case 1: launch_scan_i8<1>(h, q, out, s); break;  case 2: launch_scan_i8<2>(h, q, out, s); break;
+        case 3: launch_scan_i8<3>(h, q, out, s); break;  case 4: launch_scan_i8<4>(h, q, out, s); break;
+        case 5: launch_scan_i8<5>(h, q, out, s); break;  case 6: launch_scan_i8<6>(h, q, out, s); break;
+        case 7: launch_scan_i8<7>(h, q, out, s); break;  default: launch_scan_i8<8>(h, q, out, s); break;
+      }
+    }
+    CC_HIP(hipGetLastError());
+    return;
+  }
   if (h->storage == BF16) {                         // bf16 rows: 8 queries per pass over half the bytes (dim % 256 == 0 is checked at create)
     for (int q0 = 0; q0 < Q; q0 += 8) {
       const float* q = h->q_dev + (size_t)q0 * h->dim; float* out = h->scores + (size_t)q0 * h->n;
@@ -776,8 +894,9 @@ extern "C" {
 int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int storage) {
   CC_API_BEGIN
   CC_CHECK(h && dim > 0 && dim % 4 == 0 && capacity > 0, "bad argument (dim must be a multiple of 4)");
-  CC_CHECK(storage == F32 || storage == BF16, "index storage must be 0 (f32) or 2 (bf16)");
-  CC_CHECK(storage == F32 || dim % 256 == 0, "a bf16 index needs dim % 256 == 0");
+  CC_CHECK(storage == F32 || storage == BF16 || storage == CC_INDEX_I8, "index storage must be 0 (f32), 2 (bf16) or 8 (int8 with group scales)");
+  CC_CHECK(storage != BF16 || dim % 256 == 0, "a bf16 index needs dim % 256 == 0");
+  CC_CHECK(storage != CC_INDEX_I8 || (dim % 256 == 0 && dim <= 16384), "an int8 index needs dim % 256 == 0 (and dim <= 16384)");
   int n = 0; CC_HIP(hipGetDeviceCount(&n));
   CC_CHECK(n > 0 && device >= 0 && device < n, "no such HIP device");
   CC_HIP(hipSetDevice(device));
@@ -793,7 +912,7 @@ int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int 
 
 int cc_index_create(cc_index** h, int dim, int64_t capacity, int device) { return cc_index_create_ex(h, dim, capacity, device, F32); }
 
-// Append n rows (f32 in; rounded to bf16 for a bf16 index) with their group ids (null: group 0) and track slots (null: -1, no
+// Append n rows (f32 in; rounded to bf16 for a bf16 index, quantised for an int8 one) with their group ids (null: group 0) and track slots (null: -1, no
 // track).  The matrix grows geometrically when it is full (new allocation, device-to-device copy, swap), so callers never see a
 // capacity error.
 int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks) {
@@ -835,7 +954,10 @@ int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device
       // the index's private non-blocking stream, which nothing orders behind that producer.  The f32 path is ordered by its
       // blocking hipMemcpy; here the producer is waited for explicitly (add is not a hot path).
       else CC_HIP(hipDeviceSynchronize());
-      hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)std::min<size_t>((cnt + 255) / 256, 65535)), dim3(256), 0, h->stream, src, reinterpret_cast<uint16_t*>(dst), cnt);
+      const dim3 grid((unsigned)std::min<size_t>((cnt + 255) / 256, 65535));
+      if (h->storage == CC_INDEX_I8) hipLaunchKernelGGL(quantise_i8_kernel, grid, dim3(256), 0, h->stream, src, dst, cnt, h->dim);
+      else hipLaunchKernelGGL(to_bf16_kernel, grid, dim3(256), 0, h->stream, src, reinterpret_cast<uint16_t*>(dst), cnt);
+      CC_HIP(hipGetLastError());
       CC_HIP(hipStreamSynchronize(h->stream));
       if (tmp) hipFree(tmp);
     }
@@ -886,7 +1008,7 @@ int cc_index_scores(cc_index* h, const float* q, int Q, float* scores, int on_de
 
 }  // extern "C"
 
-namespace cc { std::atomic<int> g_index_slab_rows{-1}; }
+namespace cc { std::atomic<int> g_index_slab_rows{-1}; std::atomic<int> g_index_i8_pass{-1}; }
 
 namespace {
 
@@ -936,7 +1058,7 @@ int remove_impl(cc_index* h, bool by_rows, const uint8_t* drop, int64_t n_rows, 
   T = T > 0 ? (T + kGran - 1) / kGran * kGran : kSlabRows;
   const int64_t direct_min = std::max<int64_t>(kGran, T / 4);
   const size_t rb = h->row_bytes();
-  const int chunks = (int)(rb / 16);                 // dim % 4 == 0 (f32) / dim % 256 == 0 (bf16): whole 16-byte pieces
+  const int chunks = (int)(rb / 16);                 // dim % 4 == 0 (f32) / dim % 256 == 0 (bf16; int8: dim + dim / 8 bytes, a multiple of 32): whole 16-byte pieces
   char* emb = reinterpret_cast<char*>(h->emb);
   int64_t ga = 0;                                    // granules before the first removed row stay where they are
   while (ga < nb && (int64_t)off[ga + 1] - (int64_t)off[ga] == std::min<int64_t>(kGran, n - ga * kGran)) ++ga;

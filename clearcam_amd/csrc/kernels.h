@@ -186,6 +186,8 @@ void resize_slots(int device, hipStream_t base, std::vector<hipStream_t>& slot_s
 void order_after(hipStream_t waiter, hipStream_t signaller);
 // cc_dev_set("index_slab_rows"): rows per bounced slab of cc_index_remove_* (index.hip); -1 = the default
 extern std::atomic<int> g_index_slab_rows;
+// cc_dev_set("index_i8_pass"): queries per scan pass over int8 rows (index.hip, 1..8); -1 = the measured default
+extern std::atomic<int> g_index_i8_pass;
 
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;

@@ -139,13 +139,17 @@ class OpenCLIP:
 
 
 class EmbeddingIndex:
-    """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores) or "bf16" (half the
-    bytes per scan, scores within ~1e-3 for unit vectors).  `capacity` is the initial allocation; the matrix grows."""
+    """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores), "bf16" (half the
+    bytes per scan, scores within ~1e-3 for unit vectors) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
+    bytes a row, scores within ~1e-3 as well; include/clearcam_hip.h has the rule).  `capacity` is the initial allocation; the
+    matrix grows."""
+
+    STORAGE = {"f32": 0, "bf16": 2, "i8": 8}           # name -> the `storage` argument of cc_index_create_ex
 
     def __init__(self, dim: int = 768, capacity: int = 1 << 20, device: int = 0, storage: str = "f32"):
         self.dim, self.device, self.storage = dim, device, storage
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().cc_index_create_ex(C.byref(self._h), dim, max(int(capacity), 1), device, {"f32": 0, "bf16": 2}[storage]))
+        _lib.check(_lib.lib().cc_index_create_ex(C.byref(self._h), dim, max(int(capacity), 1), device, self.STORAGE[storage]))
 
     @property
     def capacity(self) -> int:
@@ -504,7 +508,7 @@ class ObjectFinder:
         self._dev_sig: Dict[str, tuple] = {}
         self._version = {"image": 0, "face": 0}
         self._stores: Dict[str, object] = {}
-        self.index_storage = "f32"             # "bf16" halves the scan bytes (scores within ~1e-3)
+        self.index_storage = "f32"             # "bf16" halves the scan bytes, "i8" takes 9/8 byte per element (scores within ~1e-3 either way)
 
     def init_clip(self, **clip_kwargs):
         """:199-206 (warm-up included: the first call per shape builds and captures the hipGraph)."""

@@ -208,6 +208,8 @@ int cc_round_weights(int dtype, const float* w, int64_t cout, int64_t cin, int64
  * keys "stream_abl", "tile64_abl": timing ablations of development builds (no effect otherwise);
  * key "index_slab_rows": rows per bounced slab of cc_index_remove_* (-1 = the measured default), so that a test can force many
  *     slabs on a small index; rounded up to a multiple of 64.
+ * key "index_i8_pass": queries per scan pass over the rows of a CC_INDEX_I8 index, 1 .. 8 (-1 = the measured default, 8), read at every
+ *     search, so that the measuring tool can sweep it; scores do not depend on it.
  * key "route_log": 1 = every conv / GEMM launch appends one record to a process-wide list (cc_route_log_take), 0 = off (default).
  * Plans already built keep the launches they were built with.  Not part of the drop-in surface. */
 int cc_dev_set(const char* key, int value);
@@ -336,7 +338,18 @@ typedef struct cc_index cc_index;
 int cc_index_create(cc_index** h, int dim, int64_t capacity, int device);        /* f32 rows */
 /* storage 0: f32 rows, exact f32 dot products.  storage 2: rows rounded to bf16 (half the bytes per scan; scores within
  * ~1e-3 of the f32 index for unit vectors; dim % 256 == 0).  `capacity` is the initial allocation: the matrix grows
- * geometrically (device-to-device copy) when cc_index_add* runs past it. */
+ * geometrically (device-to-device copy) when cc_index_add* runs past it.
+ * storage CC_INDEX_I8 (8, clear of the CC_DTYPE_* numbers): int8 rows, dim % 256 == 0 (and dim <= 16384).  A stored row is dim int8
+ * codes (two's complement, element order) followed by dim / 32 float32 scales, one per group of 32 consecutive elements:
+ * dim + dim / 8 bytes, 864 for dim 768.  The rule, per group with elements x_i, all in float32:
+ *   a = max |x_i|;  s = a / 127.0f (correctly rounded division);  if s is zero or subnormal: s = 0 and every code 0;
+ *   otherwise code_i = clamp(rintf(x_i / s), -127, 127) (round half to even).  The decoded element is (float)code_i * s.
+ * A score is sum over groups of s_g * (sum_i code_i * q_i), accumulated in f32 in a fixed order: deterministic, ties break by row id,
+ * and the same however a query batch is split into passes.  |score - exact| <= sum_g (s_g / 2) * ||q_g||_1 plus f32 summation error
+ * (about 1e-3 at most, 2e-4 rms for unit 768-d rows).  Queries stay f32; any number of them goes through repeated scan passes (no
+ * MFMA GEMM path).  Rows must be finite: a NaN or infinite element leaves the codes and the scale of ITS group of 32 undefined (the
+ * row then scores NaN or nonsense); other groups and other rows are not affected, and nothing checks for it. */
+#define CC_INDEX_I8 8
 int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int storage);
 int cc_index_add(cc_index* h, const float* emb, int64_t n, int on_device);       /* append n rows (n,dim) f32, group 0 */
 /* the same with one group id (0 <= id < 2^24) per row on the HOST: the caller's (camera, day folder) bucket, the unit
