@@ -15,6 +15,7 @@ SYMBOLS = [
     "cc_yolo_get_tensor", "cc_yolo_get_tensor_frames", "cc_yolo_nonfinite",
     "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv2d_ex", "cc_route_log_take", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
     "cc_dev_decode", "cc_dev_head_tail", "cc_dev_topk_nms", "cc_dev_blaze_post",
+    "cc_dev_attention", "cc_dev_layernorm", "cc_dev_assemble_ln", "cc_dev_patchify", "cc_dev_embed", "cc_dev_l2norm",
     "cc_clip_create", "cc_clip_load", "cc_clip_finalize", "cc_clip_encode_image", "cc_clip_encode_text",
     "cc_clip_set_in_flight", "cc_clip_submit_image", "cc_clip_wait",
     "cc_clip_last_gpu_ms", "cc_clip_destroy", "cc_crop_preprocess", "cc_cv_resize_linear_u8", "cc_cv_warp_affine_u8",
@@ -104,6 +105,12 @@ def lib() -> C.CDLL:
         "cc_dev_head_tail": [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, ip, ip, C.c_int, vp, C.c_float, vp, ip, vp],
         "cc_dev_topk_nms": [vp, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp, vp],
         "cc_dev_blaze_post": [vp, vp, vp, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp],
+        "cc_dev_attention": [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp],
+        "cc_dev_layernorm": [C.c_int, vp, C.c_longlong, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
+        "cc_dev_assemble_ln": [C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
+        "cc_dev_patchify": [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp],
+        "cc_dev_embed": [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
+        "cc_dev_l2norm": [vp, C.c_int, C.c_int, C.c_float, vp],
         "cc_conv_bench": [C.c_int] * 11 + [fp],
         "cc_dev_set": [C.c_char_p, C.c_int],
         "cc_round_weights": [C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, vp],

@@ -184,6 +184,31 @@ int cc_dev_head_tail(int dtype, int ch, const void* const* bx_dev, const void* c
 int cc_dev_topk_nms(const float* rows_dev, int B, int A, float iou_thr, const float* geometry, int ragged, float* out_dev, void* stream);
 int cc_dev_blaze_post(const float* r8_dev, const float* r16_dev, const float* c8_dev, const float* c16_dev, int B, const float* anchors,
                       float scale, int pad_top, int pad_left, float* out_dev, float* first_dev, int32_t* first_idx_dev, void* stream);
+/* Single-launch entries of the CLIP kernel tests: ONE launch of a CLIP tower kernel other than the GEMMs through its production launcher
+ * (launch_attention, launch_layernorm, launch_assemble_ln, launch_patchify, launch_embed, launch_l2norm).  Every tensor is a device
+ * pointer the caller owns (the entries allocate nothing, so alignment and buffer size are the caller's; only cc_dev_embed takes HOST
+ * tokens and holds a device copy for the call).  Each validates its arguments (an error, and no launch, on null pointers, non-positive
+ * sizes, an unsupported dtype, or what the launcher itself refuses) and synchronises `stream`.  dtype 0 / 1 / 2 = f32 / f16 / bf16.
+ *
+ * cc_dev_attention: qkv_dev (B*L, 3*D) and ctx_dev (B*L, D) in the storage type, D = 64*H; 1 <= L <= 288, scale > 0; f16 / bf16 run
+ * attn_mfma_kernel (qkv_dev 16-byte, ctx_dev 8-byte aligned), f32 attn_simple_kernel.
+ * cc_dev_layernorm: row r reads in_dev + (row_index_dev ? row_index_dev[r] : r) * in_row_stride (float32, D <= 1024) and writes row r
+ * of out_dev (rows, D): float32 when out_f32, else the storage type.
+ * cc_dev_assemble_ln: patches_dev (B*(L-1), D) in the storage type, cls_dev (D), pos_dev (L, D), LayerNorm w_dev / b_dev (D) -> out_dev
+ * (B*L, D) float32; D <= 1024.
+ * cc_dev_patchify: x_dev float32 (B,3,S,S) -> out_dev (B*g*g, Kpad) in the storage type, g = S / patch; S % patch == 0,
+ * Kpad >= 3*patch*patch, columns past 3*patch*patch zero.
+ * cc_dev_embed: tokens HOST int32 (B,L), each checked against vocab before anything is uploaded; table_dev (vocab, D), pos_dev (L, D)
+ * -> out_dev (B*L, D), all float32.
+ * cc_dev_l2norm: x_dev float32 (rows, D) in place, x / (||x|| + eps); eps >= 0. */
+int cc_dev_attention(int dtype, const void* qkv_dev, int B, int L, int H, int causal, float scale, void* ctx_dev, void* stream);
+int cc_dev_layernorm(int dtype, const float* in_dev, long long in_row_stride, const int32_t* row_index_dev, const float* w_dev, const float* b_dev,
+                     void* out_dev, int out_f32, int rows, int D, void* stream);
+int cc_dev_assemble_ln(int dtype, const void* patches_dev, const float* cls_dev, const float* pos_dev, const float* w_dev, const float* b_dev,
+                       float* out_dev, int B, int L, int D, void* stream);
+int cc_dev_patchify(int dtype, const float* x_dev, void* out_dev, int B, int S, int patch, int Kpad, void* stream);
+int cc_dev_embed(const int32_t* tokens, int vocab, const float* table_dev, const float* pos_dev, float* out_dev, int B, int L, int D, void* stream);
+int cc_dev_l2norm(float* x_dev, int rows, int D, float eps, void* stream);
 /* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 18 ints each into `records` and sets *n to the number of records
  * the log held; records that did not fit (*n > cap) stay in the log for the next call.  A record: kernel, schedule, tile pixels, tile channels, k, stride, Ho / Wo beyond the symmetric formula,
  * act, residual (0 none / 1 storage type / 2 float32), out_f32, Cout / out_coff / out_cstride all multiples of 8, then B, H, W, Cin,
