@@ -180,10 +180,14 @@ template <class T, int BN> static void launch_adown_k(const ConvP& p, hipStream_
   CC_HIP(hipGetLastError());
 }
 
+int conv_adown_bn(const ConvP& p) {
+  auto padded = [&](int bn) { return (p.Cout + bn - 1) / bn * bn; };
+  return padded(64) < padded(128) ? 64 : 128;
+}
+
 void launch_conv_adown(int dt, const ConvP& p, hipStream_t stream) {
   CC_CHECK(conv_adown_supported(dt, p), "fused average + stride-2 conv: unsupported shape");
-  auto padded = [&](int bn) { return (p.Cout + bn - 1) / bn * bn; };
-  const bool narrow = padded(64) < padded(128);
+  const bool narrow = conv_adown_bn(p) == 64;
   if (dt == F16) { if (narrow) launch_adown_k<f16_t, 64>(p, stream); else launch_adown_k<f16_t, 128>(p, stream); }
   else { if (narrow) launch_adown_k<bf16_t, 64>(p, stream); else launch_adown_k<bf16_t, 128>(p, stream); }
 }

@@ -285,38 +285,62 @@ __global__ __launch_bounds__(256) void pool_kernel(const PoolP p) {
   reinterpret_cast<T*>(p.out)[m * p.out_cstride + p.out_coff + c] = from_f32<T>(acc);
 }
 
-template <class T> static void launch_pool_t(const PoolP& p, hipStream_t stream) {
-  constexpr int E = 16 / (int)sizeof(T);
+// Output rows per thread of the avg 2x2 / avg-max kernels: cc_dev_set("pool_rows") where set, else CLEARCAM_POOL_ROWS, else the defaults
+// (eight rows for the average, two for avg-max; kNoPoolRows = neither is set)
+std::atomic<int> g_pool_rows_override{-1};
+constexpr int kNoPoolRows = INT32_MIN;
+static int pool_rows() {
+  const int ov = g_pool_rows_override.load();
+  if (ov >= 0) return ov;
+  static const int env = [] { const char* e = getenv("CLEARCAM_POOL_ROWS"); return e ? atoi(e) : kNoPoolRows; }();
+  return env;
+}
+
+PoolKernel choose_pool(int dt, const PoolP& p) {
+  const int E = dt == F32 ? 4 : 8;
   const bool vec = p.C % E == 0 && p.in_coff % E == 0 && p.in_cstride % E == 0 && p.out_coff % E == 0 && p.out_cstride % E == 0 &&
                    ((uintptr_t)p.in & 15) == 0 && ((uintptr_t)p.out & 15) == 0;
-  const dim3 vgrid((unsigned)((p.Wo * (p.C / E) + 255) / 256), (unsigned)p.Ho, (unsigned)p.B);
+  const int set = pool_rows();
   if (p.mode == 2) {
     CC_CHECK(vec && p.k == 3 && p.stride == 2 && p.pad == 1, "avg-max pool: needs 16-byte channel chunks, k=3 s=2 p=1");
-    static const int rows2 = [] { const char* e = getenv("CLEARCAM_POOL_ROWS"); return e ? atoi(e) : 4; }();
-    if (rows2 != 1 && p.Ho >= 32) hipLaunchKernelGGL(avgmax_rows2_kernel<T>, dim3(vgrid.x, (unsigned)((p.Ho + 1) / 2), vgrid.z), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(avgmax_pool_kernel<T>, vgrid, dim3(256), 0, stream, p);
-  } else if (vec && p.mode == 0 && p.k == 2) {
+    const int rows2 = set == kNoPoolRows ? 4 : set;
+    return rows2 != 1 && p.Ho >= 32 ? POOL_AVGMAX_ROWS2 : POOL_AVGMAX;
+  }
+  if (vec && p.mode == 0 && p.k == 2) {
     // stride 1, no padding, at least 64 rows: eight output rows per thread (CLEARCAM_POOL_ROWS=4 / 1: four / one).  Pools per 64-frame step:
     // 0.726 ms with one row, 0.660 with four (+ two rows in the avg-max kernel), 0.654 with eight - same bits (profiles/r05t_pool_rows.txt)
-    static const int rows = [] { const char* e = getenv("CLEARCAM_POOL_ROWS"); return e ? atoi(e) : 8; }();
+    const int rows = set == kNoPoolRows ? 8 : set;
     const bool plain = p.stride == 1 && p.pad == 0 && p.Ho >= 64 && p.Wo == p.W - 1 && p.Ho == p.H - 1;
-    if (rows == 8 && plain)
-      hipLaunchKernelGGL((avg2_rows_kernel<T, 8>), dim3(vgrid.x, (unsigned)((p.Ho + 7) / 8), vgrid.z), dim3(256), 0, stream, p);
-    else if (rows == 4 && plain)
-      hipLaunchKernelGGL((avg2_rows_kernel<T, 4>), dim3(vgrid.x, (unsigned)((p.Ho + 3) / 4), vgrid.z), dim3(256), 0, stream, p);
-    else
-    hipLaunchKernelGGL((pool_vec_kernel<T, 2, 0>), vgrid, dim3(256), 0, stream, p);
-  } else if (vec && p.mode == 1 && p.k == 1) {                       // AdaFace's MaxPool2d(1, stride) shortcut: a strided copy
-    hipLaunchKernelGGL((pool_vec_kernel<T, 1, 1>), vgrid, dim3(256), 0, stream, p);
-  } else if (vec && p.mode == 1 && p.k == 2) {                       // BlazeFace's max_pool2d(2, 2)
-    hipLaunchKernelGGL((pool_vec_kernel<T, 2, 1>), vgrid, dim3(256), 0, stream, p);
-  } else if (vec && p.mode == 1 && p.k == 3) {
-    hipLaunchKernelGGL((pool_vec_kernel<T, 3, 1>), vgrid, dim3(256), 0, stream, p);
-  } else if (vec && p.mode == 1 && p.k == 5) {
-    hipLaunchKernelGGL((pool_vec_kernel<T, 5, 1>), vgrid, dim3(256), 0, stream, p);
-  } else {
-    const size_t total = (size_t)p.B * p.Ho * p.Wo * p.C;
-    hipLaunchKernelGGL(pool_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
+    if (rows == 8 && plain) return POOL_AVG2_ROWS8;
+    if (rows == 4 && plain) return POOL_AVG2_ROWS4;
+    return POOL_VEC_AVG2;
+  }
+  if (vec && p.mode == 1 && p.k == 1) return POOL_VEC_MAX1;           // AdaFace's MaxPool2d(1, stride) shortcut: a strided copy
+  if (vec && p.mode == 1 && p.k == 2) return POOL_VEC_MAX2;           // BlazeFace's max_pool2d(2, 2)
+  if (vec && p.mode == 1 && p.k == 3) return POOL_VEC_MAX3;
+  if (vec && p.mode == 1 && p.k == 5) return POOL_VEC_MAX5;
+  return POOL_SCALAR;
+}
+
+template <class T> static void launch_pool_t(PoolKernel k, const PoolP& p, hipStream_t stream) {
+  constexpr int E = 16 / (int)sizeof(T);
+  const dim3 vgrid((unsigned)((p.Wo * (p.C / E) + 255) / 256), (unsigned)p.Ho, (unsigned)p.B);
+  auto rows_grid = [&](int r) { return dim3(vgrid.x, (unsigned)((p.Ho + r - 1) / r), vgrid.z); };
+  switch (k) {
+    case POOL_AVGMAX_ROWS2: hipLaunchKernelGGL(avgmax_rows2_kernel<T>, rows_grid(2), dim3(256), 0, stream, p); break;
+    case POOL_AVGMAX: hipLaunchKernelGGL(avgmax_pool_kernel<T>, vgrid, dim3(256), 0, stream, p); break;
+    case POOL_AVG2_ROWS8: hipLaunchKernelGGL((avg2_rows_kernel<T, 8>), rows_grid(8), dim3(256), 0, stream, p); break;
+    case POOL_AVG2_ROWS4: hipLaunchKernelGGL((avg2_rows_kernel<T, 4>), rows_grid(4), dim3(256), 0, stream, p); break;
+    case POOL_VEC_AVG2: hipLaunchKernelGGL((pool_vec_kernel<T, 2, 0>), vgrid, dim3(256), 0, stream, p); break;
+    case POOL_VEC_MAX1: hipLaunchKernelGGL((pool_vec_kernel<T, 1, 1>), vgrid, dim3(256), 0, stream, p); break;
+    case POOL_VEC_MAX2: hipLaunchKernelGGL((pool_vec_kernel<T, 2, 1>), vgrid, dim3(256), 0, stream, p); break;
+    case POOL_VEC_MAX3: hipLaunchKernelGGL((pool_vec_kernel<T, 3, 1>), vgrid, dim3(256), 0, stream, p); break;
+    case POOL_VEC_MAX5: hipLaunchKernelGGL((pool_vec_kernel<T, 5, 1>), vgrid, dim3(256), 0, stream, p); break;
+    case POOL_SCALAR: {
+      const size_t total = (size_t)p.B * p.Ho * p.Wo * p.C;
+      hipLaunchKernelGGL(pool_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
+      break;
+    }
   }
   CC_HIP(hipGetLastError());
 }
@@ -363,10 +387,12 @@ void launch_fuse(int dt, const FuseP& p, hipStream_t stream) {
   CC_HIP(hipGetLastError());
 }
 
-void launch_pool(int dt, const PoolP& p, hipStream_t stream) {
-  if (dt == F32) launch_pool_t<float>(p, stream);
-  else if (dt == F16) launch_pool_t<f16_t>(p, stream);
-  else launch_pool_t<bf16_t>(p, stream);
+void launch_pool(int dt, const PoolP& p, hipStream_t stream, PoolKernel* chosen) {
+  const PoolKernel k = choose_pool(dt, p);
+  if (chosen) *chosen = k;
+  if (dt == F32) launch_pool_t<float>(k, p, stream);
+  else if (dt == F16) launch_pool_t<f16_t>(k, p, stream);
+  else launch_pool_t<bf16_t>(k, p, stream);
 }
 
 }  // namespace cc

@@ -120,26 +120,28 @@ PConv make_conv(cc_face* h, const std::string& wname, const std::string& bn, con
   return pc;
 }
 
+void launch_affine(int dt, const AffineP& af, hipStream_t s) {
+  const int E = dt == F32 ? 4 : 8;
+  const unsigned blocks = (unsigned)((af.n / E + 255) / 256);
+  if (dt == F32) hipLaunchKernelGGL(affine_kernel<float>, dim3(blocks), dim3(256), 0, s, af);
+  else if (dt == F16) hipLaunchKernelGGL(affine_kernel<f16_t>, dim3(blocks), dim3(256), 0, s, af);
+  else hipLaunchKernelGGL(affine_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, af);
+}
+
+void launch_face_pre(int dt, const FacePreP& pre, hipStream_t s) {
+  const unsigned blocks = (unsigned)(((long)pre.B * kRes * kRes + 255) / 256);
+  if (dt == F32) hipLaunchKernelGGL(face_pre_kernel<float>, dim3(blocks), dim3(256), 0, s, pre);
+  else if (dt == F16) hipLaunchKernelGGL(face_pre_kernel<f16_t>, dim3(blocks), dim3(256), 0, s, pre);
+  else hipLaunchKernelGGL(face_pre_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, pre);
+}
+
 void run_ops(cc_face* h, FPlan* P, hipStream_t s) {
   for (const FOp& op : P->ops) {
     switch (op.kind) {
       case 0: launch_conv(h->dtype, op.conv, s); break;
       case 1: launch_pool(h->dtype, op.pool, s); break;
-      case 2: {
-        const int E = h->dtype == F32 ? 4 : 8;
-        const unsigned blocks = (unsigned)((op.af.n / E + 255) / 256);
-        if (h->dtype == F32) hipLaunchKernelGGL(affine_kernel<float>, dim3(blocks), dim3(256), 0, s, op.af);
-        else if (h->dtype == F16) hipLaunchKernelGGL(affine_kernel<f16_t>, dim3(blocks), dim3(256), 0, s, op.af);
-        else hipLaunchKernelGGL(affine_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, op.af);
-        break;
-      }
-      case 3: {
-        const unsigned blocks = (unsigned)(((long)op.pre.B * kRes * kRes + 255) / 256);
-        if (h->dtype == F32) hipLaunchKernelGGL(face_pre_kernel<float>, dim3(blocks), dim3(256), 0, s, op.pre);
-        else if (h->dtype == F16) hipLaunchKernelGGL(face_pre_kernel<f16_t>, dim3(blocks), dim3(256), 0, s, op.pre);
-        else hipLaunchKernelGGL(face_pre_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, op.pre);
-        break;
-      }
+      case 2: launch_affine(h->dtype, op.af, s); break;
+      case 3: launch_face_pre(h->dtype, op.pre, s); break;
       default: launch_l2norm(op.nm, s);
     }
   }
@@ -305,6 +307,33 @@ void cc_face_destroy(cc_face* h) {
   for (void* p : h->wallocs) hipFree(p);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)
   delete h;
+}
+
+// Development entries: ONE launch of affine_kernel / face_pre_kernel, as run_ops launches them, on buffers the caller crafts (no handle,
+// no plan).  Every pointer is device memory the caller owns; arguments are validated before anything is launched.
+int cc_dev_affine(int dtype, const void* x_dev, void* y_dev, const float* scale_dev, const float* shift_dev, long long n, int C, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(dtype >= 0 && dtype <= 2, "dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  CC_CHECK(x_dev && y_dev && scale_dev && shift_dev, "null argument");
+  const int E = dtype == F32 ? 4 : 8;
+  CC_CHECK(C > 0 && C % E == 0 && n > 0 && n % C == 0 && n < (1LL << 31), "n must be whole pixels of C channels, C whole 16-byte chunks");
+  CC_CHECK(((uintptr_t)x_dev & 15) == 0 && ((uintptr_t)y_dev & 15) == 0, "x and y must be 16-byte aligned (uint4 accesses)");
+  launch_affine(dtype, AffineP{x_dev, y_dev, scale_dev, shift_dev, (long)n, C}, (hipStream_t)stream);
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipStreamSynchronize((hipStream_t)stream));
+  CC_API_END
+}
+
+int cc_dev_face_pre(int dtype, const void* img_dev, int img_f32, void* out_dev, int B, int cpad, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(dtype >= 0 && dtype <= 2, "dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  CC_CHECK(img_dev && out_dev, "null argument");
+  CC_CHECK(B > 0 && B <= 4096 && cpad >= 3 && cpad <= 64, "bad batch size / channel padding");
+  CC_CHECK(!img_f32 || ((uintptr_t)img_dev & 3) == 0, "float32 frames must be 4-byte aligned");
+  launch_face_pre(dtype, FacePreP{img_dev, img_f32 ? 1 : 0, out_dev, B, cpad}, (hipStream_t)stream);
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipStreamSynchronize((hipStream_t)stream));
+  CC_API_END
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@ void launch_conv_direct(int dt, const ConvP& p, hipStream_t stream);
 void launch_conv(int dt, const ConvP& p, hipStream_t stream);
 // 3x3 stride-2 conv over the 2x2 stride-1 average of its source (ConvP::s0.shift == -1; Hin x Win = the averaged map): conv_adown.hip
 bool conv_adown_supported(int dt, const ConvP& p);
+int conv_adown_bn(const ConvP& p);                       // channel tile of the launch: 64 where that pads Cout less than 128 does
 void launch_conv_adown(int dt, const ConvP& p, hipStream_t stream);
 
 // ---- fused RepNCSP block (csp_fused.hip) ----------------------------------------------------------
@@ -72,7 +73,24 @@ struct PoolP {
   int mode;              // 0 = avg (count_include_pad, pad must be 0), 1 = max (-inf padding),
                          // 2 = avg 2x2 s1 p0 followed by max k s p (k,stride,pad describe the max stage; H,W are the raw input)
 };
-void launch_pool(int dt, const PoolP& p, hipStream_t stream);
+// The kernel a pool launch takes (conv_direct.hip).  choose_pool is pure (no HIP calls): shape, alignment and the rows-per-thread switch
+// decide; it throws on the one shape no kernel runs (mode 2 without 16-byte channel chunks or with a max stage other than k3 s2 p1).
+enum PoolKernel : int {
+  POOL_SCALAR = 0,            // pool_kernel: one thread per (pixel, channel), any channel count / alignment
+  POOL_VEC_MAX1 = 1,          // pool_vec_kernel<T, 1, 1>
+  POOL_VEC_MAX2 = 2,          // pool_vec_kernel<T, 2, 1>
+  POOL_VEC_MAX3 = 3,          // pool_vec_kernel<T, 3, 1>
+  POOL_VEC_MAX5 = 4,          // pool_vec_kernel<T, 5, 1>
+  POOL_VEC_AVG2 = 5,          // pool_vec_kernel<T, 2, 0>
+  POOL_AVG2_ROWS4 = 6,        // avg2_rows_kernel<T, 4>
+  POOL_AVG2_ROWS8 = 7,        // avg2_rows_kernel<T, 8>
+  POOL_AVGMAX = 8,            // avgmax_pool_kernel
+  POOL_AVGMAX_ROWS2 = 9,      // avgmax_rows2_kernel
+};
+PoolKernel choose_pool(int dt, const PoolP& p);
+// cc_dev_set("pool_rows"): output rows per thread of the avg 2x2 / avg-max kernels, as CLEARCAM_POOL_ROWS (8 / 4 / 1); -1 = the environment / default
+extern std::atomic<int> g_pool_rows_override;
+void launch_pool(int dt, const PoolP& p, hipStream_t stream, PoolKernel* chosen = nullptr);
 
 // CBFuse (detection/yolov9.py:230-245): out = sum_k nearest_upsample(in_k, 2^shift_k) (+ the last, unscaled input)
 struct FuseP {

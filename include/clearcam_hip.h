@@ -209,6 +209,42 @@ int cc_dev_assemble_ln(int dtype, const void* patches_dev, const float* cls_dev,
 int cc_dev_patchify(int dtype, const float* x_dev, void* out_dev, int B, int S, int patch, int Kpad, void* stream);
 int cc_dev_embed(const int32_t* tokens, int vocab, const float* table_dev, const float* pos_dev, float* out_dev, int B, int L, int D, void* stream);
 int cc_dev_l2norm(float* x_dev, int rows, int D, float eps, void* stream);
+/* Single-launch entries of the glue-kernel tests: ONE launch of a kernel that sits between the convs, through its production launcher, on
+ * device buffers the caller crafts.  Each validates its arguments (an error, and no launch, on null pointers, non-positive sizes, a
+ * channel view outside its buffer, windows outside the input, or whatever the launcher itself refuses) and synchronises `stream`.
+ * What a launcher refuses is refused before the first HIP call.  dtype 0 / 1 / 2 = f32 / f16 / bf16.
+ *
+ * cc_dev_pool: launch_pool over channels [in_coff, in_coff + C) of a (B,H,W,in_cstride) buffer into channels [out_coff, out_coff + C)
+ * of a (B,Ho,Wo,out_cstride) one.  mode 0 = average (pad 0, windows inside the input), 1 = max with -inf padding, 2 = the 2x2 stride-1
+ * average followed by the max (k, stride, pad describe the max stage: only 3 / 2 / 1 runs).  *kernel (may be null) receives the
+ * PoolKernel that ran (csrc/kernels.h): 0 scalar, 1-4 vector max k = 1 / 2 / 3 / 5, 5 vector avg 2x2, 6 / 7 avg 2x2 with four / eight rows per
+ * thread, 8 avg-max, 9 avg-max with two rows per thread.
+ * cc_dev_pool_choice: the same arguments and the same validation, no launch and no HIP call: *kernel = what cc_dev_pool would run.
+ * cc_dev_fuse: launch_fuse (CBFuse): out = sum over the n <= 6 inputs of input i read at (ho >> shift[i], wo >> shift[i]); arrays of n
+ * entries; every pointer 16-byte aligned, C / coff / cstride whole 16-byte chunks (else refused).
+ * cc_dev_conv_src: ONE conv over the channel concat of two source views (s1 null: one source), each read as it is (shift 0), nearest-
+ * upsampled by 2^shift, or - first source alone - through its 2x2 stride-1 average (shift -1: conv_adown.hip, 16-bit storage, 3x3 stride 2,
+ * Cin a multiple of 64).  d: dtype 0 .. 3 (3 = f16 storage, split weights), H x W = the conv's logical input, Cin = s0.C + s1.C,
+ * groups 1, act 0 .. 2, no residual; w OIHW float32 and bias host arrays, packed as the detector packs them (controlled rounding: values
+ * already representable are kept; two planes for dtype 3).  choice (int[6] or null) receives ConvKernel, phase schedule, tile pixels,
+ * tile channels, simple loader, two-source eight-wave loader (csrc/conv_select.h); the averaging kernel reports CC_DEV_CONV_ADOWN,
+ * 0, 128, its channel tile (64 / 128), 0, 0.
+ * cc_dev_affine: affine_kernel (AdaFace's BatchNorm in front of a padded conv): y = x * scale[c] + shift[c] over n elements of C-channel
+ * pixels in the storage type (x may be y); scale / shift device float32[C]; C whole 16-byte chunks.
+ * cc_dev_face_pre: face_pre_kernel: (B,112,112,3) uint8 or float32 frames -> (B,112,112,cpad) storage type, channels reversed,
+ * ((v / 255) - 0.5) / 0.5, channels 3 .. cpad zero. */
+typedef struct { const void* ptr; int H, W, cstride, coff, C, shift; } cc_src_desc;
+#define CC_DEV_CONV_ADOWN 100
+int cc_dev_pool(int dtype, const void* in_dev, int in_cstride, int in_coff, void* out_dev, int out_cstride, int out_coff, int B, int H, int W,
+                int C, int Ho, int Wo, int k, int stride, int pad, int mode, int* kernel, void* stream);
+int cc_dev_pool_choice(int dtype, const void* in_dev, int in_cstride, int in_coff, void* out_dev, int out_cstride, int out_coff, int B, int H,
+                       int W, int C, int Ho, int Wo, int k, int stride, int pad, int mode, int* kernel);
+int cc_dev_fuse(int dtype, int n, const void* const* in_dev, const int* H, const int* W, const int* cstride, const int* coff, const int* shift,
+                void* out_dev, int out_cstride, int out_coff, int B, int Ho, int Wo, int C, void* stream);
+int cc_dev_conv_src(const cc_conv_desc* d, const cc_src_desc* s0, const cc_src_desc* s1, const float* w_oihw, const float* bias, void* out_dev,
+                    int* choice, void* stream);
+int cc_dev_affine(int dtype, const void* x_dev, void* y_dev, const float* scale_dev, const float* shift_dev, long long n, int C, void* stream);
+int cc_dev_face_pre(int dtype, const void* img_dev, int img_f32, void* out_dev, int B, int cpad, void* stream);
 /* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 18 ints each into `records` and sets *n to the number of records
  * the log held; records that did not fit (*n > cap) stay in the log for the next call.  A record: kernel, schedule, tile pixels, tile channels, k, stride, Ho / Wo beyond the symmetric formula,
  * act, residual (0 none / 1 storage type / 2 float32), out_f32, Cout / out_coff / out_cstride all multiples of 8, then B, H, W, Cin,
@@ -235,6 +271,8 @@ int cc_round_weights(int dtype, const float* w, int64_t cout, int64_t cin, int64
  *     slabs on a small index; rounded up to a multiple of 64.
  * key "index_i8_pass": queries per scan pass over the rows of a CC_INDEX_I8 index, 1 .. 8 (-1 = the measured default, 8), read at every
  *     search, so that the measuring tool can sweep it; scores do not depend on it.
+ * key "pool_rows": output rows per thread of the avg 2x2 / avg-max pool kernels, as CLEARCAM_POOL_ROWS (8 / 4 / 1; -1 = back to the
+ *     environment / default), read at every pool launch, so that one process can reach every row variant.
  * key "route_log": 1 = every conv / GEMM launch appends one record to a process-wide list (cc_route_log_take), 0 = off (default).
  * Plans already built keep the launches they were built with.  Not part of the drop-in surface. */
 int cc_dev_set(const char* key, int value);
