@@ -24,7 +24,7 @@ SYMBOLS = [
     "cc_face_locate", "cc_face_align",
     "cc_face_create", "cc_face_load", "cc_face_finalize", "cc_face_embed", "cc_face_destroy",
     "cc_ocsort_create", "cc_ocsort_update", "cc_ocsort_update_many", "cc_ocsort_num_tracks", "cc_ocsort_destroy",
-    "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores",
+    "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores", "cc_index_last_path",
     "cc_index_search", "cc_index_search_groups", "cc_index_add_tracked", "cc_index_search_tracks", "cc_index_rank",
     "cc_index_remove_rows", "cc_index_remove_groups", "cc_index_destroy",
 ]
@@ -168,6 +168,7 @@ def lib() -> C.CDLL:
         "cc_index_remove_groups": [vp, vp, C.c_int, i64p],
         "cc_index_size": [vp, i64p],
         "cc_index_scores": [vp, vp, C.c_int, vp, C.c_int, vp],
+        "cc_index_last_path": [vp, ip],
         "cc_index_search": [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp],
     }
     for name, args in sig.items():

@@ -40,6 +40,8 @@ struct cc_index {
   hipStream_t stream = nullptr;
   float* q_dev = nullptr; int q_cap = 0;
   uint16_t* q16 = nullptr; int q16_cap = 0;     // bf16 copy of the queries (bf16 index, many queries: one MFMA GEMM pass)
+  void* q_planes = nullptr; size_t q_planes_cap = 0;   // three bf16 planes of the queries (int8 index, a batch on the MFMA kernel: index_i8_mfma.hip)
+  int last_path = 0;                            // which kernel wrote `scores` last (cc_index_last_path): 0 scan passes, 1 the f32 / bf16 MFMA GEMM, 2 the int8 MFMA kernel
   float* scores = nullptr; size_t scores_cap = 0;
   unsigned long long* cand = nullptr; size_t cand_cap = 0;
   int* idx_dev = nullptr; float* sc_dev = nullptr; size_t out_cap = 0;
@@ -209,6 +211,11 @@ __global__ void to_bf16_kernel(const float* __restrict__ in, uint16_t* __restric
 // (steps ascending, codes ascending, then the 16-lane butterfly) and does not depend on QB: a batch scores the same however it is split.
 constexpr int kI8Pass = 8;                                        // queries per pass over int8 rows (compute_scores): the fastest of 1..8 measured
 constexpr int kI8Rows = 4;                                        // groups of four rows per wave iteration
+// The smallest batch that leaves the scan passes for the MFMA kernel (index_i8_mfma.hip) by default.  Never below 18: a batch of up to
+// 17 queries is promised bit-equal to single queries.  The sweep behind it (docs/measurement.md, "int8 rows": 1 M x 768, search(q, 100),
+// p50 in ms, forced scan / MFMA kernel): Q = 8 0.43 / 0.35, 16 0.80 / 0.38, 24 1.18 / 0.48, 32 1.56 / 0.52, 48 2.33 / 0.65, 64 3.10 / 0.82,
+// 128 6.18 / 1.54, 256 12.3 / 3.05: the MFMA kernel is never the slower one, so the threshold is the lowest the contract allows.
+constexpr int kI8MfmaFrom = 18;
 
 __device__ __forceinline__ float i8_code(unsigned w, int b) { return (float)((int)(w << (24 - 8 * b)) >> 24); }
 
@@ -826,10 +833,21 @@ void compute_scores(cc_index* h, int Q, hipStream_t s) {
     const size_t cnt = (size_t)Q * h->dim;
     hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, h->q_dev, h->q16, cnt);
     const ConvP g = gemm_params(h->q16, h->dim, Q, h->dim, h->emb, h->dim, nullptr, (int)h->n, h->scores, (int)h->n, 1, 0, nullptr, 0, 0);
-    if (conv_mfma_supported(BF16, g)) { launch_conv_mfma(BF16, g, s); return; }
+    if (conv_mfma_supported(BF16, g)) { launch_conv_mfma(BF16, g, s); h->last_path = 1; return; }
   }
+  h->last_path = 0;
   if (h->storage == CC_INDEX_I8) {
-    // int8 rows: there is no MFMA GEMM path for them, any number of queries goes through repeated scan passes.  The pass width is a
+    // A batch of at least T queries goes to the MFMA kernel of index_i8_mfma.hip: one launch, every row read from HBM once, the same
+    // exact products as the scan summed in another order (last-bit differences, like the f32 GEMM below).  T: cc_dev_set
+    // ("index_i8_mfma"), 0 = never, -1 = kI8MfmaFrom.  Rows wider than kIndexI8MfmaMaxDim stay with the scan.
+    const int key = g_index_i8_mfma.load(), T = key < 0 ? kI8MfmaFrom : key;
+    if (T > 0 && Q >= T && index_i8_mfma_supported(h->dim, (long)h->n)) {
+      ensure(&h->q_planes, &h->q_planes_cap, index_i8_mfma_plane_bytes(h->dim, Q));
+      launch_index_i8_mfma(h->emb, h->q_dev, h->q_planes, h->scores, (long)h->n, h->dim, Q, s);
+      h->last_path = 2;
+      return;
+    }
+    // Smaller batches go through repeated scan passes, bit-identical to single queries.  The pass width is a
     // measured choice (docs/measurement.md, "int8 rows"): one convert and QB fma per code keep a pass at HBM speed only while QB is
     // small.  cc_dev_set("index_i8_pass") overrides it (1..8); the LDS copy of the queries caps it at 64 KB / (dim * 4).
     int W = g_index_i8_pass.load();
@@ -863,7 +881,7 @@ void compute_scores(cc_index* h, int Q, hipStream_t s) {
   // measured on a 125 k x 768 shard: a scan pass costs ~65 us whatever its query count (1..8), the GEMM ~220 us flat up to 128 queries
   if (Q > (scan8 ? 16 : 4) && h->n % 4 == 0 && h->dim % 32 == 0) {
     const ConvP g = gemm_params(h->q_dev, h->dim, Q, h->dim, h->emb, h->dim, nullptr, (int)h->n, h->scores, (int)h->n, 1, 0, nullptr, 0, 0);
-    if (h->n < (1L << 31) && conv_mfma_supported(F32, g)) { launch_conv_mfma(F32, g, s); return; }
+    if (h->n < (1L << 31) && conv_mfma_supported(F32, g)) { launch_conv_mfma(F32, g, s); h->last_path = 1; return; }
   }
   if (scan8) {
     for (int q0 = 0; q0 < Q; q0 += 8) {
@@ -993,6 +1011,13 @@ int cc_index_size(cc_index* h, int64_t* n) {
   CC_API_END
 }
 
+int cc_index_last_path(cc_index* h, int* path) {
+  CC_API_BEGIN
+  CC_CHECK(h && path, "null argument");
+  *path = h->last_path;
+  CC_API_END
+}
+
 int cc_index_scores(cc_index* h, const float* q, int Q, float* scores, int on_device, void* stream) {
   CC_API_BEGIN
   CC_CHECK(h && q && scores && Q > 0, "bad argument");
@@ -1008,7 +1033,7 @@ int cc_index_scores(cc_index* h, const float* q, int Q, float* scores, int on_de
 
 }  // extern "C"
 
-namespace cc { std::atomic<int> g_index_slab_rows{-1}; std::atomic<int> g_index_i8_pass{-1}; }
+namespace cc { std::atomic<int> g_index_slab_rows{-1}; std::atomic<int> g_index_i8_pass{-1}; std::atomic<int> g_index_i8_mfma{-1}; }
 
 namespace {
 
@@ -1311,7 +1336,7 @@ void cc_index_destroy(cc_index* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
+  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
                   (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)

@@ -206,6 +206,16 @@ void order_after(hipStream_t waiter, hipStream_t signaller);
 extern std::atomic<int> g_index_slab_rows;
 // cc_dev_set("index_i8_pass"): queries per scan pass over int8 rows (index.hip, 1..8); -1 = the measured default
 extern std::atomic<int> g_index_i8_pass;
+// cc_dev_set("index_i8_mfma"): the smallest batch that takes the MFMA kernel over int8 rows (index.hip); 0 = never, -1 = the measured default
+extern std::atomic<int> g_index_i8_mfma;
+
+// ---- int8 index rows, batches of queries on the matrix cores (index_i8_mfma.hip) ----------------
+constexpr int kIndexI8MfmaMaxDim = 4096;                 // wider rows stay with the scan passes (nothing above it has been measured)
+bool index_i8_mfma_supported(int dim, long n);           // dim % 256 == 0, dim <= kIndexI8MfmaMaxDim, 1 <= n < 2^31
+size_t index_i8_mfma_plane_bytes(int dim, int Q);        // the three bf16 planes of Q queries, padded to a multiple of 16 queries
+// out[q][row] (Q, n) f32 = <decoded row, q>: emb = n int8 rows (dim codes + dim / 32 f32 scales each), q = (Q, dim) f32 on the device,
+// planes = scratch of index_i8_mfma_plane_bytes(dim, Q).  Two launches on `stream`: the plane split, then the scores.
+void launch_index_i8_mfma(const void* emb, const float* q, void* planes, float* out, long n, int dim, int Q, hipStream_t stream);
 
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;

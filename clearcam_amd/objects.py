@@ -142,7 +142,12 @@ class EmbeddingIndex:
     """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores), "bf16" (half the
     bytes per scan, scores within ~1e-3 for unit vectors) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
     bytes a row, scores within ~1e-3 as well; include/clearcam_hip.h has the rule).  `capacity` is the initial allocation; the
-    matrix grows."""
+    matrix grows.
+
+    Batches on "i8" rows: fewer than 18 queries are scored by scan passes, bit-identical to single queries; from 18 on (dim <= 4096)
+    one MFMA launch scores the whole batch, the same exact products summed in another order (last-bit differences, the same error
+    bound).  Either way a (query, row) score depends on that pair alone, equal rows tie exactly and ties break by row id.
+    `last_scores_path()` tells which kernel ran."""
 
     STORAGE = {"f32": 0, "bf16": 2, "i8": 8}           # name -> the `storage` argument of cc_index_create_ex
 
@@ -225,6 +230,13 @@ class EmbeddingIndex:
         if len(self):
             _lib.check(_lib.lib().cc_index_scores(self._h, _lib.ptr(qa), qa.shape[0], _lib.ptr(out), 0, None))
         return out
+
+    def last_scores_path(self) -> int:
+        """Which kernel produced the scores of the last scoring call (scores / search* / rank) on this index: 0 scan passes,
+        1 the f32 / bf16 MFMA GEMM, 2 the int8 MFMA kernel (cc_index_last_path)."""
+        p = C.c_int()
+        _lib.check(_lib.lib().cc_index_last_path(self._h, C.byref(p)))
+        return p.value
 
     def search(self, q, k: int, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
         """(Q,dim) queries -> (idx (Q,k) int32, score (Q,k) f32), descending, ties by lower row id; -1/-inf past N.

@@ -7,7 +7,9 @@ One process, N x 768 unit rows (default 1 M) filled on the device, the same rows
   effective GB/s of the Q = 1 search from the real row bytes (the select is inside that time);
   max and rms of |score - score_f32| over 8 queries and the top-100 overlap with the f32 index.
 For i8 also the pass-width sweep: search(q, 100) with Q = 8 and 64 at cc_dev_set("index_i8_pass") = 1 .. 8 (what compute_scores'
-default was chosen from).  One JSON line per storage."""
+default was chosen from) and the batch sweep: search(q, 100) for Q = 8 .. 256 with cc_dev_set("index_i8_mfma") at 0 (scan passes only)
+and at 1 (the MFMA kernel of index_i8_mfma.hip), three repetitions each, from which compute_scores' threshold was chosen; bf16 rows
+get the same Q column for comparison.  One JSON line per storage."""
 import argparse
 import json
 import os
@@ -23,6 +25,7 @@ from clearcam_amd import _lib
 from clearcam_amd.objects import EmbeddingIndex
 
 DIM = 768
+BATCHES = (8, 16, 24, 32, 48, 64, 128, 256)
 ROW_BYTES = {"f32": DIM * 4, "bf16": DIM * 2, "i8": DIM + DIM // 8}
 
 
@@ -54,6 +57,8 @@ def main():
     q0 = unit(torch.randn(DIM, generator=gen, device="cuda"))
     queries = unit(q0 + 0.2 * torch.randn((64, DIM), generator=gen, device="cuda") / DIM ** 0.5).cpu().numpy()
     E = unit(torch.randn((n, DIM), generator=gen, device="cuda"))
+    more = unit(q0 + 0.2 * torch.randn((BATCHES[-1] - 64, DIM), generator=gen, device="cuda") / DIM ** 0.5).cpu().numpy()
+    queries = np.concatenate([queries, more])                      # the first 64 are those of the earlier columns
     rng = np.random.default_rng(1)
     slots = rng.integers(0, max(n // 20, 1), n).astype(np.int32)
     groups = rng.integers(0, 20, n).astype(np.int32)
@@ -77,12 +82,25 @@ def main():
             res["score_err_rms"] = float(np.sqrt((err ** 2).mean()))
             res["top100_overlap_min_mean"] = [min(len(set(x) & set(y)) for x, y in zip(top, ref_top)),
                                               float(np.mean([len(set(x) & set(y)) for x, y in zip(top, ref_top)]))]
+        def batch_column():
+            return {f"q{Q}": [round(p50(lambda: ix.search(queries[:Q], 100), a.calls, a.warmup), 4) for _ in range(a.reps)] for Q in BATCHES}
+
+        if storage == "bf16":
+            res["batch_sweep_p50_ms"] = batch_column()
         if storage == "i8":
+            res["batch_sweep_p50_ms"] = {}
+            for key, name in ((0, "scan"), (1, "mfma")):
+                _lib.check(_lib.lib().cc_dev_set(b"index_i8_mfma", key))
+                res["batch_sweep_p50_ms"][name] = batch_column()
+                assert ix.last_scores_path() == (2 if key else 0)
+            _lib.check(_lib.lib().cc_dev_set(b"index_i8_mfma", -1))
             sweep = {}
+            _lib.check(_lib.lib().cc_dev_set(b"index_i8_mfma", 0))      # the pass width is a property of the scan passes
             for w in range(1, 9):
                 _lib.check(_lib.lib().cc_dev_set(b"index_i8_pass", w))
                 sweep[str(w)] = {f"q{Q}": round(p50(lambda: ix.search(queries[:Q], 100), a.calls, a.warmup), 4) for Q in (8, 64)}
             _lib.check(_lib.lib().cc_dev_set(b"index_i8_pass", -1))
+            _lib.check(_lib.lib().cc_dev_set(b"index_i8_mfma", -1))
             res["pass_width_sweep_p50_ms"] = sweep
         print(json.dumps(res), flush=True)
         ix.close()
