@@ -16,8 +16,10 @@
 //     U   second 3x3 + a (inner pixels), aliasing X behind T
 // The recompute on the halo is 14 % of the block's MACs (cv1 on 240 instead of 128 pixels, the first 3x3 on 180).
 // Every intermediate is rounded to the storage type exactly where the layer-at-a-time path stores it and the K order of every
-// accumulation is the same, so the result is bit-identical to the four launches it replaces
-// (tests/test_gpu_yolo.py::test_fused_csp_equals_unfused).
+// accumulation is the same, so the result is bit-identical to the four launches it replaces: tests/test_gpu_fused_kernels.py holds
+// every dbg dump and the output of one launch (cc_dev_csp, dev_fused.hip) to exactly that, each stage to float64 from the stage before
+// it, and both variants below and csp_tile.hip to each other, at shapes from one ragged tile to more tiles than blocks;
+// tests/test_gpu_yolo.py::test_fused_csp_equals_unfused compares the whole detectors.
 //
 // Work split: stage 1 gives wave w patch-pixel fragments w and w+8 (all 2*HID channels); stage 2 gives (pixel group, channel half);
 // from stage 3 on a wave OWNS one 16-pixel output row with all its channels, so stage 4 and the store epilogue (staged through the
@@ -196,7 +198,8 @@ __global__ __launch_bounds__(512, 2) void csp_fused_kernel(const CspP p) {
     const int ho = h0 + (q >> 4), wo = w0 + (q & 15);
     return (ho < p.H && wo < p.W) ? ((long)b * p.H + ho) * p.W + wo : -1L;
   };
-  // development: copy an intermediate (inner 8 x 16 pixels) to the output view instead of finishing the block
+  // development (CspP::dbg): copy an intermediate (inner 8 x 16 pixels: every tile together, the whole image) to the output view instead of
+  // finishing the block - stage 1: [a | b], 2: t (hid channels), 3: [u | b]
   auto dump = [&](int region, auto rowfn, int ch_off) {
     for (int idx = tid; idx < 128 * CPA; idx += 512) {
       const int q = idx / CPA, ch = idx - q * CPA, row = rowfn(q);
@@ -436,7 +439,29 @@ template <class T, int HID, bool RES, int SPLIT = 0> static void launch_csp(cons
   hipLaunchKernelGGL((csp_fused_kernel<T, HID, RES, SPLIT>), dim3(grid), dim3(512), lds, stream, p);
 }
 
-void launch_csp_fused(int dt, const CspP& p0, hipStream_t stream) {
+// cc_dev_set("csp_tile"): -1 = CLEARCAM_CSP_TILE / the default (1)
+std::atomic<int> g_csp_tile_override{-1};
+// CLEARCAM_CSP_TILE=0 keeps the round-2 kernel at hidden width 32 (A/B, tools/dev), =2 takes the round-6 kernel at every batch size
+// (tests: small batches, ragged tiles); the environment is read once per process, the override at every launch
+int csp_tile_mode() {
+  const int ov = g_csp_tile_override.load();
+  if (ov >= 0) return ov;
+  static const int tile_mode = [] { const char* e = getenv("CLEARCAM_CSP_TILE"); return e ? atoi(e) : 1; }();
+  return tile_mode;
+}
+
+// Pure (no HIP call): csp_tile.hip from one round of its 16 x 32 tiles on (256 tiles: B >= 6 at 160 x 160; measured a tie from 200 tiles
+// and 1.6 % ahead at 400, profiles/r06n_csp_tile_threshold.txt): below that (a single frame: 50 tiles, +0.04 ms) this file's 128-pixel
+// tiles spread over more CUs.  Both are bit-identical to the four launches they replace, so the choice may depend on the batch size.
+CspKernel choose_csp(int dt, int hid, int split, int B, int H, int W, int stream, int dbg, int tile_mode) {
+  const bool tile_on = tile_mode != 0;
+  const long tiles32 = (long)B * ((H + 15) / 16) * ((W + 31) / 32);
+  if (tile_on && !stream && !dbg && (tiles32 >= 256 || tile_mode == 2) && csp_tile_supported(dt, hid, split)) return CSP_TILE;
+  // 56 KB of weights stay in LDS; 208 KB (hidden 64) cannot, and two weight planes (72 KB at hidden 32) stream as well
+  return hid == 32 && !stream && split == 0 ? CSP_FUSED_RESIDENT : CSP_FUSED_STREAMED;
+}
+
+void launch_csp_fused(int dt, const CspP& p0, hipStream_t stream, CspKernel* chosen) {
   CC_CHECK(csp_fused_supported(dt, p0.hid, p0.split), "fused RepNCSP: 16-bit storage (split weights: f16) and hidden width 32 or 64 only");
   CC_CHECK(p0.x_cstride % 8 == 0 && p0.x_coff % 8 == 0 && p0.out_cstride % 8 == 0 && p0.out_coff % 8 == 0 && (((uintptr_t)p0.x | (uintptr_t)p0.out) & 15) == 0,
            "fused RepNCSP: views must be 16-byte aligned");
@@ -444,20 +469,14 @@ void launch_csp_fused(int dt, const CspP& p0, hipStream_t stream) {
   const int s1 = p0.split != 0, s3 = p0.split == 1;
   CC_CHECK(p0.kw12 % 64 == 0 && p0.kw3 % 64 == 0 && p0.kwr % 64 == 0 && p0.kwb % 64 == 0 && p0.kwr >= 9 * p0.hid * (1 + s3) && p0.kwb >= 9 * p0.hid * (1 + s3) &&
            p0.kw12 >= 2 * p0.hid * (1 + s1) && p0.kw3 >= 2 * p0.hid * (1 + s1), "fused RepNCSP: weight rows must cover whole K slabs");
-  // CLEARCAM_CSP_TILE=0 keeps the round-2 kernel at hidden width 32 (A/B, tools/dev), =2 takes the round-6 kernel at every batch size
-  // (tests: small batches, ragged tiles); read once per process
-  static const int tile_mode = [] { const char* e = getenv("CLEARCAM_CSP_TILE"); return e ? atoi(e) : 1; }();
-  const bool tile_on = tile_mode != 0;
-  // ... from one round of its 16 x 32 tiles on (256 tiles: B >= 6 at 160 x 160; measured a tie from 200 tiles and 1.6 % ahead at 400,
-  // profiles/r06n_csp_tile_threshold.txt): below that (a single frame: 50 tiles, +0.04 ms) this file's 128-pixel tiles spread over more CUs.
-  // Both are bit-identical to the four launches they replace, so the choice may depend on the batch size.
-  const long tiles32 = (long)p0.B * ((p0.H + 15) / 16) * ((p0.W + 31) / 32);
-  if (tile_on && !p0.stream && !p0.dbg && (tiles32 >= 256 || tile_mode == 2) && csp_tile_supported(dt, p0.hid, p0.split)) { launch_csp_tile(dt, p0, stream); return; }
+  const CspKernel kernel = choose_csp(dt, p0.hid, p0.split, p0.B, p0.H, p0.W, p0.stream, p0.dbg, csp_tile_mode());
+  if (chosen) *chosen = kernel;
+  if (kernel == CSP_TILE) { launch_csp_tile(dt, p0, stream); return; }
   CspP p = p0;
   p.tx = (p.W + 15) / 16; p.tiles = ((p.H + 7) / 8) * p.tx;
   p.inv_tiles = 1.0f / (float)p.tiles; p.inv_tx = 1.0f / (float)p.tx;
   CC_CHECK((long)p.B * p.tiles < (1L << 22), "fused RepNCSP: too many tiles");
-  const bool res = p.hid == 32 && !p.stream;                        // 56 KB of weights stay in LDS; 208 KB (hidden 64) cannot
+  const bool res = kernel == CSP_FUSED_RESIDENT;
   if (p.split == 1) {                                               // two weight planes: streamed at both widths
     if (p.hid == 64) launch_csp<f16_t, 64, false, 1>(p, stream); else launch_csp<f16_t, 32, false, 1>(p, stream);
   } else if (p.split == 2) {                                        // ... in the 1x1 convs only (72 KB of weights at hidden 32: streamed as well)

@@ -27,7 +27,8 @@
 // against 0.22 / 0.26; 0.19 / 0.25 even with the weight stream switched off: nine barriers per 256-pixel tile, waves parked 44-63 %,
 // profiles/r06e_*) - removed; csp_fused.hip keeps hidden width 64.
 // K order of every accumulation (tap, plane, 32-channel step) and the rounding points are those of the four launches it replaces:
-// bit-identical (tests/test_gpu_yolo.py::test_fused_csp_equals_unfused).
+// bit-identical (one launch against those four launches and against csp_fused.hip's two variants: tests/test_gpu_fused_kernels.py; whole
+// detectors: tests/test_gpu_yolo.py::test_fused_csp_equals_unfused).
 #include <utility>
 #include "conv_tile.h"
 

@@ -74,6 +74,7 @@ int cc_dev_set(const char* key, int value) {
   else if (std::string(key) == "index_i8_pass") cc::g_index_i8_pass = value;
   else if (std::string(key) == "index_i8_mfma") cc::g_index_i8_mfma = value;
   else if (std::string(key) == "pool_rows") cc::g_pool_rows_override = value;
+  else if (std::string(key) == "csp_tile") cc::g_csp_tile_override = value;
   else if (std::string(key) == "route_log") cc::g_route_log = value ? 1 : 0;
   else throw cc::Error(-22, std::string("cc_dev_set: unknown key ") + key);
   CC_API_END

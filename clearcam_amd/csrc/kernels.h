@@ -53,7 +53,15 @@ struct CspP {
   int stream;                                    // 1: take the weight-streaming one-tile-per-block variant even where the weights fit in LDS
 };
 bool csp_fused_supported(int dt, int hid, int split = 0);
-void launch_csp_fused(int dt, const CspP& p, hipStream_t stream);
+// The kernel a fused RepNCSP launch takes.  choose_csp is pure (no HIP call): csp_tile.hip from 256 of its 16 x 32 tiles on (tile_mode 1),
+// at every size (2) or never (0), and only where it can run (hidden width 32, split 0 / 2, no dbg, no stream); else csp_fused_kernel,
+// weights resident at hidden width 32 with one plane, streamed otherwise.
+enum CspKernel : int { CSP_FUSED_RESIDENT = 0, CSP_FUSED_STREAMED = 1, CSP_TILE = 2 };
+CspKernel choose_csp(int dt, int hid, int split, int B, int H, int W, int stream, int dbg, int tile_mode);
+// cc_dev_set("csp_tile"): the tile mode, as CLEARCAM_CSP_TILE (0 / 1 / 2); -1 = the environment / default.  csp_tile_mode() is what a launch reads.
+extern std::atomic<int> g_csp_tile_override;
+int csp_tile_mode();
+void launch_csp_fused(int dt, const CspP& p, hipStream_t stream, CspKernel* chosen = nullptr);
 
 // ---- calibration-aware rounding of the 1x1 convs (calibrate.hip, C-ABI dtype "f16c") -----------------------------------------------
 // S pixel rows (indices rows_dev) of a 1x1 stride-1 conv's input view over f32 activations -> dense (S, Cin) f32

@@ -117,6 +117,15 @@ PackedConv pack_convs(int dt, const std::vector<const HostTensor*>& ws, const st
 // The op list of P (geometry and axis tables set) from the handle's weights, its arena packed and allocated, every pointer patched.
 void build_plan(cc_yolo* Y, Plan* P);
 // ---- yolo_run.hip ----
+// letterbox geometry, detection/yolov9.py:390-403
+struct LetterboxGeo { int nh, nw, pad_y, pad_x; };
+void letterbox_geometry(int H, int W, int res, int& nh, int& nw, int& pad_y, int& pad_x);
+extern const char* const kNot32;                         // the error text of a frame that does not letterbox to a multiple of 32
+// a ragged batch's checks and per-frame records (cc_yolo_detect_ragged, cc_dev_stem); neither makes a HIP call
+void ragged_geometry(const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B, int frame_f32, int res,
+                     std::vector<LetterboxGeo>& geo, int& Hn, int& Wn, size_t& end);
+FrameDesc frame_record(long long off, int H, int W, const LetterboxGeo& g, int Hn, int Wn, const int* xlo, const int* xhi, const float* xfr,
+                       const int* ylo, const int* yhi, const float* yfr);
 PreP plan_prep(const Plan* P);
 void launch_op(int dtype, const Plan* P, const Op& op, hipStream_t s, bool with_stem);
 Plan* get_plan(cc_yolo* Y, int B, int H, int W, int frame_f32, int slot = 0, bool ragged = false);

@@ -37,13 +37,13 @@ template <class T> static T* to_device(const std::vector<T>& v) {
 }
 
 // letterbox geometry, detection/yolov9.py:390-403 (python round = half-to-even)
-static void letterbox_geometry(int H, int W, int res, int& nh, int& nw, int& pad_y, int& pad_x) {
+void letterbox_geometry(int H, int W, int res, int& nh, int& nw, int& pad_y, int& pad_x) {
   const double r = std::min((double)res / H, (double)res / W);
   nw = round_half_even(W * r); nh = round_half_even(H * r);
   const double dw = ((res - nw) % 32) / 2.0, dh = ((res - nh) % 32) / 2.0;
   pad_x = round_half_even(dw - 0.1); pad_y = round_half_even(dh - 0.1);
 }
-static const char* kNot32 = "letterboxed frame is not a multiple of 32 (the reference graph cannot run this shape either)";
+const char* const kNot32 = "letterboxed frame is not a multiple of 32 (the reference graph cannot run this shape either)";
 
 // The letterbox of plan P as a launch's PreP; the caller adds its own frames / out fields.
 PreP plan_prep(const Plan* P) {
@@ -287,6 +287,44 @@ void sync_all(cc_yolo* h) {
   for (hipStream_t t : h->slot_stream) CC_HIP(hipStreamSynchronize(t));
 }
 
+// The checks of a ragged batch, no HIP call: every frame's letterbox geometry, the ONE network shape Hn x Wn they must share (a multiple of
+// 32) and `end`, the size of the packed buffer (the last byte any frame reaches).
+void ragged_geometry(const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B, int frame_f32, int res,
+                     std::vector<LetterboxGeo>& geo, int& Hn, int& Wn, size_t& end) {
+  const size_t es = frame_f32 ? 4 : 1;
+  geo.assign(B, LetterboxGeo{});
+  Hn = Wn = 0; end = 0;
+  for (int b = 0; b < B; ++b) {
+    const std::string who = "frame " + std::to_string(b) + " (" + std::to_string(heights[b]) + "x" + std::to_string(widths[b]) + ")";
+    if (heights[b] <= 0 || widths[b] <= 0 || offsets[b] < 0) throw cc::Error(-22, who + ": bad shape or offset");
+    if (frame_f32 && offsets[b] % 4 != 0) throw cc::Error(-22, who + ": float32 frames must start at a multiple of 4 bytes");
+    LetterboxGeo& g = geo[b];
+    letterbox_geometry(heights[b], widths[b], res, g.nh, g.nw, g.pad_y, g.pad_x);
+    const int hn = g.nh + 2 * g.pad_y, wn = g.nw + 2 * g.pad_x;
+    if (!(hn % 32 == 0 && wn % 32 == 0 && hn > 0 && wn > 0 && g.nh > 0 && g.nw > 0)) throw cc::Error(-22, who + ": " + kNot32);
+    if (b == 0) { Hn = hn; Wn = wn; }
+    else if (hn != Hn || wn != Wn)
+      throw cc::Error(-22, who + " letterboxes to " + std::to_string(hn) + "x" + std::to_string(wn) + " but frame 0 (" + std::to_string(heights[0]) + "x" +
+                               std::to_string(widths[0]) + ") to " + std::to_string(Hn) + "x" + std::to_string(Wn) +
+                               ": the frames of one ragged batch must share one network shape (group them with cc_letterbox_geometry)");
+    end = std::max(end, (size_t)offsets[b] + (size_t)heights[b] * widths[b] * 3 * es);
+  }
+}
+
+// One frame's record of a ragged batch: its place in the packed buffer, its geometry, its six axis tables (device) and scale_boxes.
+FrameDesc frame_record(long long off, int H, int W, const LetterboxGeo& g, int Hn, int Wn, const int* xlo, const int* xhi, const float* xfr,
+                       const int* ylo, const int* yhi, const float* yfr) {
+  FrameDesc d{};
+  d.off = off; d.H = H; d.W = W; d.nh = g.nh; d.nw = g.nw; d.pad_y = g.pad_y; d.pad_x = g.pad_x;
+  d.xlo = xlo; d.xhi = xhi; d.xfr = xfr; d.ylo = ylo; d.yhi = yhi; d.yfr = yfr;
+  // scale_boxes exactly as the uniform plan's NMS launch gets it (Builder::head_finish): double arithmetic, then one cast to float
+  const double gain = std::min((double)Hn / H, (double)Wn / W);
+  d.gain = (float)gain;
+  d.fpad_x = (float)((Wn - W * gain) / 2); d.fpad_y = (float)((Hn - H * gain) / 2);
+  d.src_w = (float)W; d.src_h = (float)H;
+  return d;
+}
+
 // The frame's tables for one axis, from the handle's cache (built and uploaded the first time a size is seen).
 static cc_yolo::AxisTab& axis_tab(cc_yolo* h, int n_in, int n_out) {
   auto it = h->axis_tabs.find({n_in, n_out});
@@ -309,26 +347,10 @@ constexpr size_t kMaxAxisTabs = 256;
 static Plan* ragged_prepare(cc_yolo* h, const void* pixels, const int64_t* offsets, const int32_t* heights, const int32_t* widths, int B,
                             int frame_f32, int slot, size_t* bytes) {
   CC_CHECK(pixels && offsets && heights && widths && B > 0, "null argument / empty batch");
-  const size_t es = frame_f32 ? 4 : 1;
-  struct Geo { int nh, nw, pad_y, pad_x; };
-  std::vector<Geo> geo(B);
+  std::vector<LetterboxGeo> geo;
   int Hn = 0, Wn = 0;
   size_t end = 0;
-  for (int b = 0; b < B; ++b) {
-    const std::string who = "frame " + std::to_string(b) + " (" + std::to_string(heights[b]) + "x" + std::to_string(widths[b]) + ")";
-    if (heights[b] <= 0 || widths[b] <= 0 || offsets[b] < 0) throw cc::Error(-22, who + ": bad shape or offset");
-    if (frame_f32 && offsets[b] % 4 != 0) throw cc::Error(-22, who + ": float32 frames must start at a multiple of 4 bytes");
-    Geo& g = geo[b];
-    letterbox_geometry(heights[b], widths[b], h->res, g.nh, g.nw, g.pad_y, g.pad_x);
-    const int hn = g.nh + 2 * g.pad_y, wn = g.nw + 2 * g.pad_x;
-    if (!(hn % 32 == 0 && wn % 32 == 0 && hn > 0 && wn > 0 && g.nh > 0 && g.nw > 0)) throw cc::Error(-22, who + ": " + kNot32);
-    if (b == 0) { Hn = hn; Wn = wn; }
-    else if (hn != Hn || wn != Wn)
-      throw cc::Error(-22, who + " letterboxes to " + std::to_string(hn) + "x" + std::to_string(wn) + " but frame 0 (" + std::to_string(heights[0]) + "x" +
-                               std::to_string(widths[0]) + ") to " + std::to_string(Hn) + "x" + std::to_string(Wn) +
-                               ": the frames of one ragged batch must share one network shape (group them with cc_letterbox_geometry)");
-    end = std::max(end, (size_t)offsets[b] + (size_t)heights[b] * widths[b] * 3 * es);
-  }
+  ragged_geometry(offsets, heights, widths, B, frame_f32, h->res, geo, Hn, Wn, end);
   Plan* P = get_plan(h, B, Hn, Wn, frame_f32 ? 1 : 0, slot, true);
   // the pinned records may still be the source of the previous upload on this plan (see Plan): wait for that copy, not for the batch
   if (P->desc_pending) { CC_HIP(hipEventSynchronize(P->desc_up)); P->desc_pending = false; }
@@ -341,17 +363,10 @@ static Plan* ragged_prepare(cc_yolo* h, const void* pixels, const int64_t* offse
   }
   bool big = false;
   for (int b = 0; b < B; ++b) {
-    const Geo& g = geo[b];
+    const LetterboxGeo& g = geo[b];
     const int H = heights[b], W = widths[b];
-    FrameDesc d{};
-    d.off = offsets[b]; d.H = H; d.W = W; d.nh = g.nh; d.nw = g.nw; d.pad_y = g.pad_y; d.pad_x = g.pad_x;
     const cc_yolo::AxisTab &tx = axis_tab(h, W, g.nw), &ty = axis_tab(h, H, g.nh);
-    d.xlo = tx.lo; d.xhi = tx.hi; d.xfr = tx.fr; d.ylo = ty.lo; d.yhi = ty.hi; d.yfr = ty.fr;
-    // scale_boxes exactly as the uniform plan's NMS launch gets it (Builder::head_finish): double arithmetic, then one cast to float
-    const double gain = std::min((double)Hn / H, (double)Wn / W);
-    d.gain = (float)gain;
-    d.fpad_x = (float)((Wn - W * gain) / 2); d.fpad_y = (float)((Hn - H * gain) / 2);
-    d.src_w = (float)W; d.src_h = (float)H;
+    const FrameDesc d = frame_record(offsets[b], H, W, g, Hn, Wn, tx.lo, tx.hi, tx.fr, ty.lo, ty.hi, ty.fr);
     P->desc_host[b] = d;
     big = big || stem_needs_big(H, W, g.nh, g.nw, frame_f32);
   }

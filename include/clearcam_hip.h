@@ -245,6 +245,34 @@ int cc_dev_conv_src(const cc_conv_desc* d, const cc_src_desc* s0, const cc_src_d
                     int* choice, void* stream);
 int cc_dev_affine(int dtype, const void* x_dev, void* y_dev, const float* scale_dev, const float* shift_dev, long long n, int C, void* stream);
 int cc_dev_face_pre(int dtype, const void* img_dev, int img_f32, void* out_dev, int B, int cpad, void* stream);
+/* Single-launch entries of the fused multi-conv kernels (csrc/dev_fused.hip): ONE launch of a kernel that keeps its intermediates on
+ * chip, through its production launcher, on device buffers the caller crafts.  Every argument is validated before the first HIP call
+ * (an error with its text behind cc_last_error, and no launch, on whatever the launcher itself would refuse); weights are host float32
+ * OIHW arrays packed as the detector packs them; `stream` is synchronised and everything packed is freed.
+ *
+ * cc_dev_csp: one RepNCSP block with one bottleneck (csrc/csp_fused.hip, csp_tile.hip) over channels [x_coff, x_coff + 2 hid) of a
+ * (B,H,W,x_cstride) buffer into channels [out_coff, out_coff + 2 hid) of a (B,H,W,out_cstride) one.  dtype 1 / 2 = f16 / bf16 storage;
+ * split 0 = one weight plane, 1 = two f16 planes in all convs, 2 = in the 1x1 convs only (f16 storage); hid 32 or 64.  w / bias: five
+ * host pointers each - cv1 (hid,2hid,1,1), cv2 (hid,2hid,1,1), m.0.cv1 folded to one 3x3 (hid,hid,3,3), m.0.cv2 (hid,hid,3,3),
+ * cv3 (2hid,2hid,1,1).  variant 0 = the launcher's own rule (CLEARCAM_CSP_TILE / cc_dev_set("csp_tile")), 1 = csp_fused_kernel as the
+ * launcher picks it by width, 2 = csp_fused_kernel with streamed weights, 3 = csp_tile_kernel (hid 32, split 0 / 2, no dbg), 4 = the
+ * four conv launches the kernel replaces, on the same packed weights.  dbg 1 .. 3: stop after that stage and leave [a | b], t (hid
+ * channels) or [u | b] in the output view (inner pixels of every tile; not with variant 3).  *choice (may be null) receives what ran:
+ * 0 csp_fused_kernel with resident weights, 1 csp_fused_kernel with streamed weights, 2 csp_tile_kernel, CC_DEV_CSP_LAYERS the four launches.
+ * cc_dev_csp_choice: the same checks on the same arguments without the buffers, no launch and no HIP call: *choice = what cc_dev_csp would run.
+ * cc_dev_stem: letterbox + first conv (3x3 stride 2, 3 -> Cout, bias, SiLU; csrc/detect.hip stem_fused_kernel) from B frames (BGR uint8,
+ * or float32 with frame_f32) at byte offsets[b] of frames_dev with heights[b] x widths[b], for a detector of resolution `res`, into
+ * channels [out_coff, out_coff + Cout) of a (B,Hn/2,Wn/2,out_cstride) buffer.  ragged 0 = the uniform launch (frames of one size, one
+ * behind the other), 1 = the launch over per-frame records; either way the frames must letterbox to ONE network shape Hn x Wn that is a
+ * multiple of 32 (else refused, as the plans refuse it).  dtype 1 / 2; split 1 = two f16 weight planes (f16 storage); w (Cout,3,3,3) and
+ * bias host arrays, Cout 16 / 32 / 64.  info (int[3] or null) receives Hn, Wn and whether the launch took the 36 KB scratch. */
+#define CC_DEV_CSP_LAYERS 3
+int cc_dev_csp(int dtype, int split, int hid, const void* x_dev, int x_cstride, int x_coff, void* out_dev, int out_cstride, int out_coff,
+               int B, int H, int W, const float* const* w, const float* const* bias, int variant, int dbg, int* choice, void* stream);
+int cc_dev_csp_choice(int dtype, int split, int hid, int B, int H, int W, int variant, int dbg, int* choice);
+int cc_dev_stem(int dtype, int split, const void* frames_dev, int frame_f32, const int64_t* offsets, const int32_t* heights, const int32_t* widths,
+                int B, int res, int ragged, const float* w_oihw, const float* bias, int Cout, void* out_dev, int out_cstride, int out_coff,
+                int* info, void* stream);
 /* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 18 ints each into `records` and sets *n to the number of records
  * the log held; records that did not fit (*n > cap) stay in the log for the next call.  A record: kernel, schedule, tile pixels, tile channels, k, stride, Ho / Wo beyond the symmetric formula,
  * act, residual (0 none / 1 storage type / 2 float32), out_f32, Cout / out_coff / out_cstride all multiples of 8, then B, H, W, Cin,
@@ -276,6 +304,8 @@ int cc_round_weights(int dtype, const float* w, int64_t cout, int64_t cin, int64
  *     with the scan whatever the key says).  cc_index_last_path tells which kernel ran.
  * key "pool_rows": output rows per thread of the avg 2x2 / avg-max pool kernels, as CLEARCAM_POOL_ROWS (8 / 4 / 1; -1 = back to the
  *     environment / default), read at every pool launch, so that one process can reach every row variant.
+ * key "csp_tile": which kernel a fused RepNCSP launch at hidden width 32 takes, as CLEARCAM_CSP_TILE (0 = csp_fused_kernel, 1 = csp_tile_kernel
+ *     from 256 of its tiles on, 2 = csp_tile_kernel at every size; -1 = back to the environment / default), read at every launch.
  * key "route_log": 1 = every conv / GEMM launch appends one record to a process-wide list (cc_route_log_take), 0 = off (default).
  * Plans already built keep the launches they were built with.  Not part of the drop-in surface. */
 int cc_dev_set(const char* key, int value);
