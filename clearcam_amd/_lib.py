@@ -28,6 +28,7 @@ SYMBOLS = [
     "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores", "cc_index_last_path",
     "cc_index_search", "cc_index_search_groups", "cc_index_add_tracked", "cc_index_search_tracks", "cc_index_rank",
     "cc_index_remove_rows", "cc_index_remove_groups", "cc_index_destroy",
+    "cc_watch_create", "cc_watch_set", "cc_watch_size", "cc_watch_scores", "cc_watch_match", "cc_watch_destroy",
 ]
 
 
@@ -177,12 +178,17 @@ def lib() -> C.CDLL:
         "cc_index_scores": [vp, vp, C.c_int, vp, C.c_int, vp],
         "cc_index_last_path": [vp, ip],
         "cc_index_search": [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp],
+        "cc_watch_create": [C.POINTER(vp), C.c_int, C.c_int],
+        "cc_watch_set": [vp, vp, vp, vp, C.c_int],
+        "cc_watch_size": [vp, ip],
+        "cc_watch_scores": [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp],
+        "cc_watch_match": [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = C.c_int
-    for name in ("cc_yolo_destroy", "cc_clip_destroy", "cc_index_destroy", "cc_ocsort_destroy", "cc_face_destroy", "cc_blaze_destroy"):
+    for name in ("cc_yolo_destroy", "cc_clip_destroy", "cc_index_destroy", "cc_ocsort_destroy", "cc_face_destroy", "cc_blaze_destroy", "cc_watch_destroy"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = None
     _lib = L

@@ -18,6 +18,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from .alerts import AlertBook, WatchList  # noqa: F401  (re-exported: the alert surface belongs to this module's ObjectFinder)
 from .arch import CLIP_L14, ClipArch
 from .helpers import Tensor, as_numpy
 from .weights import load_safetensors
@@ -521,6 +522,9 @@ class ObjectFinder:
         self._version = {"image": 0, "face": 0}
         self._stores: Dict[str, object] = {}
         self.index_storage = "f32"             # "bf16" halves the scan bytes, "i8" takes 9/8 byte per element (scores within ~1e-3 either way)
+        self.alerts = AlertBook(768)           # text-described alerts per camera (set_alerts / check_alerts)
+        self._watch: Optional[WatchList] = None
+        self._watch_version = -1               # the AlertBook.version the device table was uploaded for
 
     def init_clip(self, **clip_kwargs):
         """:199-206 (warm-up included: the first call per shape builds and captures the hipGraph)."""
@@ -881,6 +885,45 @@ class ObjectFinder:
         if getattr(self, "_attached", False):
             index, table = self._dev["store"]
             self._add_rows(index, table, e, [path])
+
+    # -- text-described alerts at ingest (clearcam.py:1289-1307) ------------------------------------------------
+    def set_alerts(self, cam_name: str, alerts) -> None:
+        """Replace one camera's alerts: an ordered mapping id -> {"desc": str, "threshold": 0.28, "desc_emb": optional,
+        "active": optional bool or callable, "last_det": optional}.  The mapping's order is the priority (the reference walks
+        `alerts.items()`).  Descriptions without an embedding are encoded in ONE text batch (the reference encodes them one by
+        one on first use, :1295-1297) and the embeddings are kept on the alert."""
+        self.alerts.set_camera(cam_name, alerts)
+        todo = self.alerts.missing()
+        if todo:
+            if self.model is None:
+                raise RuntimeError("set_alerts needs init_clip() to encode descriptions given without desc_emb")
+            tokens = np.concatenate([self.model.tokenizer.tokens_for_model(a.desc) for _, _, a in todo])
+            for (_, _, a), e in zip(todo, self.model.encode_tokens(tokens)):
+                a.desc_emb = np.array(e, np.float32)
+            self.alerts._changed()
+
+    def remove_alerts(self, cam_name: str) -> None:
+        self.alerts.remove_camera(cam_name)
+
+    def _watch_list(self) -> WatchList:
+        """The device table of the alert book, uploaded when the book changed (once per change, not per crop)."""
+        if self._watch is None:
+            self._watch = WatchList(768, device=self.model.device if self.model else 0)
+        if self._watch_version != self.alerts.version:
+            self._watch.set(*self.alerts.table())
+            self._watch_version = self.alerts.version
+        return self._watch
+
+    def check_alerts(self, paths, embs, now: Optional[float] = None) -> list:
+        """The alert walk of clearcam.py:1289-1307 for a batch of crops in arrival order: `embs` (B,768), a host array or a
+        CUDA torch tensor (what `precompute_embedding_device` left on the GPU), `paths` their crop paths (the camera is the
+        component after `cameras`).  -> [(path, cam_name, alert id, desc, score)] for the crops that fired, in crop order;
+        every fired alert gets `last_det = now` and is spent for the crops behind it.  One `WatchList.match` call: only the
+        B (alert, score) pairs leave the GPU.  Notifying and exporting the clip stay the caller's."""
+        paths = list(paths)
+        if not paths or len(self.alerts) == 0:
+            return []
+        return self.alerts.check(self._watch_list().match, embs, paths, now)
 
     # -- retention: the NVR deletes day folders (clearcam.py:1347-1381, :574-578); the matrix has to forget their crops ------------
     def _forget_dirs(self, gone) -> int:

@@ -500,6 +500,43 @@ int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* r
 int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed);
 void cc_index_destroy(cc_index* h);
 
+/* ---------------------------------------------------------------------------------------------
+ * Text-described alerts at ingest — the walk of clearcam.py:1289-1307 for a whole batch of crop embeddings in one call.
+ * Per crop the reference goes through its camera's alerts in order, skips those that fired less than 60 s ago, are inactive or
+ * have no description, and the first whose `desc_emb @ emb.T` is STRICTLY above its threshold notifies and ends the walk.  A crop
+ * fires at most one alert, and a fired alert is spent for the crops behind it in the batch (a later crop can still fire the next
+ * alert in order).  The table of descriptions stands on the device; which alerts are armed (cooldown, active, described) is the
+ * caller's byte per alert.
+ * Scores: every (crop, alert) score is the f32 dot product summed in the order of the index's scan (16 lanes a row, lane j takes
+ * elements 64 t + 4 j + {0,1,2,3} for t ascending with fma from 0, then a 16-lane xor butterfly at 8, 4, 2, 1).  It depends on
+ * that pair alone - not on B, A or the position in either table - and equals, bit for bit, the score an f32 cc_index holding the
+ * crop gives a single query with the description.  An alert that fired with score s is therefore found by searching for its
+ * description with exactly s.
+ * Handles are not thread-safe.  Errors: a negative code, text behind cc_last_error().
+ * ------------------------------------------------------------------------------------------- */
+typedef struct cc_watch cc_watch;
+/* The most alerts one table holds: cc_watch_match settles a batch on ONE wave, in which each of the 64 lanes owns one 32-bit word
+ * of the armed mask in a register (64 x 32).  A larger table is refused by cc_watch_set. */
+#define CC_WATCH_MAX_ALERTS 2048
+int cc_watch_create(cc_watch** h, int dim, int device);                          /* dim % 256 == 0 and dim <= 4096 */
+/* Replace the whole table: desc (A,dim) f32, threshold A floats, group A camera numbers in [0, 2^24), all on the HOST.  Index in
+ * the table is priority (the camera's dict order).  A == 0 clears it; A > CC_WATCH_MAX_ALERTS or a group outside the range is an
+ * error and leaves the table as it was.  Synchronous: waits for the handle's own stream; calls given another stream are the caller's to order. */
+int cc_watch_set(cc_watch* h, const float* desc, const float* threshold, const int32_t* group, int A);
+int cc_watch_size(cc_watch* h, int* A);
+/* The (B,A) scores, row-major: emb (B,dim) f32 on the host or the device (emb_on_device), scores to the host or the device
+ * (on_device).  What the reference prints as `sim =`.  Nothing is written when B or A is 0. */
+int cc_watch_scores(cc_watch* h, const float* emb, int B, int emb_on_device, float* scores, int on_device, void* stream);
+/* The walk.  crop_group: B camera numbers on the HOST; armed: A bytes on the HOST (non-zero = armed), NULL = all armed.
+ * alert[b] = the table index of the alert crop b fires, -1 where none; score[b] = that alert's score, 0 where none; both to the
+ * host or the device (on_device).  Alert a can fire for crop b when it is armed, not yet fired by an earlier crop of this batch,
+ * group[a] == crop_group[b] and score > threshold[a] in f32 (a NaN score never fires); the lowest such a fires.
+ * Two launches on `stream` (NULL: the handle's own): scores + hit bits, then the sequential rule on one wave.  B == 0 does nothing;
+ * A == 0 launches no kernel and answers -1 / 0.  Host outputs wait for the stream; device outputs wait for nothing. */
+int cc_watch_match(cc_watch* h, const float* emb, int B, int emb_on_device, const int32_t* crop_group, const uint8_t* armed,
+                   int32_t* alert, float* score, int on_device, void* stream);
+void cc_watch_destroy(cc_watch* h);
+
 #ifdef __cplusplus
 }
 #endif
