@@ -27,6 +27,7 @@ SYMBOLS = [
     "cc_ocsort_create", "cc_ocsort_update", "cc_ocsort_update_many", "cc_ocsort_num_tracks", "cc_ocsort_destroy",
     "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores", "cc_index_last_path",
     "cc_index_search", "cc_index_search_groups", "cc_index_add_tracked", "cc_index_search_tracks", "cc_index_rank",
+    "cc_index_add_described", "cc_index_row_info", "cc_index_rank_where", "cc_index_timeline",
     "cc_index_remove_rows", "cc_index_remove_groups", "cc_index_destroy",
     "cc_watch_create", "cc_watch_set", "cc_watch_size", "cc_watch_scores", "cc_watch_match", "cc_watch_destroy",
 ]
@@ -58,6 +59,14 @@ class FaceAlignRec(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
                 ("cx1", C.c_int32), ("cy1", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32),
                 ("out_w", C.c_int32), ("out_h", C.c_int32), ("rot", C.c_double * 6), ("place", C.c_double * 6)]
+
+
+ROW_NO_TS = -(1 << 31)                                # CC_ROW_NO_TS: a row without a ts
+
+
+class RowFilter(C.Structure):
+    """cc_row_filter: the row filter of cc_index_rank_where / cc_index_timeline (include/clearcam_hip.h)."""
+    _fields_ = [("use_ts", C.c_int32), ("ts_min", C.c_int32), ("ts_max", C.c_int32), ("use_cls", C.c_int32), ("cls_mask", C.c_uint64 * 4)]
 
 
 class CCError(RuntimeError):
@@ -172,6 +181,10 @@ def lib() -> C.CDLL:
         "cc_index_search_groups": [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp],
         "cc_index_search_tracks": [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp],
         "cc_index_rank": [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp],
+        "cc_index_add_described": [vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp],
+        "cc_index_row_info": [vp, C.c_int64, C.c_int64, vp, vp],
+        "cc_index_rank_where": [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter), vp, vp, vp, C.c_int, vp],
+        "cc_index_timeline": [vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter), C.c_int32, C.c_int32, C.c_int, vp, vp, C.c_int, vp],
         "cc_index_remove_rows": [vp, vp, C.c_int64, i64p],
         "cc_index_remove_groups": [vp, vp, C.c_int, i64p],
         "cc_index_size": [vp, i64p],

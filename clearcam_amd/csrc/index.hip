@@ -15,6 +15,10 @@
 //
 // cc_index_remove_rows / cc_index_remove_groups take rows out by stable compaction in place ("Removing rows"):
 // keep flags -> per-granule counts -> one-block scan -> one mover launch per slab, ordered by the stream alone.
+//
+// Every row also carries ts (seconds into the day's recording) and cls (the detector's class), the other two facts of a crop's name.
+// cc_index_rank_where tests them where the group filter is tested (row_passes, in the track reduction and in the key pass), and
+// cc_index_timeline counts the answers of a ranking into bins of their ts (timeline_kernel) instead of selecting a window.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -31,6 +35,9 @@ struct cc_index {
   float* emb = nullptr;                           // (capacity, row_bytes()) rows in the storage type
   int* grp = nullptr;                             // (capacity) group id of each row (camera/day bucket chosen by the caller); 0 by default
   int* trk = nullptr;                             // (capacity) track slot of each row: dense per distinct track id, -1 = a crop without one (the default)
+  int* ts = nullptr;                              // (capacity) seconds into the day's recording of each row; CC_ROW_NO_TS = none (the default)
+  int* cls = nullptr;                             // (capacity) detector class of each row in [0, 255]; -1 = none (the default)
+  int* attr_tmp = nullptr; size_t attr_tmp_cap = 0;   // removal: the ts and cls columns as they were, the source of the scatter
   int n_slots = 0;                                // highest slot + 1
   unsigned long long* best = nullptr; size_t best_cap = 0;   // (Q, n_slots) per-track maximum of the current track search: ordered(score) << 32 | ~row
   unsigned* first = nullptr; size_t first_cap = 0;           // (n_slots) first allowed row of each track in the current track search
@@ -374,6 +381,26 @@ __device__ __forceinline__ bool row_allowed(const int* __restrict__ grp, const u
   return g < (unsigned)n_allowed && allowed[g];
 }
 
+// cc_row_filter as the kernels take it (by value, in the kernel arguments): a null column = no filter on that attribute.
+struct RowWhere { const int* ts; const int* cls; int ts_min, ts_max; unsigned long long m0, m1, m2, m3; };
+
+// The row competes: its group is allowed, and it has the attributes the filter asks for.  The mask word is chosen by compares, not
+// by an index, so the four words stay in scalar registers.
+__device__ __forceinline__ bool row_passes(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, const RowWhere& w, long r) {
+  if (!row_allowed(grp, allowed, n_allowed, r)) return false;
+  if (w.ts) {
+    const int t = w.ts[r];
+    if (t == CC_ROW_NO_TS || t < w.ts_min || t > w.ts_max) return false;
+  }
+  if (w.cls) {
+    const unsigned c = (unsigned)w.cls[r];
+    if (c > 255u) return false;                                    // -1: no class
+    const unsigned long long m = c < 128u ? (c < 64u ? w.m0 : w.m1) : (c < 192u ? w.m2 : w.m3);
+    if (!((m >> (c & 63u)) & 1ull)) return false;
+  }
+  return true;
+}
+
 // Track search, pass 1: every allowed row with a track slot t raises best[q][t] to ordered(score) << 32 | ~row (a 64-bit integer
 // maximum: the best score, and among equal scores the lowest row, whatever the arrival order) and lowers first[t] to its row id.
 // Thousands of rows of ONE track (a parked car: one crop every 10 s all day) would send thousands of atomics to one address, so a
@@ -385,7 +412,7 @@ constexpr int kTrkRows = 2048, kTrkTab = 1024;
 
 __global__ __launch_bounds__(256) void track_reduce_kernel(const float* __restrict__ scores, long n, int T, const int* __restrict__ trk,
                                                            const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed,
-                                                           unsigned long long* __restrict__ best, unsigned* __restrict__ first) {
+                                                           const RowWhere where, unsigned long long* __restrict__ best, unsigned* __restrict__ first) {
   __shared__ int tag[kTrkTab]; __shared__ unsigned long long val[kTrkTab]; __shared__ unsigned fst[kTrkTab];
   const int q = blockIdx.y, tid = threadIdx.x;
   const bool want_first = q == 0;                                // first[] depends on the filter only: the blocks of query 0 fill it
@@ -396,7 +423,7 @@ __global__ __launch_bounds__(256) void track_reduce_kernel(const float* __restri
   unsigned long long* b = best + (size_t)q * T;
   for (long r = base + tid; r < end; r += 256) {
     const int t = trk[r];
-    if (t < 0 || t >= T || !row_allowed(grp, allowed, n_allowed, r)) continue;
+    if (t < 0 || t >= T || !row_passes(grp, allowed, n_allowed, where, r)) continue;
     const unsigned long long key = ((unsigned long long)ordered(s[r]) << 32) | (unsigned)(~(unsigned)r);
     const int h = t & (kTrkTab - 1);
     const int owner = atomicCAS(&tag[h], -1, t);
@@ -527,7 +554,7 @@ template <bool TRACKS>
 __global__ __launch_bounds__(256) void rank_keys_kernel(const float* __restrict__ scores, long n, const int* __restrict__ grp,
                                                         const unsigned char* __restrict__ allowed, int n_allowed, const int* __restrict__ trk,
                                                         const unsigned long long* __restrict__ best, const unsigned* __restrict__ first, int T,
-                                                        float min_score, unsigned* __restrict__ hi, unsigned* __restrict__ total) {
+                                                        float min_score, const RowWhere where, unsigned* __restrict__ hi, unsigned* __restrict__ total) {
   __shared__ unsigned s_cnt[4];
   const int q = blockIdx.y, tid = threadIdx.x;
   const long base = (long)blockIdx.x * kRankRows, end = min(n, base + kRankRows);
@@ -536,7 +563,7 @@ __global__ __launch_bounds__(256) void rank_keys_kernel(const float* __restrict_
   unsigned cnt = 0;
   for (long r = base + tid; r < end; r += 256) {
     unsigned u = 0;
-    if (row_allowed(grp, allowed, n_allowed, r)) {
+    if (row_passes(grp, allowed, n_allowed, where, r)) {
       if (TRACKS) {
         const int t = trk[r];
         if (t < 0) u = ordered(s[r]);
@@ -681,6 +708,42 @@ __global__ void rank_pad_kernel(int* __restrict__ idx, float* __restrict__ score
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) { idx[i] = -1; score[i] = -INFINITY; }
 }
 
+// cc_index_timeline, behind rank_keys_kernel: counts[q][bin] += the answers of the block's kRankRows rows whose time falls into the
+// bin.  hi[q][r] != 0 says that row r carries an answer; its time is the ts of the row the emit kernel would name (a track: the low
+// word of best[q][slot], its best passing crop).  bin = (ts - t0) / bin_seconds in 64 bits (t0 = -2^31 + 1, ts = 2^31 - 1 differ by
+// 2^32 - 2); a negative difference is below bin 0 and is dropped before the division, so truncation and floor agree.  The block
+// counts in an LDS table of n_bins words (dynamic: 96 bytes for a day of hours, 16 KB at the limit of 4096, which still leaves ten
+// blocks a CU) and adds its non-empty bins to global memory: integer sums, no block waits for another, no order to depend on.
+template <bool TRACKS>
+__global__ __launch_bounds__(256) void timeline_kernel(const unsigned* __restrict__ hi, long n, const int* __restrict__ trk,
+                                                       const unsigned long long* __restrict__ best, int T, const int* __restrict__ ts,
+                                                       long long t0, unsigned bin_seconds, int n_bins, unsigned* __restrict__ counts) {
+  extern __shared__ unsigned bins[];
+  const int q = blockIdx.y, tid = threadIdx.x;
+  for (int i = tid; i < n_bins; i += 256) bins[i] = 0u;
+  __syncthreads();
+  const long base = (long)blockIdx.x * kRankRows, end = min(n, base + kRankRows);
+  const unsigned* h = hi + (long)q * n;
+  for (long r = base + tid; r < end; r += 256) {
+    if (h[r] == 0u) continue;
+    long row = r;
+    if (TRACKS) {
+      const int t = trk[r];
+      if (t >= 0) row = (long)(~(unsigned)(best[(size_t)q * T + t] & 0xffffffffull));
+    }
+    if (row < 0 || row >= n) continue;                             // cannot happen behind rank_keys_kernel; keeps the load inside the column
+    const int t = ts[row];
+    if (t == CC_ROW_NO_TS) continue;
+    const long long d = (long long)t - t0;
+    if (d < 0) continue;
+    const unsigned long long b = (unsigned long long)d / bin_seconds;
+    if (b < (unsigned long long)n_bins) atomicAdd(&bins[(unsigned)b], 1u);
+  }
+  __syncthreads();
+  unsigned* c = counts + (size_t)q * n_bins;
+  for (int i = tid; i < n_bins; i += 256) { const unsigned v = bins[i]; if (v) atomicAdd(&c[i], v); }
+}
+
 // ---- removal: stable compaction in place -------------------------------------------------------------------------------------
 // Row r moves to pos(r) = the survivors before it, and pos(r) <= r.  Positions come from three passes: keep flags and survivor
 // counts per granule of kGran rows, an exclusive scan of the counts by ONE block (64-bit), and the place inside the granule from a
@@ -789,6 +852,25 @@ __global__ __launch_bounds__(256) void copy_down_kernel(const uint4* __restrict_
   }
   for (; i < n16; i += nt) dst[i] = src[i];
   for (size_t i = tid; i < (size_t)rows; i += nt) { dgrp[i] = sgrp[i]; dtrk[i] = strk[i]; }
+}
+
+// The ts and cls columns follow their rows in a pass of their own, which leaves the movers above as they are: the columns as they
+// were (sts / scls, a copy in scratch) are scattered to pos(r) = goff[granule] + the survivors before the row in its granule.  One
+// wave per granule, like keep_count_kernel.  Source and destination are different buffers, so the order of the blocks is free.
+__global__ __launch_bounds__(256) void attr_compact_kernel(const int* __restrict__ sts, const int* __restrict__ scls, int* __restrict__ dts, int* __restrict__ dcls,
+                                                           const unsigned char* __restrict__ keep, const unsigned long long* __restrict__ goff, long n) {
+  const int lane = threadIdx.x & 63;
+  const long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6), r = g * kGran + lane;
+  const bool k = r < n && keep[r] != 0;
+  const unsigned long long m = __ballot(k);
+  if (k) {
+    const long d = (long)goff[g] + __popcll(m & ((1ull << lane) - 1ull));
+    dts[d] = sts[r]; dcls[d] = scls[r];
+  }
+}
+
+__global__ void fill_i32_kernel(int* __restrict__ p, int v, size_t cnt) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
 void ensure(void** p, size_t* cap, size_t bytes) {
@@ -923,6 +1005,8 @@ int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int 
   CC_HIP(hipMalloc((void**)&x->emb, (size_t)capacity * x->row_bytes() + 256));
   CC_HIP(hipMalloc((void**)&x->grp, (size_t)capacity * 4 + 256));
   CC_HIP(hipMalloc((void**)&x->trk, (size_t)capacity * 4 + 256));
+  CC_HIP(hipMalloc((void**)&x->ts, (size_t)capacity * 4 + 256));
+  CC_HIP(hipMalloc((void**)&x->cls, (size_t)capacity * 4 + 256));
   x->stream = pool_stream_get(device);
   *h = x.release();
   CC_API_END
@@ -932,10 +1016,13 @@ int cc_index_create(cc_index** h, int dim, int64_t capacity, int device) { retur
 
 // Append n rows (f32 in; rounded to bf16 for a bf16 index, quantised for an int8 one) with their group ids (null: group 0) and track slots (null: -1, no
 // track).  The matrix grows geometrically when it is full (new allocation, device-to-device copy, swap), so callers never see a
-// capacity error.
-int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks) {
+// capacity error.  ts / cls: the two per-row attributes (null: none), which grow and move with the rows.
+int cc_index_add_described(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks,
+                           const int32_t* ts, const int32_t* cls) {
   CC_API_BEGIN
   CC_CHECK(h && (emb || n == 0) && n >= 0, "bad argument");
+  if (cls)
+    for (int64_t i = 0; i < n; ++i) CC_CHECK(cls[i] >= -1 && cls[i] <= 255, "row classes must be in [0, 255] or -1");
   int n_slots = h->n_slots;
   if (tracks)
     for (int64_t i = 0; i < n; ++i) {
@@ -948,17 +1035,19 @@ int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device
     int64_t cap = h->capacity;
     while (cap < h->n + n) cap *= 2;
     CC_CHECK((size_t)cap * h->row_bytes() < ((size_t)1 << 40), "index would exceed 1 TiB");
-    float* emb2 = nullptr; int* grp2 = nullptr; int* trk2 = nullptr;
+    float* emb2 = nullptr; int* col2[4] = {nullptr, nullptr, nullptr, nullptr};      // grp, trk, ts, cls
     CC_HIP(hipMalloc((void**)&emb2, (size_t)cap * h->row_bytes() + 256));
-    if (hipMalloc((void**)&grp2, (size_t)cap * 4 + 256) != hipSuccess || hipMalloc((void**)&trk2, (size_t)cap * 4 + 256) != hipSuccess) {
-      hipFree(emb2); if (grp2) hipFree(grp2);
-      throw cc::Error(-12, "out of device memory growing the index");
-    }
+    for (int c = 0; c < 4; ++c)
+      if (hipMalloc((void**)&col2[c], (size_t)cap * 4 + 256) != hipSuccess) {
+        hipFree(emb2);
+        for (int d = 0; d < c; ++d) hipFree(col2[d]);
+        throw cc::Error(-12, "out of device memory growing the index");
+      }
+    int** col[4] = {&h->grp, &h->trk, &h->ts, &h->cls};
     CC_HIP(hipMemcpy(emb2, h->emb, (size_t)h->n * h->row_bytes(), hipMemcpyDeviceToDevice));
-    CC_HIP(hipMemcpy(grp2, h->grp, (size_t)h->n * 4, hipMemcpyDeviceToDevice));
-    CC_HIP(hipMemcpy(trk2, h->trk, (size_t)h->n * 4, hipMemcpyDeviceToDevice));
-    hipFree(h->emb); hipFree(h->grp); hipFree(h->trk);
-    h->emb = emb2; h->grp = grp2; h->trk = trk2; h->capacity = cap;
+    for (int c = 0; c < 4; ++c) CC_HIP(hipMemcpy(col2[c], *col[c], (size_t)h->n * 4, hipMemcpyDeviceToDevice));
+    hipFree(h->emb); h->emb = emb2; h->capacity = cap;
+    for (int c = 0; c < 4; ++c) { hipFree(*col[c]); *col[c] = col2[c]; }
   }
   if (n) {
     char* dst = reinterpret_cast<char*>(h->emb) + (size_t)h->n * h->row_bytes();
@@ -983,9 +1072,32 @@ int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device
     else CC_HIP(hipMemset(h->grp + h->n, 0, (size_t)n * 4));
     if (tracks) CC_HIP(hipMemcpy(h->trk + h->n, tracks, (size_t)n * 4, hipMemcpyHostToDevice));
     else CC_HIP(hipMemset(h->trk + h->n, 0xff, (size_t)n * 4));
+    if (ts) CC_HIP(hipMemcpy(h->ts + h->n, ts, (size_t)n * 4, hipMemcpyHostToDevice));
+    else {
+      hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, h->ts + h->n, (int)CC_ROW_NO_TS, (size_t)n);
+      CC_HIP(hipGetLastError());
+      CC_HIP(hipStreamSynchronize(h->stream));
+    }
+    if (cls) CC_HIP(hipMemcpy(h->cls + h->n, cls, (size_t)n * 4, hipMemcpyHostToDevice));
+    else CC_HIP(hipMemset(h->cls + h->n, 0xff, (size_t)n * 4));
   }
   h->n += n;
   h->n_slots = n_slots;
+  CC_API_END
+}
+
+int cc_index_add_tracked(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks) {
+  return cc_index_add_described(h, emb, n, on_device, groups, tracks, nullptr, nullptr);
+}
+
+int cc_index_row_info(cc_index* h, int64_t row0, int64_t n, int32_t* ts_out, int32_t* cls_out) {
+  CC_API_BEGIN
+  CC_CHECK(h, "null index");
+  CC_CHECK(row0 >= 0 && n >= 0 && row0 <= h->n && n <= h->n - row0, "rows outside the index");
+  CC_HIP(hipSetDevice(h->device));
+  CC_HIP(hipStreamSynchronize(h->stream));
+  if (n && ts_out) CC_HIP(hipMemcpy(ts_out, h->ts + row0, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (n && cls_out) CC_HIP(hipMemcpy(cls_out, h->cls + row0, (size_t)n * 4, hipMemcpyDeviceToHost));
   CC_API_END
 }
 
@@ -1081,6 +1193,11 @@ int remove_impl(cc_index* h, bool by_rows, const uint8_t* drop, int64_t n_rows, 
   if (total == n) return 0;                          // group removal that met no row
   int64_t T = g_index_slab_rows.load();
   T = T > 0 ? (T + kGran - 1) / kGran * kGran : kSlabRows;
+  // ts / cls: the columns to scratch, then scattered by keep / goff (attr_compact_kernel); neither is touched by the movers below
+  ensure((void**)&h->attr_tmp, &h->attr_tmp_cap, (size_t)n * 8);
+  CC_HIP(hipMemcpyAsync(h->attr_tmp, h->ts, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  CC_HIP(hipMemcpyAsync(h->attr_tmp + n, h->cls, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(attr_compact_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, h->attr_tmp, h->attr_tmp + n, h->ts, h->cls, h->keep, h->goff, (long)n);
   const int64_t direct_min = std::max<int64_t>(kGran, T / 4);
   const size_t rb = h->row_bytes();
   const int chunks = (int)(rb / 16);                 // dim % 4 == 0 (f32) / dim % 256 == 0 (bf16; int8: dim + dim / 8 bytes, a multiple of 32): whole 16-byte pieces
@@ -1172,7 +1289,7 @@ int search(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, in
       ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * h->n * 4);
       CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
       hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((h->n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, (long)h->n, T, h->trk, h->grp,
-                         allowed_dev, h->allowed_cap, h->best, h->first);
+                         allowed_dev, h->allowed_cap, RowWhere{}, h->best, h->first);
       hipLaunchKernelGGL(topk_stage1<true>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
                          h->trk, h->best, h->first, T, h->key_hi);
     } else {
@@ -1212,10 +1329,46 @@ const unsigned char* upload_allowed(cc_index* h, const uint8_t* allowed, int n_g
   return h->allowed;
 }
 
-// cc_index_rank.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
+// The caller's row filter, checked, as the kernels take it.
+RowWhere make_where(const cc_index* h, const cc_row_filter* where) {
+  RowWhere w{};
+  if (!where) return w;
+  if (where->use_ts) {
+    CC_CHECK(where->ts_min <= where->ts_max, "empty time window (ts_min > ts_max)");
+    w.ts = h->ts; w.ts_min = where->ts_min; w.ts_max = where->ts_max;
+  }
+  if (where->use_cls) {
+    CC_CHECK((where->cls_mask[0] | where->cls_mask[1] | where->cls_mask[2] | where->cls_mask[3]) != 0, "empty class set (all-zero mask)");
+    w.cls = h->cls; w.m0 = where->cls_mask[0]; w.m1 = where->cls_mask[1]; w.m2 = where->cls_mask[2]; w.m3 = where->cls_mask[3];
+  }
+  return w;
+}
+
+// What cc_index_rank_where and cc_index_timeline share behind the scan: (track reduction,) keys + totals.  n > 0.
+void rank_keys(cc_index* h, int Q, bool tracks, float min_score, const unsigned char* allowed_dev, const RowWhere& w, unsigned* tot_dev, hipStream_t s) {
+  const long n = (long)h->n;
+  ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * n * 4);
+  const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
+  const int T = std::max(h->n_slots, 1);
+  if (tracks) {
+    ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
+    ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
+    CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
+    CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
+    hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, n, T, h->trk, h->grp,
+                       allowed_dev, h->allowed_cap, w, h->best, h->first);
+    hipLaunchKernelGGL(rank_keys_kernel<true>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, h->trk, h->best, h->first, T,
+                       min_score, w, h->key_hi, tot_dev);
+  } else {
+    hipLaunchKernelGGL(rank_keys_kernel<false>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, nullptr, nullptr, nullptr, 0,
+                       min_score, w, h->key_hi, tot_dev);
+  }
+}
+
+// cc_index_rank / cc_index_rank_where.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
 // init, eight times (histogram, pick), collect, emit.  Answers past the last row the index could give are padded by one fill.
 int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
-         int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
+         const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
   CC_API_BEGIN
   CC_CHECK(h && q && idx && score, "null argument");
   CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
@@ -1226,6 +1379,7 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
   CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");       // keys hold ~row and ~(n + row) in 32 bits
   const bool tracks = (flags & CC_RANK_TRACKS) != 0;
+  const RowWhere w = make_where(h, where);
   CC_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const long n = (long)h->n;
@@ -1261,22 +1415,9 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
     const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
     upload_queries(h, q, Q, on_device, s);
     compute_scores(h, Q, s);
-    ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * n * 4);
+    rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
     const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
     const int T = std::max(h->n_slots, 1);
-    if (tracks) {
-      ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
-      ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
-      CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
-      CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
-      hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, n, T, h->trk, h->grp,
-                         allowed_dev, h->allowed_cap, h->best, h->first);
-      hipLaunchKernelGGL(rank_keys_kernel<true>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, h->trk, h->best, h->first, T,
-                         min_score, h->key_hi, tot_dev);
-    } else {
-      hipLaunchKernelGGL(rank_keys_kernel<false>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, nullptr, nullptr, nullptr, 0,
-                         min_score, h->key_hi, tot_dev);
-    }
     const int* trk = tracks ? h->trk : nullptr;
     const int64_t nwin = (avail + kMaxK - 1) / kMaxK;
     if (nwin) ensure((void**)&h->cand, &h->cand_cap, (size_t)Q * kRankSel * kMaxK * 8);
@@ -1305,6 +1446,51 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   CC_API_END
 }
 
+// cc_index_timeline.  Launches on one stream: scan, (track reduction,) keys + totals as in rank(), then the histogram kernel.
+int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+             int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && q && counts, "null argument");
+  CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
+  CC_CHECK(min_score == min_score, "min_score is NaN");
+  CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
+  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  CC_CHECK(bin_seconds >= 1, "bin_seconds must be at least 1");
+  CC_CHECK(n_bins >= 1 && n_bins <= 4096, "n_bins must be in [1, 4096]");
+  CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");
+  const bool tracks = (flags & CC_RANK_TRACKS) != 0;
+  const RowWhere w = make_where(h, where);
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const long n = (long)h->n;
+  const size_t qbytes = ((size_t)Q * h->dim * 4 + 255) & ~(size_t)255, cbytes = (size_t)Q * n_bins * 4;
+  ensure_pinned(h, qbytes + (size_t)Q * 4);
+  unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes);
+  ensure((void**)&h->rank_ws, &h->rank_ws_cap, (size_t)Q * 4 + cbytes);     // per query the total, then (host caller) the bins
+  unsigned* tot_dev = reinterpret_cast<unsigned*>(h->rank_ws);
+  unsigned* cnt_dev = on_device ? counts : tot_dev + Q;
+  CC_HIP(hipMemsetAsync(tot_dev, 0, (size_t)Q * 4, s));
+  CC_HIP(hipMemsetAsync(cnt_dev, 0, cbytes, s));
+  if (n > 0) {
+    const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
+    upload_queries(h, q, Q, on_device, s);
+    compute_scores(h, Q, s);
+    rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
+    const dim3 grid((unsigned)((n + kRankRows - 1) / kRankRows), Q);
+    const size_t lds = (size_t)n_bins * 4;
+    if (tracks) hipLaunchKernelGGL(timeline_kernel<true>, grid, dim3(256), lds, s, h->key_hi, n, h->trk, h->best, std::max(h->n_slots, 1), h->ts,
+                                   (long long)t0, (unsigned)bin_seconds, n_bins, cnt_dev);
+    else hipLaunchKernelGGL(timeline_kernel<false>, grid, dim3(256), lds, s, h->key_hi, n, nullptr, nullptr, 0, h->ts,
+                            (long long)t0, (unsigned)bin_seconds, n_bins, cnt_dev);
+  }
+  CC_HIP(hipGetLastError());
+  if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+  if (!on_device) CC_HIP(hipMemcpyAsync(counts, cnt_dev, cbytes, hipMemcpyDeviceToHost, s));
+  if (!on_device || total) CC_HIP(hipStreamSynchronize(s));
+  if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
+  CC_API_END
+}
+
 }  // namespace
 
 extern "C" {
@@ -1325,7 +1511,17 @@ int cc_index_search(cc_index* h, const float* q, int Q, int k, int32_t* idx, flo
 
 int cc_index_rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
                   int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
-  return rank(h, q, Q, start, count, min_score, flags, allowed, n_groups, idx, score, total, on_device, stream);
+  return rank(h, q, Q, start, count, min_score, flags, allowed, n_groups, nullptr, idx, score, total, on_device, stream);
+}
+
+int cc_index_rank_where(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
+                        const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
+  return rank(h, q, Q, start, count, min_score, flags, allowed, n_groups, where, idx, score, total, on_device, stream);
+}
+
+int cc_index_timeline(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                      int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int on_device, void* stream) {
+  return timeline(h, q, Q, min_score, flags, allowed, n_groups, where, t0, bin_seconds, n_bins, counts, total, on_device, stream);
 }
 
 int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
@@ -1336,7 +1532,7 @@ void cc_index_destroy(cc_index* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
+  for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
                   (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)

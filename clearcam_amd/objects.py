@@ -139,6 +139,32 @@ class OpenCLIP:
             pass
 
 
+def row_filter(ts_range=None, classes=None) -> Optional["_lib.RowFilter"]:
+    """The row filter of `rank` / `rank_device` / `timeline` (cc_row_filter), or None when neither argument is given.
+    ts_range: (first, last) seconds, inclusive at both ends, either may be None for "open"; classes: the class ids that
+    pass, each in [0, 255].  A row without the attribute never passes a filter on it.  An empty window (first > last, or
+    outside int32) and an empty class set are errors: they could only answer nothing."""
+    if ts_range is None and classes is None:
+        return None
+    f = _lib.RowFilter()
+    if ts_range is not None:
+        lo, hi = ts_range
+        lo, hi = (-(1 << 31) if lo is None else int(lo)), ((1 << 31) - 1 if hi is None else int(hi))
+        if lo > hi or lo >= 1 << 31 or hi < -(1 << 31):
+            raise ValueError(f"ts_range ({lo}, {hi}) is empty")
+        f.use_ts, f.ts_min, f.ts_max = 1, max(lo, -(1 << 31)), min(hi, (1 << 31) - 1)
+    if classes is not None:
+        ids = sorted({int(c) for c in np.asarray(classes).reshape(-1).tolist()})
+        if not ids:
+            raise ValueError("classes is empty")
+        if ids[0] < 0 or ids[-1] > 255:
+            raise ValueError("classes: ids in [0, 255]")
+        f.use_cls = 1
+        for c in ids:
+            f.cls_mask[c >> 6] |= 1 << (c & 63)
+    return f
+
+
 class EmbeddingIndex:
     """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores), "bf16" (half the
     bytes per scan, scores within ~1e-3 for unit vectors) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
@@ -168,10 +194,14 @@ class EmbeddingIndex:
         _lib.check(_lib.lib().cc_index_size(self._h, C.byref(n)))
         return n.value
 
-    def add(self, emb, groups=None, tracks=None) -> None:
+    row_filter = staticmethod(row_filter)
+
+    def add(self, emb, groups=None, tracks=None, ts=None, classes=None) -> None:
         """Append rows: (n,dim) / (n,1,dim) / (dim,) float32, host array or CUDA torch tensor.  Rows of any other width are
         rejected (a 512-d face row must never land in the 768-d crop matrix).  groups: one int per row (search filter unit).
-        tracks: one slot per row, a dense number per distinct track id or -1 for a crop without one (`search_tracks`)."""
+        tracks: one slot per row, a dense number per distinct track id or -1 for a crop without one (`search_tracks`).
+        ts: one int32 per row, the seconds into the day's recording, _lib.ROW_NO_TS for a row without; classes: one detector
+        class in [0, 255] per row, -1 for a row without.  Not given: no row has the attribute (it then passes no filter on it)."""
         on_dev = bool(getattr(emb, "is_cuda", False))
         if on_dev:
             a = emb.contiguous().float()
@@ -193,8 +223,26 @@ class EmbeddingIndex:
             t = np.ascontiguousarray(np.asarray(tracks, np.int32).reshape(-1))
             if t.shape[0] != a.shape[0] or (t.size and (t.min() < -1 or t.max() >= 1 << 24)):
                 raise ValueError("tracks: one slot in [0, 2^24) or -1 per row")
-        _lib.check(_lib.lib().cc_index_add_tracked(self._h, _lib.ptr(a), a.shape[0], int(on_dev), _lib.ptr(g) if g is not None else None,
-                                                   _lib.ptr(t) if t is not None else None))
+        s = c = None
+        if ts is not None:
+            s64 = np.asarray(ts, np.int64).reshape(-1)
+            if s64.shape[0] != a.shape[0] or (s64.size and (s64.min() < -(1 << 31) or s64.max() >= 1 << 31)):
+                raise ValueError("ts: one int32 per row")
+            s = np.ascontiguousarray(s64.astype(np.int32))
+        if classes is not None:
+            c = np.ascontiguousarray(np.asarray(classes, np.int32).reshape(-1))
+            if c.shape[0] != a.shape[0] or (c.size and (c.min() < -1 or c.max() > 255)):
+                raise ValueError("classes: one id in [0, 255] or -1 per row")
+        _lib.check(_lib.lib().cc_index_add_described(self._h, _lib.ptr(a), a.shape[0], int(on_dev), _lib.ptr(g) if g is not None else None,
+                                                     _lib.ptr(t) if t is not None else None, _lib.ptr(s) if s is not None else None,
+                                                     _lib.ptr(c) if c is not None else None))
+
+    def row_info(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(ts (N,) int32, class (N,) int32) of every row as the device holds them (cc_index_row_info)."""
+        n = len(self)
+        ts, c = np.empty(n, np.int32), np.empty(n, np.int32)
+        _lib.check(_lib.lib().cc_index_row_info(self._h, 0, n, _lib.ptr(ts), _lib.ptr(c)))
+        return ts, c
 
     def remove(self, rows) -> int:
         """Take rows out; the survivors keep their order and are renumbered densely (new id = survivors before the row), so
@@ -280,12 +328,16 @@ class EmbeddingIndex:
             c = np.nextafter(c, np.float32(np.inf))
         return c
 
-    def rank(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def rank(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
+             classes=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Answers start .. start+count-1 of the WHOLE descending order -> (idx (Q,count) int32, score (Q,count) f32, total (Q,)
         int64), at any depth and of any length, in one call (cc_index_rank).  tracks=True: the answers and their order are those of
         `search_tracks`; False: every allowed row answers for itself, ordered as `search` orders them.  Only answers with
         score >= min_score exist (`cut_f32` of the value given): ranks are counted among them and `total` is their number, so a
-        cut inside a run of equal scores keeps the whole run.  -1/-inf past the last answer."""
+        cut inside a run of equal scores keeps the whole run.  -1/-inf past the last answer.
+        ts_range / classes (`row_filter`): only rows that pass compete, and the call answers as an index built from those rows
+        alone would - a track is reduced among its passing rows and placed by its first passing one (cc_index_rank_where)."""
+        where = self.row_filter(ts_range, classes)
         qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
         start, count = int(start), int(count)
         if count < 1 or start < 0:
@@ -294,23 +346,48 @@ class EmbeddingIndex:
             idx, sc = np.empty((qa.shape[0], count), np.int32), np.empty((qa.shape[0], count), np.float32)
         total = np.zeros(qa.shape[0], np.int64)
         al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_rank(self._h, _lib.ptr(qa), qa.shape[0], start, count, float(self.cut_f32(min_score)), 1 if tracks else 0,
-                                            _lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size),
-                                            _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 0, None))
+        head = (self._h, _lib.ptr(qa), qa.shape[0], start, count, float(self.cut_f32(min_score)), 1 if tracks else 0,
+                _lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size))
+        tail = (_lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 0, None)
+        if where is None:
+            _lib.check(_lib.lib().cc_index_rank(*head, *tail))
+        else:
+            _lib.check(_lib.lib().cc_index_rank_where(*head, C.byref(where), *tail))
         return idx, sc, total
 
-    def rank_device(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, with_total: bool = True):
+    def rank_device(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, with_total: bool = True,
+                    ts_range=None, classes=None):
         """`rank` with idx / score left on the GPU like `search_tracks_device`.  `total` still comes back as a host array, which
         costs one wait for the stream; with_total=False returns None in its place and waits for nothing."""
         args = (int(start), int(count), float(self.cut_f32(min_score)), 1 if tracks else 0)
-        return self._search_device("cc_index_rank", q, int(count), allowed, args, with_total)
+        return self._search_device("cc_index_rank", q, int(count), allowed, args, with_total, self.row_filter(ts_range, classes))
+
+    def timeline(self, q, t0: int, bin_seconds: int, n_bins: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
+                 classes=None) -> Tuple[np.ndarray, np.ndarray]:
+        """How the answers of `rank` (same arguments) spread over time -> (counts (Q, n_bins) int64, total (Q,) int64), in one call
+        (cc_index_timeline).  An answer falls into bin floor((ts - t0) / bin_seconds), ts being that of the row `rank` names for it
+        (a track: its best passing crop); an answer without ts or outside the n_bins bins is counted in `total` only, which
+        equals `rank`'s total.  bin_seconds >= 1, 1 <= n_bins <= 4096, t0 an int32."""
+        where = self.row_filter(ts_range, classes)
+        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+        if not -(1 << 31) <= t0 < 1 << 31 or not -(1 << 31) <= bin_seconds < 1 << 31 or not -(1 << 31) <= n_bins < 1 << 31:
+            raise ValueError("t0, bin_seconds and n_bins must fit in int32")
+        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
+        counts = np.zeros((qa.shape[0], min(max(n_bins, 1), 4096)), np.uint32)     # outside [1, 4096]: the library names the error
+        total = np.zeros(qa.shape[0], np.int64)
+        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_timeline(self._h, _lib.ptr(qa), qa.shape[0], float(self.cut_f32(min_score)), 1 if tracks else 0,
+                                                _lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size),
+                                                C.byref(where) if where is not None else None, t0, bin_seconds, n_bins,
+                                                _lib.ptr(counts), _lib.ptr(total), 0, None))
+        return counts.astype(np.int64), total
 
     def search_device(self, q, k: int):
         """`search` with the result left on the GPU: (idx int32, score f32) CUDA torch tensors on the current torch stream,
         for callers that keep going on the device (clearcam_amd.dist.ShardedIndex: all-gather + merge)."""
         return self._search_device("cc_index_search_groups", q, k, None)
 
-    def _search_device(self, call: str, q, k: int, allowed, rank_args=None, with_total: bool = False):
+    def _search_device(self, call: str, q, k: int, allowed, rank_args=None, with_total: bool = False, where=None):
         import torch
         dev = torch.device("cuda", self.device)
         if not bool(getattr(q, "is_cuda", False)):
@@ -332,7 +409,11 @@ class EmbeddingIndex:
         # nothing waits for the stream here: the filter bytes stay referenced until the next call replaces them
         al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
         total = np.zeros(qa.shape[0], np.int64) if with_total else None
-        if rank_args is not None:
+        if rank_args is not None and where is not None:
+            _lib.check(_lib.lib().cc_index_rank_where(self._h, _lib.ptr(qa), qa.shape[0], *rank_args, _lib.ptr(al) if al is not None else None,
+                                                      0 if al is None else int(al.size), C.byref(where), _lib.ptr(idx), _lib.ptr(sc),
+                                                      _lib.ptr(total), 1, C.c_void_p(run.cuda_stream)))
+        elif rank_args is not None:
             _lib.check(_lib.lib().cc_index_rank(self._h, _lib.ptr(qa), qa.shape[0], *rank_args, _lib.ptr(al) if al is not None else None,
                                                 0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 1,
                                                 C.c_void_p(run.cuda_stream)))
@@ -374,6 +455,23 @@ class _RowTable:
         self.oid: List[Optional[int]] = []     # track id per row exactly as event_img_info returns it (any sign), None = no '_' in the name
         self.slot_of: Dict[int, int] = {}      # track id -> dense slot, in order of first appearance (id 0 and negative ids are ids)
         self.slot: List[int] = []              # slot per row, -1 where oid is None: what the device reduces by (EmbeddingIndex.search_tracks)
+        self.ts: List[int] = []                # seconds into the day's recording per row (event_img_info's `ts`), _lib.ROW_NO_TS = none
+        self.cls: List[int] = []               # detector class per row (event_img_info's `class_id`) in [0, 255], -1 = none
+
+    @staticmethod
+    def name_attrs(path: str) -> Tuple[int, int]:
+        """(ts, class) of a crop as the device stores them: `event_img_info` of the '<ts>_<track>_<class>.jpg' name, i.e.
+        int(float(first part)) and int(third part).  "None" (_lib.ROW_NO_TS / -1) when the name is no *.jpg, has no '_', does
+        not parse, or the value does not fit (ts: an int32 other than ROW_NO_TS itself; class: [0, 255])."""
+        fn = os.path.basename(path)
+        if not fn.lower().endswith(".jpg") or "_" not in fn:
+            return _lib.ROW_NO_TS, -1
+        try:
+            info = event_img_info(fn.split(".jpg")[0])
+        except Exception:                      # noqa: BLE001  a name the reference raises on carries no attributes
+            return _lib.ROW_NO_TS, -1
+        ts, c = info["ts"], info["class_id"]
+        return (ts if _lib.ROW_NO_TS < ts < (1 << 31) else _lib.ROW_NO_TS), (c if 0 <= c <= 255 else -1)
 
     def describe(self, path: str) -> Tuple[int, int]:
         norm = path.replace("\\", "/")
@@ -403,11 +501,30 @@ class _RowTable:
             groups[i] = g
             self.group.append(g); self.oid.append(oid)
             self.slot.append(-1 if oid is None else self.slot_of.setdefault(oid, len(self.slot_of)))
+            ts, c = self.name_attrs(p)
+            self.ts.append(ts); self.cls.append(c)
         self.paths.extend(paths)
         return groups
 
     def slots(self, start: int = 0) -> np.ndarray:
         return np.asarray(self.slot[start:], np.int32)
+
+    def attrs(self, start: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(ts, class) of the rows from `start` on, as EmbeddingIndex.add takes them."""
+        return np.asarray(self.ts[start:], np.int32), np.asarray(self.cls[start:], np.int32)
+
+    def passing(self, where) -> np.ndarray:
+        """Bool per row: the row passes the row filter (an `EmbeddingIndex.row_filter`, None: every row), as the device decides."""
+        ok = np.ones(len(self.paths), bool)
+        if where is None:
+            return ok
+        ts, c = self.attrs()
+        if where.use_ts:
+            ok &= (ts != _lib.ROW_NO_TS) & (ts >= where.ts_min) & (ts <= where.ts_max)
+        if where.use_cls:
+            bits = np.array([(int(where.cls_mask[i >> 6]) >> (i & 63)) & 1 for i in range(256)], bool)
+            ok &= (c >= 0) & bits[np.clip(c, 0, 255)]
+        return ok
 
     @staticmethod
     def dir_of(path: str) -> str:
@@ -432,6 +549,8 @@ class _RowTable:
         self.group = [self.group[r] for r in keep]
         self.oid = [self.oid[r] for r in keep]
         self.slot = [self.slot[r] for r in keep]
+        self.ts = [self.ts[r] for r in keep]
+        self.cls = [self.cls[r] for r in keep]
         for g in lost:
             self.truthy[g] = self.bad[g] = False
         for r, g in enumerate(self.group):
@@ -840,10 +959,15 @@ class ObjectFinder:
 
     @staticmethod
     def _add_rows(index: EmbeddingIndex, table: "_RowTable", rows, paths) -> None:
-        """Rows into the device matrix with their directory group and, where the index reduces per track, their track slot."""
+        """Rows into the device matrix with their directory group and, where the index reduces per track, their track slot;
+        where it keeps them, also the ts and the class of their names (the attached store and the dict-built indexes alike)."""
         groups = table.extend(paths)
-        if hasattr(index, "search_tracks"):
-            index.add(rows, groups, table.slots(len(table.paths) - len(paths)))
+        first = len(table.paths) - len(paths)
+        if hasattr(index, "row_info"):             # the index keeps ts / class per row (row filters, timeline)
+            ts, classes = table.attrs(first)
+            index.add(rows, groups, table.slots(first), ts=ts, classes=classes)
+        elif hasattr(index, "search_tracks"):
+            index.add(rows, groups, table.slots(first))
         else:
             index.add(rows, groups)
 
@@ -1029,11 +1153,17 @@ class ObjectFinder:
             raise ValueError(f"query has {q.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
         return q, index, table, table.allowed(cam_name, timestamp)
 
-    def search_page(self, query=None, start=0, count=100, cam_name=None, timestamp=None, text_embedding=None, is_face=False, min_score=None):
+    def search_page(self, query=None, start=0, count=100, cam_name=None, timestamp=None, text_embedding=None, is_face=False, min_score=None,
+                    ts_range=None, classes=None):
         """One page of the results, what the search endpoint computes (clearcam.py:1108-1118 + `send_results`, :686-705) by asking
         for top_k = start + count, cutting at the first score below 0.21 and slicing: -> (results, total) with
         results == [r for r in search(..., top_k=everything) if not r[1] < min_score][start:start+count] and total the length of
-        that filtered list.  One `EmbeddingIndex.rank` call at any depth; only `count` (path, score) pairs leave the GPU."""
+        that filtered list.  One `EmbeddingIndex.rank` call at any depth; only `count` (path, score) pairs leave the GPU.
+        ts_range=(first, last) seconds into the day, inclusive, and classes=[ids] narrow the search to the crops whose name
+        '<ts>_<track>_<class>.jpg' carries a ts inside the window / one of the classes (`EmbeddingIndex.row_filter`): the result is
+        what `search` gives over those crops alone.  Whether answers are grouped per track is decided as without a row filter,
+        from the track ids of ALL crops in the allowed folders, not only of the passing ones."""
+        where = row_filter(ts_range, classes)
         start, count = int(start), int(count)
         if start < 0 or count < 1:
             raise ValueError("search_page needs start >= 0 and count >= 1")
@@ -1048,13 +1178,18 @@ class ObjectFinder:
             return [], 0
         if any(table.bad[g] for g in live) or not hasattr(index, "rank"):
             # names the reference raises on (it raises here too), or an index that cannot rank: the whole list, cut on the host
-            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face)
+            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face,
+                               ts_range=ts_range, classes=classes)
             kept = [r for r in full if min_score is None or not r[1] < min_score]
             return kept[start:start + count], len(kept)
-        idx, sc, total = index.rank(q, start, min(count, len(table.paths)), allowed, min_score, tracks=any(table.truthy[g] for g in live))
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        idx, sc, total = index.rank(q, start, min(count, len(table.paths)), allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
         return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
 
-    def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False):
+    def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False, ts_range=None, classes=None):
+        """:356-390.  ts_range / classes: the row filter of `search_page`; with one given the device ranks (`EmbeddingIndex.rank`),
+        and grouping per track is decided as without it, from the track ids of all crops in the allowed folders."""
+        where = row_filter(ts_range, classes)
         setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
         if setup is None:
             return []
@@ -1064,14 +1199,15 @@ class ObjectFinder:
             return []
         exact_loop = any(table.bad[g] for g in live)
         grouped = any(table.truthy[g] for g in live)
-        if grouped and not exact_loop and top_k <= 1024 and hasattr(index, "search_tracks"):
+        if where is None and grouped and not exact_loop and top_k <= 1024 and hasattr(index, "search_tracks"):
             # the device reduces per track id and selects (one call, exact whatever the data: thousands of crops of one track, ties)
             idx, sc = index.search_tracks(q, int(top_k), allowed)
             return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
         if not exact_loop and hasattr(index, "rank"):
             # top_k > 1024, or no truthy track id among the allowed crops (the reference does not group then): the device ranks the
             # whole order and hands back its head.  At most one answer per row: "everything" (top_k = 10**9) allocates no more.
-            idx, sc, _ = index.rank(q, 0, min(int(top_k), len(table.paths)), allowed, None, tracks=grouped)
+            kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+            idx, sc, _ = index.rank(q, 0, min(int(top_k), len(table.paths)), allowed, None, tracks=grouped, **kw)
             return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
         # An index without `rank` (no track ids among the allowed rows, top_k > 1024 or no search_tracks either):
         # GPU: filtered top-K' (one HBM pass + radix select); host: the reference's best-per-track-id tail on K' rows.
@@ -1079,7 +1215,7 @@ class ObjectFinder:
         # enter or change it) or every allowed row has been seen; otherwise K' grows, and past 1024 the full score vector
         # is ranked (many crops of few tracks above everything else: rare).
         kk = min(1024, max(128, 16 * int(top_k)))
-        while not exact_loop:
+        while not exact_loop and where is None:             # a row filter the index cannot apply: the full score vector below
             idx, sc = index.search(q, kk, allowed)
             keep = idx[0] >= 0
             rows, scs = idx[0][keep], sc[0][keep]
@@ -1098,10 +1234,45 @@ class ObjectFinder:
                 break
             kk = min(1024, kk * 4)
         scores = index.scores(q)[0]                         # the whole score vector, ranked like the reference does it
-        rows = [r for r in range(len(table.paths)) if allowed[table.group[r]]]
+        passing = table.passing(where)
+        rows = [r for r in range(len(table.paths)) if allowed[table.group[r]] and passing[r]]
         if exact_loop:                                      # names the reference itself would raise on: let it raise the same way
             for r in rows:
                 fn = os.path.basename(table.paths[r])
                 if "_" in fn:
                     event_img_info(fn.split(".jpg")[0])
         return self._rank(table, rows, [float(scores[r]) for r in rows], grouped)[:top_k]
+
+    def timeline(self, query=None, t0=0, bin_seconds=3600, n_bins=24, cam_name=None, timestamp=None, text_embedding=None, is_face=False,
+                 min_score=0.21, ts_range=None, classes=None):
+        """How the hits of a query spread over the day -> (counts (n_bins,) int64, total): the results `search_page` would page
+        through (same folders, cut and row filter; grouped per track as `search_page` decides it), counted by the ts of each
+        result's crop into bin (ts - t0) // bin_seconds.  A result whose name carries no ts, or whose bin lies outside
+        [0, n_bins), is counted in `total` only; `total` is `search_page`'s.  One `EmbeddingIndex.timeline` call: n_bins counters
+        leave the GPU, no scores."""
+        where = row_filter(ts_range, classes)
+        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+        if bin_seconds < 1 or not 1 <= n_bins <= 4096:
+            raise ValueError("timeline needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
+        if min_score is not None and min_score != min_score:
+            raise ValueError("min_score is NaN")
+        counts = np.zeros(n_bins, np.int64)
+        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
+        if setup is None:
+            return counts, 0
+        q, index, table, allowed = setup
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return counts, 0
+        if any(table.bad[g] for g in live) or not hasattr(index, "timeline"):
+            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face,
+                               ts_range=ts_range, classes=classes)
+            kept = [r for r in full if min_score is None or not r[1] < min_score]
+            for path, _ in kept:
+                ts = _RowTable.name_attrs(path)[0]
+                if ts != _lib.ROW_NO_TS and 0 <= (ts - t0) // bin_seconds < n_bins:
+                    counts[(ts - t0) // bin_seconds] += 1
+            return counts, len(kept)
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        c, total = index.timeline(q, t0, bin_seconds, n_bins, allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
+        return c[0], int(total[0])

@@ -492,6 +492,41 @@ int cc_index_search_tracks(cc_index* h, const float* q, int Q, int k, const uint
 int cc_index_rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags,
                   const uint8_t* allowed, int n_groups,
                   int32_t* idx, float* score, int64_t* total, int on_device, void* stream);
+/* Two attributes per row beside its group and its track slot, both read from the crop's name '<ts>_<track>_<class>.jpg':
+ *   ts  - int32, the seconds into that day's recording (CC_ROW_NO_TS: the row has none);
+ *   cls - int32 in [-1, 255], the detector's class (-1: the row has none).
+ * cc_index_add_described is cc_index_add_tracked plus the two tables, all four on the HOST and each may be NULL (group 0, slot -1,
+ * no ts, no class); the other add calls store "none" for both.  A cls outside [-1, 255] is an error (-22, nothing added).  The
+ * attributes follow their rows through growth and through cc_index_remove_* (the same stable compaction, the same new numbers).
+ * cc_index_row_info reads them back: rows row0 .. row0 + n - 1 into ts_out / cls_out (n int32 each on the HOST, either may be
+ * NULL); a range outside the index is an error (-22). */
+#define CC_ROW_NO_TS INT32_MIN
+int cc_index_add_described(cc_index* h, const float* emb, int64_t n, int on_device, const int32_t* groups, const int32_t* tracks,
+                           const int32_t* ts, const int32_t* cls);
+int cc_index_row_info(cc_index* h, int64_t row0, int64_t n, int32_t* ts_out, int32_t* cls_out);
+/* A row filter for ranking.  A row competes when its group is allowed AND (use_ts == 0 OR it has a ts with ts_min <= ts <= ts_max)
+ * AND (use_cls == 0 OR it has a class c with bit c of cls_mask set: cls_mask[c / 64] >> (c % 64) & 1).  A row without the attribute
+ * never passes a filter on that attribute.  The struct travels as kernel arguments: no allocation, no copy. */
+typedef struct { int32_t use_ts, ts_min, ts_max;   /* inclusive at both ends */
+                 int32_t use_cls; uint64_t cls_mask[4]; /* bit c set: class c passes */ } cc_row_filter;
+/* cc_index_rank among the competing rows only.  Everything else is cc_index_rank's contract: with CC_RANK_TRACKS a track is reduced
+ * among its PASSING rows and its place among equal scores is its first PASSING row, so the call answers as an index built from the
+ * passing rows alone would (same slots, same groups): scores bit for bit, rows under their numbers in THIS index, total equal.
+ * where == NULL: exactly cc_index_rank.  Errors (-22, nothing changed): those of cc_index_rank, ts_min > ts_max with use_ts, an
+ * all-zero mask with use_cls. */
+int cc_index_rank_where(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags,
+                        const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                        int32_t* idx, float* score, int64_t* total, int on_device, void* stream);
+/* How the answers of a query spread over time: a histogram of the answers cc_index_rank_where would rank (same cut, flags, filters).
+ * An answer's time is the ts of the row `idx` would name for it (a track: its best passing crop, not its first row).  It is counted
+ * in bin floor((ts - t0) / bin_seconds), computed in 64 bits; an answer without ts, or with a bin outside [0, n_bins), is counted in
+ * total only, so sum(counts[q]) <= total[q], and total[q] equals cc_index_rank_where's.  counts: (Q, n_bins) uint32, on the device
+ * with on_device (queries then too); total: Q int64 on the HOST, may be NULL.  The call waits for the stream unless on_device is
+ * set and total is NULL.  bin_seconds >= 1, 1 <= n_bins <= 4096, otherwise -22 like the errors of cc_index_rank_where.
+ * Integer sums: the result does not depend on the order in which blocks arrive. */
+int cc_index_timeline(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups,
+                      const cc_row_filter* where, int32_t t0, int32_t bin_seconds, int n_bins,
+                      uint32_t* counts, int64_t* total, int on_device, void* stream);
 /* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
  * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
  * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
