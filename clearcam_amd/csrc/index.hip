@@ -66,6 +66,11 @@ namespace {
 
 constexpr int kChunk = 16384;     // rows per stage-1 block
 constexpr int kMaxK = 1024;
+// scan_kernel and scan_bf16_kernel keep the queries of a pass in LDS, dim floats each.  A pass takes as many as the 160 KB of a gfx950
+// CU hold, at most 8: 8 up to dim 5120 (768 and 512 among them), 7 at 5376, 5 at 8192, 2 at 16384, 1 from 20736 to 40960, the
+// widest bf16 row cc_index_create_ex accepts.  Per query the order of the additions does not depend on the width of the pass.
+constexpr int kScanLdsFloats = 40960;
+inline int scan_pass_width(int dim) { return std::max(1, std::min(8, kScanLdsFloats / dim)); }
 
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
@@ -148,7 +153,9 @@ __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ emb
 
 template <int QB> void launch_scan(cc_index* h, const float* q, float* out, hipStream_t s) {
   const int blocks = (int)std::min<int64_t>((h->n + 15) / 16, 256 * 8);
-  hipLaunchKernelGGL(scan_kernel<QB>, dim3(blocks), dim3(256), (size_t)QB * h->dim * 4, s, h->emb, q, out, (long)h->n, h->dim);
+  const size_t lds = (size_t)QB * h->dim * 4;                     // <= kScanLdsFloats * 4: compute_scores cuts the passes by scan_pass_width
+  if (lds > 65536) ensure_max_lds(scan_kernel<QB>, (size_t)kScanLdsFloats * 4);
+  hipLaunchKernelGGL(scan_kernel<QB>, dim3(blocks), dim3(256), lds, s, h->emb, q, out, (long)h->n, h->dim);
 }
 
 // bf16-stored rows: 16 lanes x 8 halfs per step, two independent groups of four rows per wave iteration (four 16-byte loads per
@@ -202,7 +209,9 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const uint16_t* __restri
 
 template <int QB> void launch_scan_bf16(cc_index* h, const float* q, float* out, hipStream_t s) {
   const int blocks = (int)std::min<int64_t>((h->n + 31) / 32, 256 * 8);
-  hipLaunchKernelGGL(scan_bf16_kernel<QB>, dim3(blocks), dim3(256), (size_t)QB * h->dim * 4, s, reinterpret_cast<const uint16_t*>(h->emb), q, out, (long)h->n, h->dim);
+  const size_t lds = (size_t)QB * h->dim * 4;
+  if (lds > 65536) ensure_max_lds(scan_bf16_kernel<QB>, (size_t)kScanLdsFloats * 4);
+  hipLaunchKernelGGL(scan_bf16_kernel<QB>, dim3(blocks), dim3(256), lds, s, reinterpret_cast<const uint16_t*>(h->emb), q, out, (long)h->n, h->dim);
 }
 
 // f32 rows -> bf16 rows (round to nearest even), for cc_index_add on a bf16-stored index
@@ -946,10 +955,11 @@ void compute_scores(cc_index* h, int Q, hipStream_t s) {
     CC_HIP(hipGetLastError());
     return;
   }
-  if (h->storage == BF16) {                         // bf16 rows: 8 queries per pass over half the bytes (dim % 256 == 0 is checked at create)
-    for (int q0 = 0; q0 < Q; q0 += 8) {
+  const int W = scan_pass_width(h->dim);            // 8 unless the rows are wider than 5120
+  if (h->storage == BF16) {                         // bf16 rows: W queries per pass over half the bytes (dim % 256 == 0 is checked at create)
+    for (int q0 = 0; q0 < Q; q0 += W) {
       const float* q = h->q_dev + (size_t)q0 * h->dim; float* out = h->scores + (size_t)q0 * h->n;
-      switch (std::min(8, Q - q0)) {
+      switch (std::min(W, Q - q0)) {
         case 1: launch_scan_bf16<1>(h, q, out, s); break;  case 2: launch_scan_bf16<2>(h, q, out, s); break;
         case 3: launch_scan_bf16<3>(h, q, out, s); break;  case 4: launch_scan_bf16<4>(h, q, out, s); break;
         case 5: launch_scan_bf16<5>(h, q, out, s); break;  case 6: launch_scan_bf16<6>(h, q, out, s); break;
@@ -965,10 +975,10 @@ void compute_scores(cc_index* h, int Q, hipStream_t s) {
     const ConvP g = gemm_params(h->q_dev, h->dim, Q, h->dim, h->emb, h->dim, nullptr, (int)h->n, h->scores, (int)h->n, 1, 0, nullptr, 0, 0);
     if (h->n < (1L << 31) && conv_mfma_supported(F32, g)) { launch_conv_mfma(F32, g, s); h->last_path = 1; return; }
   }
-  if (scan8) {
-    for (int q0 = 0; q0 < Q; q0 += 8) {
+  if (scan8) {                                      // dim <= 4096: W is 8
+    for (int q0 = 0; q0 < Q; q0 += W) {
       const float* q = h->q_dev + (size_t)q0 * h->dim; float* out = h->scores + (size_t)q0 * h->n;
-      switch (std::min(8, Q - q0)) {
+      switch (std::min(W, Q - q0)) {
         case 1: launch_scan<1>(h, q, out, s); break;  case 2: launch_scan<2>(h, q, out, s); break;
         case 3: launch_scan<3>(h, q, out, s); break;  case 4: launch_scan<4>(h, q, out, s); break;
         case 5: launch_scan<5>(h, q, out, s); break;  case 6: launch_scan<6>(h, q, out, s); break;
@@ -995,7 +1005,8 @@ int cc_index_create_ex(cc_index** h, int dim, int64_t capacity, int device, int 
   CC_API_BEGIN
   CC_CHECK(h && dim > 0 && dim % 4 == 0 && capacity > 0, "bad argument (dim must be a multiple of 4)");
   CC_CHECK(storage == F32 || storage == BF16 || storage == CC_INDEX_I8, "index storage must be 0 (f32), 2 (bf16) or 8 (int8 with group scales)");
-  CC_CHECK(storage != BF16 || dim % 256 == 0, "a bf16 index needs dim % 256 == 0");
+  // one query of a scan pass has to fit into the LDS of a CU (kScanLdsFloats): a wider bf16 row is refused here, not at the first search
+  CC_CHECK(storage != BF16 || (dim % 256 == 0 && dim <= kScanLdsFloats), "a bf16 index needs dim % 256 == 0 (and dim <= 40960)");
   CC_CHECK(storage != CC_INDEX_I8 || (dim % 256 == 0 && dim <= 16384), "an int8 index needs dim % 256 == 0 (and dim <= 16384)");
   int n = 0; CC_HIP(hipGetDeviceCount(&n));
   CC_CHECK(n > 0 && device >= 0 && device < n, "no such HIP device");

@@ -167,7 +167,7 @@ def row_filter(ts_range=None, classes=None) -> Optional["_lib.RowFilter"]:
 
 class EmbeddingIndex:
     """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores), "bf16" (half the
-    bytes per scan, scores within ~1e-3 for unit vectors) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
+    bytes per scan, scores within ~1e-3 for unit vectors; dim % 256 == 0 and at most 40960) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
     bytes a row, scores within ~1e-3 as well; include/clearcam_hip.h has the rule).  `capacity` is the initial allocation; the
     matrix grows.
 

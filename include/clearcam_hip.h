@@ -433,7 +433,8 @@ void cc_ocsort_destroy(cc_ocsort* h);
 typedef struct cc_index cc_index;
 int cc_index_create(cc_index** h, int dim, int64_t capacity, int device);        /* f32 rows */
 /* storage 0: f32 rows, exact f32 dot products.  storage 2: rows rounded to bf16 (half the bytes per scan; scores within
- * ~1e-3 of the f32 index for unit vectors; dim % 256 == 0).  `capacity` is the initial allocation: the matrix grows
+ * ~1e-3 of the f32 index for unit vectors; dim % 256 == 0 and dim <= 40960, or the call fails: one query of a scan pass has to fit
+ * into the LDS of a CU).  `capacity` is the initial allocation: the matrix grows
  * geometrically (device-to-device copy) when cc_index_add* runs past it.
  * storage CC_INDEX_I8 (8, clear of the CC_DTYPE_* numbers): int8 rows, dim % 256 == 0 (and dim <= 16384).  A stored row is dim int8
  * codes (two's complement, element order) followed by dim / 32 float32 scales, one per group of 32 consecutive elements:
