@@ -19,6 +19,10 @@
 // Every row also carries ts (seconds into the day's recording) and cls (the detector's class), the other two facts of a crop's name.
 // cc_index_rank_where tests them where the group filter is tested (row_passes, in the track reduction and in the key pass), and
 // cc_index_timeline counts the answers of a ranking into bins of their ts (timeline_kernel) instead of selecting a window.
+//
+// cc_index_rank_like takes its queries from the matrix itself ("more like this stored crop / this whole track"): fetch_rows_kernel
+// gathers and decodes them, like_fold_kernel folds their score vectors into one by the row-wise maximum and marks the excluded rows,
+// which row_passes then keeps out of the ranking like rows the filter rejects ("Query by stored rows").
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -60,6 +64,11 @@ struct cc_index {
   unsigned long long* goff = nullptr; size_t goff_cap = 0;     // survivors before each granule, and the total behind the last one
   char* bounce = nullptr; size_t bounce_cap = 0;               // one slab of survivors: rows, then their groups, then their slots
   char* rank_ws = nullptr; size_t rank_ws_cap = 0;             // cc_index_rank: per query and select the state, a 256-bin table and a window counter; per query the total
+  // query by stored rows (cc_index_fetch_rows / cc_index_rank_like)
+  unsigned char* dead = nullptr; size_t dead_cap = 0;          // (n) one byte per row of the current cc_index_rank_like: non-zero = excluded, does not compete
+  long long* rows_pin = nullptr; size_t rows_pin_cap = 0;      // pinned, device-visible: the row numbers of a gather of more than CC_LIKE_MAX_ROWS rows, read by fetch_rows_kernel
+  hipEvent_t rows_ev = nullptr;                                // recorded behind that gather: rows_pin is rewritten only after it
+  std::vector<int32_t> grp_host, trk_host;                     // the grp / trk columns on the host (n each): CC_LIKE_EXCLUDE_TRACK is checked without a device round trip
 };
 
 namespace {
@@ -391,12 +400,15 @@ __device__ __forceinline__ bool row_allowed(const int* __restrict__ grp, const u
 }
 
 // cc_row_filter as the kernels take it (by value, in the kernel arguments): a null column = no filter on that attribute.
-struct RowWhere { const int* ts; const int* cls; int ts_min, ts_max; unsigned long long m0, m1, m2, m3; };
+// dead: one byte per row, non-zero = the row is out of the running (cc_index_rank_like's exclusion, written by like_fold_kernel); null
+// everywhere else.
+struct RowWhere { const int* ts; const int* cls; int ts_min, ts_max; unsigned long long m0, m1, m2, m3; const unsigned char* dead; };
 
-// The row competes: its group is allowed, and it has the attributes the filter asks for.  The mask word is chosen by compares, not
-// by an index, so the four words stay in scalar registers.
+// The row competes: its group is allowed, it has the attributes the filter asks for, and it is not dead.  The mask word is chosen by
+// compares, not by an index, so the four words stay in scalar registers.
 __device__ __forceinline__ bool row_passes(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, const RowWhere& w, long r) {
   if (!row_allowed(grp, allowed, n_allowed, r)) return false;
+  if (w.dead && w.dead[r]) return false;
   if (w.ts) {
     const int t = w.ts[r];
     if (t == CC_ROW_NO_TS || t < w.ts_min || t > w.ts_max) return false;
@@ -753,6 +765,106 @@ __global__ __launch_bounds__(256) void timeline_kernel(const unsigned* __restric
   for (int i = tid; i < n_bins; i += 256) { const unsigned v = bins[i]; if (v) atomicAdd(&c[i], v); }
 }
 
+// ---- query by stored rows (cc_index_fetch_rows / cc_index_rank_like) ------------------------------------------------------------
+// The queries are rows of the matrix: a gather decodes them to f32 where upload_queries would have copied them, the scoring routes
+// of compute_scores run as for any batch, one pass folds the (Q, n) score matrix into one vector (the row-wise maximum) and marks the
+// excluded rows, and the ranking of ONE query follows unchanged.  Ordered by the stream alone, like everything above.
+
+// Up to CC_LIKE_MAX_ROWS row numbers by value, in the kernel arguments (-1 behind the last one): the query rows of a
+// cc_index_rank_like, for the gather and for the fold.
+struct LikeRows { int n; int r[CC_LIKE_MAX_ROWS]; };
+
+// out[i] = row i of the list decoded to f32.  One wave (one block) per row, one 16-byte piece of the stored row per lane and load,
+// like compact_kernel: f32 the bytes as they are, bf16 the 16 bits moved to the high half, int8 (float)code * s_g with s_g from the
+// row's trailer (a piece of 16 codes lies inside one group of 32).  The list: `rows` (pinned host memory) or, when that is null,
+// `few` in the arguments, indexed by the block number alone, so that the number comes from a scalar load.  The numbers were checked
+// on the host; the test here keeps every load inside the matrix whatever the list holds.
+__global__ __launch_bounds__(64) void fetch_rows_kernel(const char* __restrict__ emb, const long long* __restrict__ rows, const LikeRows few, long size, int dim,
+                                                        int storage, float* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const long i = blockIdx.x;
+  const long long r = rows ? rows[i] : (long long)few.r[blockIdx.x & (CC_LIKE_MAX_ROWS - 1)];
+  if ((unsigned long long)r >= (unsigned long long)size) return;
+  float4* o = reinterpret_cast<float4*>(out + (size_t)i * dim);
+  if (storage == F32) {
+    const float4* e = reinterpret_cast<const float4*>(emb + (size_t)r * dim * 4);
+    for (int c = lane; c < (dim >> 2); c += 64) o[c] = e[c];
+  } else if (storage == BF16) {
+    const uint4* e = reinterpret_cast<const uint4*>(emb + (size_t)r * dim * 2);
+    for (int c = lane; c < (dim >> 3); c += 64) {
+      const uint4 v = e[c];
+      o[2 * c] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+      o[2 * c + 1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u));
+    }
+  } else {
+    const char* e = emb + (size_t)r * ((size_t)dim + (dim >> 3));
+    for (int c = lane; c < (dim >> 4); c += 64) {
+      const uint4 v = reinterpret_cast<const uint4*>(e)[c];
+      const float s = reinterpret_cast<const float*>(e + dim)[c >> 1];
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[4 * c + k] = make_float4(i8_code(w[k], 0) * s, i8_code(w[k], 1) * s, i8_code(w[k], 2) * s, i8_code(w[k], 3) * s);
+    }
+  }
+}
+
+// the larger of two scores in the order of the ranking keys: +0 beats -0
+__device__ __forceinline__ float omax(float a, float b) { return ordered(b) > ordered(a) ? b : a; }
+
+// S (Q, n) -> S[0][r] = max over q of S[q][r], in place, and dead[r] (dead != null).  mode 1: the query rows are dead; mode 2: every
+// row of group G and slot T is (the query rows among them: they all have that group and that slot).  A thread reads S[.][r] and
+// writes S[0][r] and dead[r] of its own rows only, so no thread reads what another one writes and the pass needs neither atomics nor
+// LDS.  VEC (n % 4 == 0: row q of S starts at byte 4 q n, a multiple of 16 only then): four consecutive rows per thread with one
+// 16-byte load per query, the loads of a thread independent of each other.  Otherwise one row per thread and 4-byte loads.
+template <bool VEC>
+__global__ __launch_bounds__(256) void like_fold_kernel(float* __restrict__ S, int Q, long n, const int* __restrict__ grp, const int* __restrict__ trk,
+                                                        const LikeRows rows, int mode, int G, int T, unsigned char* __restrict__ dead) {
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nt = (long)gridDim.x * 256;
+  if (VEC) {
+    const long n4 = n >> 2;
+    float4* S4 = reinterpret_cast<float4*>(S);
+    for (long i = tid; i < n4; i += nt) {
+      if (Q > 1) {
+        float4 m = S4[i];
+#pragma unroll 4
+        for (int q = 1; q < Q; ++q) {
+          const float4 x = S4[(long)q * n4 + i];
+          m.x = omax(m.x, x.x); m.y = omax(m.y, x.y); m.z = omax(m.z, x.z); m.w = omax(m.w, x.w);
+        }
+        S4[i] = m;
+      }
+      if (dead) {
+        unsigned d = 0u;
+        if (mode == 2) {
+          const int4 g = reinterpret_cast<const int4*>(grp)[i], t = reinterpret_cast<const int4*>(trk)[i];
+          d = (g.x == G && t.x == T ? 1u : 0u) | (g.y == G && t.y == T ? 1u << 8 : 0u) | (g.z == G && t.z == T ? 1u << 16 : 0u) | (g.w == G && t.w == T ? 1u << 24 : 0u);
+        } else {
+          for (int j = 0; j < rows.n; ++j) {
+            const long k = (long)rows.r[j] - 4 * i;
+            if (k >= 0 && k < 4) d |= 1u << (8 * (int)k);
+          }
+        }
+        reinterpret_cast<unsigned*>(dead)[i] = d;
+      }
+    }
+  } else {
+    for (long r = tid; r < n; r += nt) {
+      if (Q > 1) {
+        float m = S[r];
+#pragma unroll 4
+        for (int q = 1; q < Q; ++q) m = omax(m, S[(long)q * n + r]);
+        S[r] = m;
+      }
+      if (dead) {
+        bool d = false;
+        if (mode == 2) d = grp[r] == G && trk[r] == T;
+        else for (int j = 0; j < rows.n; ++j) d = d || (long)rows.r[j] == r;
+        dead[r] = d ? 1 : 0;
+      }
+    }
+  }
+}
+
 // ---- removal: stable compaction in place -------------------------------------------------------------------------------------
 // Row r moves to pos(r) = the survivors before it, and pos(r) <= r.  Positions come from three passes: keep flags and survivor
 // counts per granule of kGran rows, an exclusive scan of the counts by ONE block (64-bit), and the place inside the granule from a
@@ -900,8 +1012,12 @@ void ensure_pinned(cc_index* h, size_t bytes) {
 }
 
 // Host queries go through the pinned buffer (a pageable source makes the runtime stage and block; 3 KB per query).
+void ensure_queries(cc_index* h, int Q) {
+  if (h->q_cap < Q) { if (h->q_dev) hipFree(h->q_dev); h->q_dev = nullptr; h->q_cap = 0; CC_HIP(hipMalloc((void**)&h->q_dev, (size_t)Q * h->dim * 4 + 256)); h->q_cap = Q; }
+}
+
 void upload_queries(cc_index* h, const float* q, int Q, int on_device, hipStream_t s) {
-  if (h->q_cap < Q) { if (h->q_dev) hipFree(h->q_dev); CC_HIP(hipMalloc((void**)&h->q_dev, (size_t)Q * h->dim * 4 + 256)); h->q_cap = Q; }
+  ensure_queries(h, Q);
   const size_t bytes = (size_t)Q * h->dim * 4;
   if (!on_device && bytes <= h->pin_cap) {
     memcpy(h->pin, q, bytes);
@@ -1091,6 +1207,9 @@ int cc_index_add_described(cc_index* h, const float* emb, int64_t n, int on_devi
     }
     if (cls) CC_HIP(hipMemcpy(h->cls + h->n, cls, (size_t)n * 4, hipMemcpyHostToDevice));
     else CC_HIP(hipMemset(h->cls + h->n, 0xff, (size_t)n * 4));
+    h->grp_host.resize((size_t)h->n); h->trk_host.resize((size_t)h->n);      // what an add that failed half way may have left behind
+    if (groups) h->grp_host.insert(h->grp_host.end(), groups, groups + n); else h->grp_host.insert(h->grp_host.end(), (size_t)n, 0);
+    if (tracks) h->trk_host.insert(h->trk_host.end(), tracks, tracks + n); else h->trk_host.insert(h->trk_host.end(), (size_t)n, -1);
   }
   h->n += n;
   h->n_slots = n_slots;
@@ -1244,6 +1363,15 @@ int remove_impl(cc_index* h, bool by_rows, const uint8_t* drop, int64_t n_rows, 
   }
   CC_HIP(hipGetLastError());
   CC_HIP(hipStreamSynchronize(s));
+  {                                                  // the host copies of grp / trk follow: the same keep rule, the same stable order
+    int64_t d = 0;
+    for (int64_t r = 0; r < n; ++r) {
+      const bool gone = by_rows ? drop[r] != 0 : ((unsigned)h->grp_host[r] < (unsigned)n_groups && drop[h->grp_host[r]] != 0);
+      if (!gone) { h->grp_host[d] = h->grp_host[r]; h->trk_host[d] = h->trk_host[r]; ++d; }
+    }
+    CC_CHECK(d == total, "the host columns and the device disagree about the survivors");
+    h->grp_host.resize((size_t)d); h->trk_host.resize((size_t)d);
+  }
   h->n = total;
   if (removed) *removed = n - total;
   CC_API_END
@@ -1376,12 +1504,92 @@ void rank_keys(cc_index* h, int Q, bool tracks, float min_score, const unsigned 
   }
 }
 
+void check_rows(const cc_index* h, const int64_t* rows, int n) {
+  for (int i = 0; i < n; ++i) CC_CHECK(rows[i] >= 0 && rows[i] < h->n, "a row number outside the index");
+}
+
+LikeRows like_rows(const int64_t* rows, int n) {
+  LikeRows lr; lr.n = n;
+  for (int i = 0; i < CC_LIKE_MAX_ROWS; ++i) lr.r[i] = i < n ? (int)rows[i] : -1;
+  return lr;
+}
+
+// rows (checked by the caller) -> out (n, dim) f32 on the device, one launch of fetch_rows_kernel.  Up to CC_LIKE_MAX_ROWS numbers
+// (every cc_index_rank_like) travel in the kernel arguments: copied at the launch, nothing to keep alive.  A longer list goes
+// through pinned memory.  A call that returns without waiting for the stream (device results) leaves a gather behind that has yet
+// to read it, so that buffer is this function's alone and is rewritten only behind the event recorded after the last such gather.
+void gather_rows(cc_index* h, const int64_t* rows, int n, float* out, hipStream_t s) {
+  if (n <= CC_LIKE_MAX_ROWS && h->n < (1LL << 31)) {
+    hipLaunchKernelGGL(fetch_rows_kernel, dim3((unsigned)n), dim3(64), 0, s, reinterpret_cast<const char*>(h->emb), (const long long*)nullptr, like_rows(rows, n),
+                       (long)h->n, h->dim, h->storage, out);
+    CC_HIP(hipGetLastError());
+    return;
+  }
+  if (!h->rows_ev) CC_HIP(hipEventCreateWithFlags(&h->rows_ev, hipEventDisableTiming));
+  CC_HIP(hipEventSynchronize(h->rows_ev));
+  const size_t bytes = (size_t)n * 8;
+  if (h->rows_pin_cap < bytes) {
+    if (h->rows_pin) hipHostFree(h->rows_pin);
+    h->rows_pin = nullptr; h->rows_pin_cap = 0;
+    size_t cap = 4096;
+    while (cap < bytes) cap *= 2;
+    CC_HIP(hipHostMalloc((void**)&h->rows_pin, cap, hipHostMallocDefault));
+    h->rows_pin_cap = cap;
+  }
+  for (int i = 0; i < n; ++i) h->rows_pin[i] = rows[i];
+  hipLaunchKernelGGL(fetch_rows_kernel, dim3((unsigned)n), dim3(64), 0, s, reinterpret_cast<const char*>(h->emb), (const long long*)h->rows_pin, LikeRows{}, (long)h->n,
+                     h->dim, h->storage, out);
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipEventRecord(h->rows_ev, s));
+}
+
+// The query side of cc_index_rank_like, checked: the rows, and what is excluded (0 nothing, 1 the query rows, 2 group G + slot T).
+struct LikeQuery { const int64_t* rows; int n, exclude, G, T; };
+
+int like_check(cc_index* h, const int64_t* rows, int n_rows, int flags, LikeQuery* like) {
+  CC_API_BEGIN
+  CC_CHECK(h && rows, "null argument");
+  CC_CHECK(n_rows >= 1 && n_rows <= CC_LIKE_MAX_ROWS, "n_rows must be in [1, CC_LIKE_MAX_ROWS]");
+  CC_CHECK((flags & ~(CC_RANK_TRACKS | CC_LIKE_EXCLUDE_ROWS | CC_LIKE_EXCLUDE_TRACK)) == 0, "unknown flag bits");
+  check_rows(h, rows, n_rows);
+  *like = LikeQuery{rows, n_rows, (flags & CC_LIKE_EXCLUDE_TRACK) ? 2 : (flags & CC_LIKE_EXCLUDE_ROWS) ? 1 : 0, 0, -1};
+  if (like->exclude == 2) {
+    CC_CHECK(h->grp_host.size() == (size_t)h->n && h->trk_host.size() == (size_t)h->n, "the host columns are out of step with the index");
+    like->G = h->grp_host[(size_t)rows[0]]; like->T = h->trk_host[(size_t)rows[0]];
+    CC_CHECK(like->T >= 0, "CC_LIKE_EXCLUDE_TRACK needs query rows with a track slot");
+    for (int i = 1; i < n_rows; ++i)
+      CC_CHECK(h->grp_host[(size_t)rows[i]] == like->G && h->trk_host[(size_t)rows[i]] == like->T, "CC_LIKE_EXCLUDE_TRACK needs query rows of one group and one track slot");
+  }
+  CC_API_END
+}
+
+// What cc_index_rank_like runs where cc_index_rank_where uploads and scores its queries: gather, score, fold (+ the dead bytes).
+// Leaves the folded vector in row 0 of h->scores and, with an exclusion, w.dead set.  One query row and no exclusion: no fold.
+void like_scores(cc_index* h, const LikeQuery& like, RowWhere& w, hipStream_t s) {
+  const long n = (long)h->n;
+  ensure_queries(h, like.n);
+  gather_rows(h, like.rows, like.n, h->q_dev, s);
+  compute_scores(h, like.n, s);
+  if (like.n == 1 && !like.exclude) return;
+  unsigned char* dead = nullptr;
+  if (like.exclude) { ensure((void**)&h->dead, &h->dead_cap, (size_t)n); w.dead = dead = h->dead; }
+  const LikeRows lr = like_rows(like.rows, like.n);  // n < 2^31 (checked by rank())
+  if (n % 4 == 0)
+    hipLaunchKernelGGL(like_fold_kernel<true>, dim3((unsigned)std::min<long>((n / 4 + 255) / 256, 256 * 8)), dim3(256), 0, s, h->scores, like.n, n, h->grp, h->trk, lr,
+                       like.exclude, like.G, like.T, dead);
+  else
+    hipLaunchKernelGGL(like_fold_kernel<false>, dim3((unsigned)std::min<long>((n + 255) / 256, 256 * 8)), dim3(256), 0, s, h->scores, like.n, n, h->grp, h->trk, lr,
+                       like.exclude, like.G, like.T, dead);
+  CC_HIP(hipGetLastError());
+}
+
 // cc_index_rank / cc_index_rank_where.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
 // init, eight times (histogram, pick), collect, emit.  Answers past the last row the index could give are padded by one fill.
+// like (cc_index_rank_like; Q is 1 and q unused): the score vector comes from like_scores instead, everything behind it is the same.
 int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
-         const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
+         const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream, const LikeQuery* like = nullptr) {
   CC_API_BEGIN
-  CC_CHECK(h && q && idx && score, "null argument");
+  CC_CHECK(h && (q || like) && idx && score, "null argument");
   CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
   CC_CHECK(start >= 0, "start must not be negative");
   CC_CHECK(count >= 1 && count <= (1LL << 40) / Q, "count must be positive (and Q * count below 2^40)");
@@ -1390,7 +1598,7 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
   CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");       // keys hold ~row and ~(n + row) in 32 bits
   const bool tracks = (flags & CC_RANK_TRACKS) != 0;
-  const RowWhere w = make_where(h, where);
+  RowWhere w = make_where(h, where);
   CC_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const long n = (long)h->n;
@@ -1424,8 +1632,11 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
     hipLaunchKernelGGL(rank_pad_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, sc_out, ob);
   if (n > 0) {
     const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    upload_queries(h, q, Q, on_device, s);
-    compute_scores(h, Q, s);
+    if (like) like_scores(h, *like, w, s);
+    else {
+      upload_queries(h, q, Q, on_device, s);
+      compute_scores(h, Q, s);
+    }
     rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
     const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
     const int T = std::max(h->n_slots, 1);
@@ -1535,6 +1746,31 @@ int cc_index_timeline(cc_index* h, const float* q, int Q, float min_score, int f
   return timeline(h, q, Q, min_score, flags, allowed, n_groups, where, t0, bin_seconds, n_bins, counts, total, on_device, stream);
 }
 
+int cc_index_fetch_rows(cc_index* h, const int64_t* rows, int n, float* out, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && rows && out, "null argument");
+  CC_CHECK(n >= 1 && n <= 65535, "n must be in [1, 65535]");
+  check_rows(h, rows, n);
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  if (on_device) gather_rows(h, rows, n, out, s);
+  else {                                             // a host caller: gathered where queries stand, then one copy down
+    ensure_queries(h, n);
+    gather_rows(h, rows, n, h->q_dev, s);
+    CC_HIP(hipMemcpyAsync(out, h->q_dev, (size_t)n * h->dim * 4, hipMemcpyDeviceToHost, s));
+    CC_HIP(hipStreamSynchronize(s));
+  }
+  CC_API_END
+}
+
+int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t start, int64_t count, float min_score, int flags,
+                       const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                       int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
+  LikeQuery like{};
+  if (const int rc = like_check(h, rows, n_rows, flags, &like)) return rc;
+  return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &like);
+}
+
 int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
 
 int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed) { return remove_impl(h, false, drop, 0, n_groups, removed); }
@@ -1544,8 +1780,10 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
+  if (h->rows_ev) { hipEventSynchronize(h->rows_ev); hipEventDestroy(h->rows_ev); }
+  if (h->rows_pin) hipHostFree(h->rows_pin);
   pool_stream_put(h->device, h->stream);                  // parked, never destroyed (kernels.h)
   delete h;
 }

@@ -165,6 +165,21 @@ def row_filter(ts_range=None, classes=None) -> Optional["_lib.RowFilter"]:
     return f
 
 
+def pick_track_rows(row: int, members) -> np.ndarray:
+    """The query rows of `ObjectFinder.similar(..., whole_track=True)`: `members` are the rows of the clicked crop's track (`row`
+    among them).  Up to _lib.LIKE_MAX_ROWS rows: all of them.  More: the clicked row plus 63 of the m - 1 others, those at
+    positions np.linspace(0, m - 2, 63).round() of the others in row order, so the pick spans the whole track, is the same on every
+    call and never drops the clicked crop.  Ascending, distinct."""
+    m = np.unique(np.asarray(members, np.int64))
+    if int(row) not in m:
+        raise ValueError("the clicked row is not among the track's rows")
+    if m.size <= _lib.LIKE_MAX_ROWS:
+        return m
+    others = m[m != int(row)]
+    at = np.linspace(0, others.size - 1, _lib.LIKE_MAX_ROWS - 1).round().astype(np.int64)
+    return np.sort(np.r_[others[at], np.int64(row)])
+
+
 class EmbeddingIndex:
     """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores), "bf16" (half the
     bytes per scan, scores within ~1e-3 for unit vectors; dim % 256 == 0 and at most 40960) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
@@ -362,6 +377,91 @@ class EmbeddingIndex:
         args = (int(start), int(count), float(self.cut_f32(min_score)), 1 if tracks else 0)
         return self._search_device("cc_index_rank", q, int(count), allowed, args, with_total, self.row_filter(ts_range, classes))
 
+    # -- query by stored rows: the queries are rows of this matrix (cc_index_fetch_rows / cc_index_rank_like) ------------------------
+    LIKE_EXCLUDE = {None: 0, "rows": _lib.LIKE_EXCLUDE_ROWS, "track": _lib.LIKE_EXCLUDE_TRACK}
+
+    @staticmethod
+    def _row_numbers(rows) -> np.ndarray:
+        a = np.asarray(rows)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError("row numbers must be integers")
+        return np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
+
+    def _run_stream(self, dev):
+        """(current torch stream, the stream to hand to the library).  torch's default stream has the handle 0, which the library
+        reads as "no stream given" (it then runs on the index's own stream, which nothing orders against torch): the work runs on a
+        side stream fenced by the current one instead; the caller fences the other side (`cur.wait_stream(run)`) behind its call."""
+        import torch
+        cur = run = torch.cuda.current_stream(dev)
+        if cur.cuda_stream == 0:
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = torch.cuda.Stream(dev)
+            run = self._side_stream
+            run.wait_stream(cur)
+        return cur, run
+
+    def fetch(self, rows, device_out: bool = False):
+        """What the index holds for `rows` (numbers in any order, repeats allowed, at least one), decoded -> (n, dim) float32:
+        f32 rows as they were added, bf16 rows as the bf16 values, i8 rows as code * scale.  One gather on the device
+        (cc_index_fetch_rows).  device_out: a CUDA torch tensor on the current torch stream, nothing waited for.  A number outside
+        the index is an error."""
+        ids = self._row_numbers(rows)
+        if not device_out:
+            out = np.empty((ids.size, self.dim), np.float32)
+            _lib.check(_lib.lib().cc_index_fetch_rows(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _lib.ptr(out), 0, None))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((ids.size, self.dim), dtype=torch.float32, device=dev)
+        cur, run = self._run_stream(dev)
+        _lib.check(_lib.lib().cc_index_fetch_rows(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _lib.ptr(out), 1, C.c_void_p(run.cuda_stream)))
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    def _rank_like(self, rows, start, count, allowed, min_score, tracks, exclude, where, out, total, on_device, stream):
+        if exclude not in self.LIKE_EXCLUDE:
+            raise ValueError('exclude: None, "rows" or "track"')
+        ids = self._row_numbers(rows)
+        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        flags = (_lib.RANK_TRACKS if tracks else 0) | self.LIKE_EXCLUDE[exclude]
+        _lib.check(_lib.lib().cc_index_rank_like(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), int(start), int(count),
+                                                 float(self.cut_f32(min_score)), flags, _lib.ptr(al) if al is not None else None,
+                                                 0 if al is None else int(al.size), C.byref(where) if where is not None else None,
+                                                 _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(total) if total is not None else None, on_device, stream))
+
+    def rank_like(self, rows, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, exclude=None, ts_range=None,
+                  classes=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`rank` for ONE query made of 1 .. 64 stored rows ("more like this crop", or like any crop of this track) -> (idx
+        (1, count) int32, score (1, count) f32, total (1,) int64).  A row's score is its best score against any of `rows`
+        (scored as `scores(fetch(rows))` scores them, by the same kernel route), and that vector is ranked exactly as `rank`
+        ranks a query's: same answers per track, tie rules, cut, filters and padding.  exclude="rows": the query rows do not
+        compete; "track": no row of their directory group and track slot does (they must share one group and one slot >= 0).
+        A copy of an excluded crop elsewhere still answers, with the same score.  No embedding leaves or enters the GPU
+        (cc_index_rank_like)."""
+        where = self.row_filter(ts_range, classes)
+        start, count = int(start), int(count)
+        shape = (1, count) if count >= 1 and start >= 0 else (1, 1)                 # the library names the error
+        idx, sc, total = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
+        self._rank_like(rows, start, count, allowed, min_score, tracks, exclude, where, (idx, sc), total, 0, None)
+        return idx, sc, total
+
+    def rank_like_device(self, rows, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, exclude=None,
+                         with_total: bool = True, ts_range=None, classes=None):
+        """`rank_like` with idx / score left on the GPU, as `rank_device` leaves them; with_total=False waits for nothing."""
+        import torch
+        where = self.row_filter(ts_range, classes)
+        dev = torch.device("cuda", self.device)
+        k = max(int(count), 1)
+        idx = torch.empty((1, k), dtype=torch.int32, device=dev)
+        sc = torch.empty((1, k), dtype=torch.float32, device=dev)
+        total = np.zeros(1, np.int64) if with_total else None
+        cur, run = self._run_stream(dev)
+        self._rank_like(rows, start, count, allowed, min_score, tracks, exclude, where, (idx, sc), total, 1, C.c_void_p(run.cuda_stream))
+        if run is not cur:
+            cur.wait_stream(run)
+        return idx, sc, total
+
     def timeline(self, q, t0: int, bin_seconds: int, n_bins: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
                  classes=None) -> Tuple[np.ndarray, np.ndarray]:
         """How the answers of `rank` (same arguments) spread over time -> (counts (Q, n_bins) int64, total (Q,) int64), in one call
@@ -398,14 +498,7 @@ class EmbeddingIndex:
         qa = q.contiguous().float().reshape(-1, self.dim)
         idx = torch.empty((qa.shape[0], k), dtype=torch.int32, device=dev)
         sc = torch.empty((qa.shape[0], k), dtype=torch.float32, device=dev)
-        cur = run = torch.cuda.current_stream(dev)
-        if cur.cuda_stream == 0:
-            # torch's default stream has the handle 0, which the library reads as "no stream given" (it then runs on the index's own
-            # stream, which nothing orders against torch): run on a side stream fenced by the current one on both sides instead
-            if getattr(self, "_side_stream", None) is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            run = self._side_stream
-            run.wait_stream(cur)
+        cur, run = self._run_stream(dev)
         # nothing waits for the stream here: the filter bytes stay referenced until the next call replaces them
         al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
         total = np.zeros(qa.shape[0], np.int64) if with_total else None
@@ -457,6 +550,11 @@ class _RowTable:
         self.slot: List[int] = []              # slot per row, -1 where oid is None: what the device reduces by (EmbeddingIndex.search_tracks)
         self.ts: List[int] = []                # seconds into the day's recording per row (event_img_info's `ts`), _lib.ROW_NO_TS = none
         self.cls: List[int] = []               # detector class per row (event_img_info's `class_id`) in [0, 255], -1 = none
+        self.row: Dict[str, int] = {}          # path -> row; a path stored twice names its last row (the reference's dict keeps the last value of a key)
+
+    def row_of(self, path: str) -> int:
+        """The row that holds `path` (a stored key, exactly as it was given); KeyError when there is none."""
+        return self.row[path]
 
     @staticmethod
     def name_attrs(path: str) -> Tuple[int, int]:
@@ -496,9 +594,11 @@ class _RowTable:
 
     def extend(self, paths) -> np.ndarray:
         groups = np.empty(len(paths), np.int32)
+        base = len(self.paths)
         for i, p in enumerate(paths):
             g, oid = self.describe(p)
             groups[i] = g
+            self.row[p] = base + i
             self.group.append(g); self.oid.append(oid)
             self.slot.append(-1 if oid is None else self.slot_of.setdefault(oid, len(self.slot_of)))
             ts, c = self.name_attrs(p)
@@ -551,6 +651,7 @@ class _RowTable:
         self.slot = [self.slot[r] for r in keep]
         self.ts = [self.ts[r] for r in keep]
         self.cls = [self.cls[r] for r in keep]
+        self.row = {p: r for r, p in enumerate(self.paths)}
         for g in lost:
             self.truthy[g] = self.bad[g] = False
         for r, g in enumerate(self.group):
@@ -1138,17 +1239,27 @@ class ObjectFinder:
         results.sort(key=lambda x: x[1], reverse=True)
         return results
 
+    def _is_attached(self, is_face) -> bool:
+        return getattr(self, "_attached", False) and not is_face and len(self._dev["store"][1].paths) > 0
+
+    def _has_rows(self, is_face) -> bool:
+        return bool(self.face_embeddings if is_face else self.image_embeddings) or self._is_attached(is_face)
+
+    def _index_and_table(self, is_face):
+        """The device matrix a search runs on and its row table: the attached store, or the one built from the reference's dict."""
+        if self._is_attached(is_face):
+            return self._dev["store"]
+        return self._device_index(self.face_embeddings if is_face else self.image_embeddings, "face" if is_face else "image")
+
     def _search_setup(self, query, cam_name, timestamp, text_embedding, is_face):
         """What `search` and `search_page` share: -> (q, index, table, allowed) or None when there is nothing to search."""
-        embeddings = self.face_embeddings if is_face else self.image_embeddings
-        attached = getattr(self, "_attached", False) and not is_face and len(self._dev["store"][1].paths) > 0
-        if not embeddings and not attached:
+        if not self._has_rows(is_face):
             print("No embeddings available.")
             return None
         if text_embedding is None:
             text_embedding = self.model._encode_text(query).numpy()
         q = np.asarray(as_numpy(text_embedding), np.float32).reshape(-1)
-        index, table = self._dev["store"] if attached else self._device_index(embeddings, "face" if is_face else "image")
+        index, table = self._index_and_table(is_face)
         if q.size != index.dim:
             raise ValueError(f"query has {q.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
         return q, index, table, table.allowed(cam_name, timestamp)
@@ -1184,6 +1295,74 @@ class ObjectFinder:
             return kept[start:start + count], len(kept)
         kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
         idx, sc, total = index.rank(q, start, min(count, len(table.paths)), allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
+        return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
+
+    def _stored_row(self, table: "_RowTable", path: str) -> int:
+        """The row of a stored crop named by its key, or by the endpoint's '/<cam>/objects/<day>/<file>' under base_path."""
+        names = [path]
+        if path.startswith("/"):
+            names += [os.path.join(self.base_path, path.lstrip("/")), self.base_path.rstrip("/\\") + path]
+        for name in names:
+            if name in table.row:
+                return table.row_of(name)
+        raise KeyError(path)
+
+    def similar(self, path, start=0, count=100, cam_name=None, timestamp=None, is_face=False, min_score=None, ts_range=None, classes=None,
+                whole_track=False, exclude=None):
+        """"More like this stored crop": what the search endpoint answers for `similar_img` (clearcam.py:1112-1114 -> `run_clip`,
+        :671-675) -> (results, total) as `search_page` returns them.  The reference reads the jpg back, preprocesses and embeds it
+        again; here the embedding is the row the index already holds, gathered on the device (`EmbeddingIndex.rank_like`): no file
+        is read and no model runs.  `path`: the crop's stored key, or the endpoint's '/<cam>/objects/<day>/<file>' (joined to
+        base_path); an unknown one raises KeyError.  Folders, cut, row filter and grouping per track are `search_page`'s.
+        whole_track=True: the query is every crop of the clicked crop's track (same folder and track id; at most 64 of them,
+        `pick_track_rows`), and a crop scores by its best match among them - a track seen from several sides finds what one crop
+        of it would miss.  A crop without a track id stands alone.  exclude="rows": the query crops are not answers; "track":
+        no crop of the clicked track is ("rows" for a crop without a track id)."""
+        where = row_filter(ts_range, classes)
+        start, count = int(start), int(count)
+        if start < 0 or count < 1:
+            raise ValueError("similar needs start >= 0 and count >= 1")
+        if min_score is not None and min_score != min_score:
+            raise ValueError("min_score is NaN")
+        if exclude not in (None, "rows", "track"):
+            raise ValueError('exclude: None, "rows" or "track"')
+        if not self._has_rows(is_face):
+            print("No embeddings available.")
+            return [], 0
+        index, table = self._index_and_table(is_face)
+        row = self._stored_row(table, path)
+        if not hasattr(index, "rank_like"):
+            raise RuntimeError("this index cannot be queried by its stored rows")
+        group, slot = table.group[row], table.slot[row]
+        rows = np.array([row], np.int64)
+        if slot < 0:
+            exclude = "rows" if exclude == "track" else exclude
+        elif whole_track:
+            rows = pick_track_rows(row, np.flatnonzero((np.asarray(table.group) == group) & (np.asarray(table.slot) == slot)))
+        allowed = table.allowed(cam_name, timestamp)
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return [], 0
+        grouped = any(table.truthy[g] for g in live)
+        if any(table.bad[g] for g in live):
+            # names the reference raises on: `search` with the clicked row's embedding raises the same way.  Where a row filter hides
+            # those names from it, the answer is ranked on the host from the index's own scores.
+            q = index.fetch(rows)
+            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q[list(rows).index(row)], is_face=is_face,
+                               ts_range=ts_range, classes=classes)
+            if len(rows) > 1 or exclude:
+                v = index.scores(q).max(axis=0)
+                ok = table.passing(where)
+                if exclude == "track":
+                    ok &= ~((np.asarray(table.group) == group) & (np.asarray(table.slot) == slot))
+                elif exclude == "rows":
+                    ok[rows] = False
+                cand = [r for r in range(len(table.paths)) if allowed[table.group[r]] and ok[r]]
+                full = self._rank(table, cand, [float(v[r]) for r in cand], grouped)
+            kept = [r for r in full if min_score is None or not r[1] < min_score]
+            return kept[start:start + count], len(kept)
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        idx, sc, total = index.rank_like(rows, start, min(count, len(table.paths)), allowed, min_score, tracks=grouped, exclude=exclude, **kw)
         return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
 
     def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False, ts_range=None, classes=None):

@@ -528,6 +528,39 @@ int cc_index_rank_where(cc_index* h, const float* q, int Q, int64_t start, int64
 int cc_index_timeline(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups,
                       const cc_row_filter* where, int32_t t0, int32_t bin_seconds, int n_bins,
                       uint32_t* counts, int64_t* total, int on_device, void* stream);
+/* What the index holds for some rows, decoded to f32: rows = n numbers on the HOST, any order, repeats allowed, 1 <= n <= 65535
+ * -> out (n, dim) f32 on the host or the device (on_device).  f32 rows: the bytes as they are; bf16 rows: the 16 bits in the high
+ * half of the word; CC_INDEX_I8 rows: the decoded element of the rule above, (float)code_i * s_g (one f32 multiply).  One gather
+ * launch on `stream` (NULL: the handle's own); a host `out` waits for it.  Up to CC_LIKE_MAX_ROWS numbers travel in the kernel
+ * arguments, a longer list through pinned memory.  A number outside [0, size), or n outside the range: -22, out untouched. */
+int cc_index_fetch_rows(cc_index* h, const int64_t* rows, int n, float* out, int on_device, void* stream);
+/* "More like these stored rows": the queries are rows of the index itself, gathered on the device (no embedding crosses the bus
+ * in either direction), and a row's score is its best score against any of them.  ONE answer list comes back: idx / score of
+ * `count` entries and one total.
+ *   1. Q = cc_index_fetch_rows(rows), n_rows queries in the order given.
+ *   2. S (n_rows, N) is bit for bit what cc_index_scores(h, Q, n_rows) returns, by the same route for that batch size and index size
+ *      (scan passes, the f32 / bf16 GEMM, the int8 MFMA kernel); cc_index_last_path reports it.
+ *   3. v[r] = max over q of S[q][r], the maximum in the total order of the ranking keys (+0 beats -0; NaN is not supported).
+ *   4. A row is out of the running when it is dead (the exclude flags below), when `allowed` forbids its group or when `where`
+ *      rejects it.
+ *   5. The result is that of cc_index_rank_where for a single query whose score vector is v, among the rows left: the same keys and
+ *      tie rules (a track's place is its first competing row, slot-less rows behind tracks of equal score), the same min_score
+ *      cut, total, -1 / -inf padding, on_device and stream semantics.  It answers as an index built from the competing rows would.
+ *   6. flags: CC_RANK_TRACKS and the two exclude bits.  CC_LIKE_EXCLUDE_ROWS: the query rows are dead.  CC_LIKE_EXCLUDE_TRACK: every
+ *      row that shares BOTH the group and the track slot of the query rows is dead, and so are the query rows (TRACK implies ROWS).
+ *      A byte-equal copy of a dead row elsewhere still competes, with the dead row's score.
+ *   7. Errors (-22, nothing changed): those of cc_index_rank_where; n_rows outside [1, CC_LIKE_MAX_ROWS]; a row number outside
+ *      [0, size); unknown flag bits; CC_LIKE_EXCLUDE_TRACK when the query rows do not all share one group and one slot >= 0.
+ *   8. The row numbers, and for CC_LIKE_EXCLUDE_TRACK the group and the slot of the query rows, are checked on the host before any
+ *      launch (the handle keeps a host copy of the two columns, 8 bytes a row): an error costs no device work and no wait.
+ * With one query row and no exclude bit the launches are those of cc_index_rank_where for one device query behind a gather of one
+ * row; otherwise one more pass folds S into v in place and writes the dead bytes. */
+#define CC_LIKE_MAX_ROWS 64
+#define CC_LIKE_EXCLUDE_ROWS  2   /* the query rows do not compete */
+#define CC_LIKE_EXCLUDE_TRACK 4   /* no row that shares BOTH group and track slot with the query rows competes */
+int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t start, int64_t count, float min_score, int flags,
+                       const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                       int32_t* idx, float* score, int64_t* total, int on_device, void* stream);
 /* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
  * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
  * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
