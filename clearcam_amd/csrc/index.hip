@@ -69,6 +69,9 @@ struct cc_index {
   long long* rows_pin = nullptr; size_t rows_pin_cap = 0;      // pinned, device-visible: the row numbers of a gather of more than CC_LIKE_MAX_ROWS rows, read by fetch_rows_kernel
   hipEvent_t rows_ev = nullptr;                                // recorded behind that gather: rows_pin is rewritten only after it
   std::vector<int32_t> grp_host, trk_host;                     // the grp / trk columns on the host (n each): CC_LIKE_EXCLUDE_TRACK is checked without a device round trip
+  // distinct ranking (cc_index_gram / cc_index_distinct, kernels in index_distinct.hip)
+  char* dist_ws = nullptr; size_t dist_ws_cap = 0;             // per list: squeezed rows, their places, the bit matrix, the counts (distinct_ws)
+  char* dist_io = nullptr; size_t dist_io_cap = 0;             // a host caller's lists and answers, or its Gram matrix, on the device
 };
 
 namespace {
@@ -241,8 +244,6 @@ constexpr int kI8Rows = 4;                                        // groups of f
 // p50 in ms, forced scan / MFMA kernel): Q = 8 0.43 / 0.35, 16 0.80 / 0.38, 24 1.18 / 0.48, 32 1.56 / 0.52, 48 2.33 / 0.65, 64 3.10 / 0.82,
 // 128 6.18 / 1.54, 256 12.3 / 3.05: the MFMA kernel is never the slower one, so the threshold is the lowest the contract allows.
 constexpr int kI8MfmaFrom = 18;
-
-__device__ __forceinline__ float i8_code(unsigned w, int b) { return (float)((int)(w << (24 - 8 * b)) >> 24); }
 
 template <int QB>
 __global__ __launch_bounds__(256) void scan_i8_kernel(const char* __restrict__ emb, const float* __restrict__ q, float* __restrict__ out,
@@ -791,20 +792,12 @@ __global__ __launch_bounds__(64) void fetch_rows_kernel(const char* __restrict__
     for (int c = lane; c < (dim >> 2); c += 64) o[c] = e[c];
   } else if (storage == BF16) {
     const uint4* e = reinterpret_cast<const uint4*>(emb + (size_t)r * dim * 2);
-    for (int c = lane; c < (dim >> 3); c += 64) {
-      const uint4 v = e[c];
-      o[2 * c] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-      o[2 * c + 1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u));
-    }
+    for (int c = lane; c < (dim >> 3); c += 64)
+      decode_bf16_piece(e[c], o + 2 * c);
   } else {
     const char* e = emb + (size_t)r * ((size_t)dim + (dim >> 3));
-    for (int c = lane; c < (dim >> 4); c += 64) {
-      const uint4 v = reinterpret_cast<const uint4*>(e)[c];
-      const float s = reinterpret_cast<const float*>(e + dim)[c >> 1];
-      const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[4 * c + k] = make_float4(i8_code(w[k], 0) * s, i8_code(w[k], 1) * s, i8_code(w[k], 2) * s, i8_code(w[k], 3) * s);
-    }
+    for (int c = lane; c < (dim >> 4); c += 64)
+      decode_i8_piece(reinterpret_cast<const uint4*>(e)[c], reinterpret_cast<const float*>(e + dim)[c >> 1], o + 4 * c);
   }
 }
 
@@ -1514,17 +1507,8 @@ LikeRows like_rows(const int64_t* rows, int n) {
   return lr;
 }
 
-// rows (checked by the caller) -> out (n, dim) f32 on the device, one launch of fetch_rows_kernel.  Up to CC_LIKE_MAX_ROWS numbers
-// (every cc_index_rank_like) travel in the kernel arguments: copied at the launch, nothing to keep alive.  A longer list goes
-// through pinned memory.  A call that returns without waiting for the stream (device results) leaves a gather behind that has yet
-// to read it, so that buffer is this function's alone and is rewritten only behind the event recorded after the last such gather.
-void gather_rows(cc_index* h, const int64_t* rows, int n, float* out, hipStream_t s) {
-  if (n <= CC_LIKE_MAX_ROWS && h->n < (1LL << 31)) {
-    hipLaunchKernelGGL(fetch_rows_kernel, dim3((unsigned)n), dim3(64), 0, s, reinterpret_cast<const char*>(h->emb), (const long long*)nullptr, like_rows(rows, n),
-                       (long)h->n, h->dim, h->storage, out);
-    CC_HIP(hipGetLastError());
-    return;
-  }
+// rows -> h->rows_pin, once the last launch that read it is through.  The caller launches its reader and records h->rows_ev behind it.
+void pin_rows(cc_index* h, const int64_t* rows, int n) {
   if (!h->rows_ev) CC_HIP(hipEventCreateWithFlags(&h->rows_ev, hipEventDisableTiming));
   CC_HIP(hipEventSynchronize(h->rows_ev));
   const size_t bytes = (size_t)n * 8;
@@ -1537,6 +1521,20 @@ void gather_rows(cc_index* h, const int64_t* rows, int n, float* out, hipStream_
     h->rows_pin_cap = cap;
   }
   for (int i = 0; i < n; ++i) h->rows_pin[i] = rows[i];
+}
+
+// rows (checked by the caller) -> out (n, dim) f32 on the device, one launch of fetch_rows_kernel.  Up to CC_LIKE_MAX_ROWS numbers
+// (every cc_index_rank_like) travel in the kernel arguments: copied at the launch, nothing to keep alive.  A longer list goes
+// through pinned memory.  A call that returns without waiting for the stream (device results) leaves a gather behind that has yet
+// to read it, so that buffer is this function's alone and is rewritten only behind the event recorded after the last such gather.
+void gather_rows(cc_index* h, const int64_t* rows, int n, float* out, hipStream_t s) {
+  if (n <= CC_LIKE_MAX_ROWS && h->n < (1LL << 31)) {
+    hipLaunchKernelGGL(fetch_rows_kernel, dim3((unsigned)n), dim3(64), 0, s, reinterpret_cast<const char*>(h->emb), (const long long*)nullptr, like_rows(rows, n),
+                       (long)h->n, h->dim, h->storage, out);
+    CC_HIP(hipGetLastError());
+    return;
+  }
+  pin_rows(h, rows, n);
   hipLaunchKernelGGL(fetch_rows_kernel, dim3((unsigned)n), dim3(64), 0, s, reinterpret_cast<const char*>(h->emb), (const long long*)h->rows_pin, LikeRows{}, (long)h->n,
                      h->dim, h->storage, out);
   CC_HIP(hipGetLastError());
@@ -1771,6 +1769,59 @@ int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t sta
   return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &like);
 }
 
+// Distinct ranking: the kernels are index_distinct.hip's (its head tells how they fit together); here the checks, the scratch and the copies.
+int cc_index_gram(cc_index* h, const int64_t* rows, int n, float* out, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && rows && out, "null argument");
+  CC_CHECK(n >= 1 && n <= CC_DISTINCT_MAX_DEPTH, "n must be in [1, CC_DISTINCT_MAX_DEPTH]");
+  check_rows(h, rows, n);
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  float* dst = out;
+  if (!on_device) { ensure((void**)&h->dist_io, &h->dist_io_cap, (size_t)n * n * 4); dst = reinterpret_cast<float*>(h->dist_io); }
+  pin_rows(h, rows, n);
+  launch_index_gram(h->emb, (long)h->n, h->dim, h->storage, (const long long*)h->rows_pin, n, dst, s);
+  CC_HIP(hipEventRecord(h->rows_ev, s));
+  if (!on_device) {
+    CC_HIP(hipMemcpyAsync(out, dst, (size_t)n * n * 4, hipMemcpyDeviceToHost, s));
+    CC_HIP(hipStreamSynchronize(s));
+  }
+  CC_API_END
+}
+
+int cc_index_distinct(cc_index* h, const int32_t* idx, const float* score, int Q, int depth, float same_at, int64_t start, int64_t count,
+                      int32_t* out_idx, float* out_score, int32_t* out_dups, int64_t* total, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && idx && out_idx && (out_score || !score), "null argument");
+  CC_CHECK(same_at == same_at, "same_at is NaN");
+  CC_CHECK(depth >= 1 && depth <= CC_DISTINCT_MAX_DEPTH, "depth must be in [1, CC_DISTINCT_MAX_DEPTH]");
+  CC_CHECK(Q >= 1 && Q <= CC_DISTINCT_MAX_Q, "Q must be in [1, CC_DISTINCT_MAX_Q]");
+  CC_CHECK(start >= 0, "start must not be negative");
+  CC_CHECK(count >= 1 && count <= (1LL << 40) / Q, "count must be positive (and Q * count below 2^40)");
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  ensure((void**)&h->dist_ws, &h->dist_ws_cap, distinct_ws_bytes(Q));
+  const DistinctWs ws = distinct_ws(h->dist_ws, Q);
+  const size_t in = (size_t)Q * depth, on = (size_t)Q * count;
+  if (on_device) {
+    launch_index_distinct(h->emb, (long)h->n, h->dim, h->storage, idx, score, Q, depth, same_at, start, count, ws, out_idx, out_score, out_dups, s);
+  } else {                                           // a host caller: lists up, answers down, five equal-typed planes of one buffer
+    ensure((void**)&h->dist_io, &h->dist_io_cap, (2 * in + 3 * on) * 4);
+    int* d_idx = reinterpret_cast<int*>(h->dist_io); float* d_sc = reinterpret_cast<float*>(d_idx + in);
+    int* o_idx = reinterpret_cast<int*>(d_sc + in); float* o_sc = reinterpret_cast<float*>(o_idx + on); int* o_dups = reinterpret_cast<int*>(o_sc + on);
+    CC_HIP(hipMemcpyAsync(d_idx, idx, in * 4, hipMemcpyHostToDevice, s));
+    if (score) CC_HIP(hipMemcpyAsync(d_sc, score, in * 4, hipMemcpyHostToDevice, s));
+    launch_index_distinct(h->emb, (long)h->n, h->dim, h->storage, d_idx, score ? d_sc : nullptr, Q, depth, same_at, start, count, ws, o_idx, o_sc,
+                          out_dups ? o_dups : nullptr, s);
+    CC_HIP(hipMemcpyAsync(out_idx, o_idx, on * 4, hipMemcpyDeviceToHost, s));
+    if (score) CC_HIP(hipMemcpyAsync(out_score, o_sc, on * 4, hipMemcpyDeviceToHost, s));
+    if (out_dups) CC_HIP(hipMemcpyAsync(out_dups, o_dups, on * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (total) CC_HIP(hipMemcpyAsync(total, ws.kept, (size_t)Q * 8, hipMemcpyDeviceToHost, s));
+  if (total || !on_device) CC_HIP(hipStreamSynchronize(s));
+  CC_API_END
+}
+
 int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
 
 int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed) { return remove_impl(h, false, drop, 0, n_groups, removed); }
@@ -1780,7 +1831,7 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->dist_ws, (void*)h->dist_io}) if (p) hipFree(p);
   if (h->pin) hipHostFree(h->pin);
   if (h->rows_ev) { hipEventSynchronize(h->rows_ev); hipEventDestroy(h->rows_ev); }
   if (h->rows_pin) hipHostFree(h->rows_pin);

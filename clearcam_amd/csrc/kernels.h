@@ -225,6 +225,38 @@ size_t index_i8_mfma_plane_bytes(int dim, int Q);        // the three bf16 plane
 // planes = scratch of index_i8_mfma_plane_bytes(dim, Q).  Two launches on `stream`: the plane split, then the scores.
 void launch_index_i8_mfma(const void* emb, const float* q, void* planes, float* out, long n, int dim, int Q, hipStream_t stream);
 
+// ---- stored index rows decoded to f32 (fetch_rows_kernel in index.hip, the Gram tiles in index_distinct.hip) ----
+// One 16-byte piece of a stored row -> its floats, the one decode rule of the index: f32 the bytes as they are (4 floats), bf16 the
+// 16 bits moved to the high half (8 floats), int8 (float)code * s with s the scale of the piece's group of 32 (16 floats).
+#if defined(__HIPCC__)
+__device__ __forceinline__ float i8_code(unsigned w, int b) { return (float)((int)(w << (24 - 8 * b)) >> 24); }
+__device__ __forceinline__ void decode_bf16_piece(const uint4 v, float4* o) {
+  o[0] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+  o[1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u));
+}
+__device__ __forceinline__ void decode_i8_piece(const uint4 v, float s, float4* o) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = make_float4(i8_code(w[k], 0) * s, i8_code(w[k], 1) * s, i8_code(w[k], 2) * s, i8_code(w[k], 3) * s);
+}
+#endif
+
+// ---- distinct ranking: pairwise similarities of stored rows and the greedy thinning of ranked lists (index_distinct.hip) ----
+constexpr int kDistinctMaxDepth = 1024;                  // CC_DISTINCT_MAX_DEPTH: rows of one Gram matrix, entries of one list
+constexpr int kDistinctWords = kDistinctMaxDepth / 64;   // 64-bit words in one row of a list's bit matrix
+// Device scratch of a thinning of Q lists: per list the squeezed rows (int64), their places in the list (int32) and the bit matrix; then
+// per list the number of present entries (int32) and of kept ones (int64).  The offsets are distinct_ws's.
+struct DistinctWs { long long* rows; int* pos; unsigned long long* bits; int* present; long long* kept; };
+size_t distinct_ws_bytes(int Q);
+DistinctWs distinct_ws(void* base, int Q);
+// out (n, n) f32 = <row rows[i], row rows[j]> of the stored rows decoded as fetch_rows_kernel decodes them; rows: n numbers the device
+// can read, each inside [0, size) or the row counts as zeros.  One launch.
+void launch_index_gram(const void* emb, long size, int dim, int storage, const long long* rows, int n, float* out, hipStream_t stream);
+// idx (Q, depth) -> out_idx / out_score / out_dups (Q, count) and ws.kept, all on the device (score, out_score, out_dups may be null).
+// Three launches on `stream`: squeeze, Gram tiles compared with same_at into ws.bits, the walk.
+void launch_index_distinct(const void* emb, long size, int dim, int storage, const int* idx, const float* score, int Q, int depth, float same_at,
+                           long long start, long long count, const DistinctWs& ws, int* out_idx, float* out_score, int* out_dups, hipStream_t stream);
+
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;
   float iou_thr;

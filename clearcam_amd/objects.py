@@ -462,6 +462,75 @@ class EmbeddingIndex:
             cur.wait_stream(run)
         return idx, sc, total
 
+    # -- distinct answers: near-duplicate answers of a ranked list folded into the first of them (cc_index_gram / cc_index_distinct) ----
+    def gram(self, rows, device_out: bool = False):
+        """Pairwise similarities of stored rows -> (n, n) float32, out[i][j] = <fetch(rows)[i], fetch(rows)[j]> in f32, 1 <= n <= 1024
+        (cc_index_gram).  A pair's value depends on its two stored rows alone and the matrix equals its transpose bit for bit.
+        device_out: a CUDA torch tensor on the current torch stream, nothing waited for."""
+        ids = self._row_numbers(rows)
+        n = int(ids.size)
+        side = n if 1 <= n <= _lib.DISTINCT_MAX_DEPTH else 1                       # the library names the error
+        if not device_out:
+            out = np.empty((side, side), np.float32)
+            _lib.check(_lib.lib().cc_index_gram(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), n, _lib.ptr(out), 0, None))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((side, side), dtype=torch.float32, device=dev)
+        cur, run = self._run_stream(dev)
+        _lib.check(_lib.lib().cc_index_gram(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), n, _lib.ptr(out), 1, C.c_void_p(run.cuda_stream)))
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    def distinct(self, idx, score=None, same_at: float = 0.9, start: int = 0, count=None):
+        """Thin ranked lists of row numbers -> (idx (Q, count) int32, score (Q, count) f32 or None, dups (Q, count) int32, total (Q,)
+        int64).  idx (Q, depth) or (depth,), depth <= 1024, Q <= 64, in ranked order (e.g. `rank(q, 0, depth)[0]`); entries < 0 or
+        >= len(self) are absent.  Walking a list in order, an entry is kept unless `gram` of it and an entry KEPT before it is
+        >= same_at (float32); a dropped entry is counted in `dups` of the first kept entry that matches it.  The kept entries are
+        the answers: start .. start+count-1 of them come back (count: depth by default), -1 / -inf / 0 past the last, and `total`
+        is their number.  `score` is passed through (cc_index_distinct)."""
+        ia = np.ascontiguousarray(np.asarray(idx), dtype=np.int32)
+        ia = ia.reshape(1, -1) if ia.ndim < 2 else ia.reshape(ia.shape[0], -1)
+        Q, depth = ia.shape
+        count = depth if count is None else int(count)
+        sa = None
+        if score is not None:
+            sa = np.ascontiguousarray(as_numpy(score), dtype=np.float32).reshape(Q, depth)
+        shape = (Q, count) if count >= 1 and Q >= 1 else (1, 1)                    # the library names the error
+        oi, od = np.empty(shape, np.int32), np.empty(shape, np.int32)
+        os_ = np.empty(shape, np.float32) if sa is not None else None
+        total = np.zeros(max(Q, 1), np.int64)
+        _lib.check(_lib.lib().cc_index_distinct(self._h, _lib.ptr(ia), _lib.ptr(sa), Q, depth, float(same_at), int(start), count,
+                                                _lib.ptr(oi), _lib.ptr(os_), _lib.ptr(od), _lib.ptr(total), 0, None))
+        return oi, os_, od, total
+
+    def distinct_device(self, idx, score=None, same_at: float = 0.9, start: int = 0, count=None, with_total: bool = True):
+        """`distinct` for CUDA tensors, e.g. the idx / score of `rank_device` or `rank_like_device`: the answers stay on the GPU, on
+        the current torch stream.  `total` comes back as a host array, which costs one wait for the stream; with_total=False
+        returns None in its place and waits for nothing."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ia = idx.to(device=dev, dtype=torch.int32).contiguous()
+        ia = ia.reshape(1, -1) if ia.dim() < 2 else ia.reshape(ia.shape[0], -1)
+        Q, depth = int(ia.shape[0]), int(ia.shape[1])
+        count = depth if count is None else int(count)
+        sa = None if score is None else score.to(device=dev, dtype=torch.float32).contiguous().reshape(Q, depth)
+        shape = (Q, count) if count >= 1 and Q >= 1 else (1, 1)                    # the library names the error
+        oi = torch.empty(shape, dtype=torch.int32, device=dev)
+        od = torch.empty(shape, dtype=torch.int32, device=dev)
+        os_ = torch.empty(shape, dtype=torch.float32, device=dev) if sa is not None else None
+        total = np.zeros(max(Q, 1), np.int64) if with_total else None
+        cur, run = self._run_stream(dev)
+        _lib.check(_lib.lib().cc_index_distinct(self._h, _lib.ptr(ia), _lib.ptr(sa), Q, depth, float(same_at), int(start), count,
+                                                _lib.ptr(oi), _lib.ptr(os_), _lib.ptr(od), _lib.ptr(total), 1, C.c_void_p(run.cuda_stream)))
+        if run is not cur:
+            cur.wait_stream(run)
+        for t in (ia, sa):                              # inputs made here (a cast or a copy) must outlive the launches that read them
+            if t is not None:
+                t.record_stream(run)
+        return oi, os_, od, total
+
     def timeline(self, q, t0: int, bin_seconds: int, n_bins: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
                  classes=None) -> Tuple[np.ndarray, np.ndarray]:
         """How the answers of `rank` (same arguments) spread over time -> (counts (Q, n_bins) int64, total (Q,) int64), in one call
@@ -1265,7 +1334,7 @@ class ObjectFinder:
         return q, index, table, table.allowed(cam_name, timestamp)
 
     def search_page(self, query=None, start=0, count=100, cam_name=None, timestamp=None, text_embedding=None, is_face=False, min_score=None,
-                    ts_range=None, classes=None):
+                    ts_range=None, classes=None, distinct=None, distinct_depth=1024):
         """One page of the results, what the search endpoint computes (clearcam.py:1108-1118 + `send_results`, :686-705) by asking
         for top_k = start + count, cutting at the first score below 0.21 and slicing: -> (results, total) with
         results == [r for r in search(..., top_k=everything) if not r[1] < min_score][start:start+count] and total the length of
@@ -1273,13 +1342,19 @@ class ObjectFinder:
         ts_range=(first, last) seconds into the day, inclusive, and classes=[ids] narrow the search to the crops whose name
         '<ts>_<track>_<class>.jpg' carries a ts inside the window / one of the classes (`EmbeddingIndex.row_filter`): the result is
         what `search` gives over those crops alone.  Whether answers are grouped per track is decided as without a row filter,
-        from the track ids of ALL crops in the allowed folders, not only of the passing ones."""
+        from the track ids of ALL crops in the allowed folders, not only of the passing ones.
+        distinct=<float>: near-duplicate answers are folded (`EmbeddingIndex.distinct`): the first min(distinct_depth, rows)
+        answers of the ranking above are walked in order on the device and an answer whose stored embedding has a dot product
+        >= distinct with one KEPT before it is dropped - one object under many track ids, days or cameras answers once.  The page
+        is cut from the kept answers: -> ([(path, score, dups)], total), dups the answers folded into that one ("+12 similar") and
+        total the kept answers among those first distinct_depth.  None: exactly the call without it."""
         where = row_filter(ts_range, classes)
         start, count = int(start), int(count)
         if start < 0 or count < 1:
             raise ValueError("search_page needs start >= 0 and count >= 1")
         if min_score is not None and min_score != min_score:
             raise ValueError("min_score is NaN")
+        distinct, distinct_depth = self._distinct_args(distinct, distinct_depth)
         setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
         if setup is None:
             return [], 0
@@ -1292,10 +1367,48 @@ class ObjectFinder:
             full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face,
                                ts_range=ts_range, classes=classes)
             kept = [r for r in full if min_score is None or not r[1] < min_score]
+            if distinct is not None:
+                return self._distinct_host(index, table, kept, distinct, distinct_depth, start, count)
             return kept[start:start + count], len(kept)
         kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        if distinct is not None:
+            depth = min(distinct_depth, len(table.paths))
+            idx, sc, _ = index.rank_device(q, 0, depth, allowed, min_score, tracks=any(table.truthy[g] for g in live), with_total=False, **kw)
+            return self._distinct_page(index, table, idx, sc, distinct, start, count)
         idx, sc, total = index.rank(q, start, min(count, len(table.paths)), allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
         return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
+
+    @staticmethod
+    def _distinct_args(distinct, distinct_depth):
+        """The two arguments of a distinct page, checked before any GPU work -> (None or float, int)."""
+        if distinct is None:
+            return None, distinct_depth
+        distinct = float(distinct)
+        if distinct != distinct:
+            raise ValueError("distinct is NaN")
+        distinct_depth = int(distinct_depth)
+        if not 1 <= distinct_depth <= _lib.DISTINCT_MAX_DEPTH:
+            raise ValueError(f"distinct_depth must be in [1, {_lib.DISTINCT_MAX_DEPTH}]")
+        return distinct, distinct_depth
+
+    @staticmethod
+    def _distinct_page(index, table: "_RowTable", idx, sc, distinct: float, start: int, count: int):
+        """Ranked answers on the device (1, depth) -> the page of the kept ones; only the page leaves the GPU."""
+        oi, os_, od, total = index.distinct_device(idx, sc, distinct, start, min(count, int(idx.shape[-1])))
+        rows, scores, dups = oi[0].cpu().tolist(), os_[0].cpu().numpy(), od[0].cpu().tolist()
+        return [(table.paths[r], float(v), int(d)) for r, v, d in zip(rows, scores, dups) if r >= 0], int(total[0])
+
+    @staticmethod
+    def _distinct_host(index, table: "_RowTable", kept, distinct: float, depth: int, start: int, count: int):
+        """A host-ranked list of (path, score) -> the page of its first `depth` answers thinned by their rows in the index."""
+        if not hasattr(index, "distinct"):
+            raise RuntimeError("this index cannot thin its answers")
+        head = kept[:depth]
+        if not head:
+            return [], 0
+        rows = np.array([table.row_of(p) for p, _ in head], np.int32)
+        oi, os_, od, total = index.distinct(rows, np.array([v for _, v in head], np.float32), distinct, start, min(count, len(head)))
+        return [(table.paths[r], float(v), int(d)) for r, v, d in zip(oi[0].tolist(), os_[0], od[0].tolist()) if r >= 0], int(total[0])
 
     def _stored_row(self, table: "_RowTable", path: str) -> int:
         """The row of a stored crop named by its key, or by the endpoint's '/<cam>/objects/<day>/<file>' under base_path."""
@@ -1308,7 +1421,7 @@ class ObjectFinder:
         raise KeyError(path)
 
     def similar(self, path, start=0, count=100, cam_name=None, timestamp=None, is_face=False, min_score=None, ts_range=None, classes=None,
-                whole_track=False, exclude=None):
+                whole_track=False, exclude=None, distinct=None, distinct_depth=1024):
         """"More like this stored crop": what the search endpoint answers for `similar_img` (clearcam.py:1112-1114 -> `run_clip`,
         :671-675) -> (results, total) as `search_page` returns them.  The reference reads the jpg back, preprocesses and embeds it
         again; here the embedding is the row the index already holds, gathered on the device (`EmbeddingIndex.rank_like`): no file
@@ -1317,13 +1430,15 @@ class ObjectFinder:
         whole_track=True: the query is every crop of the clicked crop's track (same folder and track id; at most 64 of them,
         `pick_track_rows`), and a crop scores by its best match among them - a track seen from several sides finds what one crop
         of it would miss.  A crop without a track id stands alone.  exclude="rows": the query crops are not answers; "track":
-        no crop of the clicked track is ("rows" for a crop without a track id)."""
+        no crop of the clicked track is ("rows" for a crop without a track id).  distinct / distinct_depth: as in `search_page`,
+        the answers then are (path, score, dups)."""
         where = row_filter(ts_range, classes)
         start, count = int(start), int(count)
         if start < 0 or count < 1:
             raise ValueError("similar needs start >= 0 and count >= 1")
         if min_score is not None and min_score != min_score:
             raise ValueError("min_score is NaN")
+        distinct, distinct_depth = self._distinct_args(distinct, distinct_depth)
         if exclude not in (None, "rows", "track"):
             raise ValueError('exclude: None, "rows" or "track"')
         if not self._has_rows(is_face):
@@ -1360,8 +1475,14 @@ class ObjectFinder:
                 cand = [r for r in range(len(table.paths)) if allowed[table.group[r]] and ok[r]]
                 full = self._rank(table, cand, [float(v[r]) for r in cand], grouped)
             kept = [r for r in full if min_score is None or not r[1] < min_score]
+            if distinct is not None:
+                return self._distinct_host(index, table, kept, distinct, distinct_depth, start, count)
             return kept[start:start + count], len(kept)
         kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        if distinct is not None:
+            depth = min(distinct_depth, len(table.paths))
+            idx, sc, _ = index.rank_like_device(rows, 0, depth, allowed, min_score, tracks=grouped, exclude=exclude, with_total=False, **kw)
+            return self._distinct_page(index, table, idx, sc, distinct, start, count)
         idx, sc, total = index.rank_like(rows, start, min(count, len(table.paths)), allowed, min_score, tracks=grouped, exclude=exclude, **kw)
         return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
 

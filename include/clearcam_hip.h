@@ -561,6 +561,42 @@ int cc_index_fetch_rows(cc_index* h, const int64_t* rows, int n, float* out, int
 int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t start, int64_t count, float min_score, int flags,
                        const uint8_t* allowed, int n_groups, const cc_row_filter* where,
                        int32_t* idx, float* score, int64_t* total, int on_device, void* stream);
+/* Distinct answers: thin ranked lists so that the same picture, stored under many track ids, on many days or by many cameras,
+ * answers once.  The embedding-space counterpart of what the detector does with boxes, behind any of the ranking calls above. */
+#define CC_DISTINCT_MAX_DEPTH 1024
+#define CC_DISTINCT_MAX_Q     64
+/* Pairwise similarities of stored rows: rows = n numbers on the HOST, 1 <= n <= CC_DISTINCT_MAX_DEPTH, any order, repeats allowed
+ * -> out (n, n) f32 on the host or the device (on_device): out[i][j] = the f32 dot product of what the index holds for rows[i] and
+ * rows[j], i.e. of the rows cc_index_fetch_rows decodes, for all three storages.  Part of the contract, because cc_index_distinct is
+ * defined on top of it: (a) out[i][j] depends on the two stored rows alone, not on i, j, n or the rest of the list (a byte-equal copy
+ * at another row number gives the same bits); (b) out[i][j] == out[j][i] bit for bit.  The summation order is otherwise free: one
+ * chain of f32 fused multiply-adds over the row (exact f32 MFMA), within the order-free float64 bound of the stored rows.  One launch
+ * on `stream` (NULL: the handle's own); a host `out` waits for it.  A number outside [0, size) or n out of range: -22, out untouched,
+ * checked on the host before any launch. */
+int cc_index_gram(cc_index* h, const int64_t* rows, int n, float* out, int on_device, void* stream);
+/* Thin Q ranked lists: an answer is kept only if it is not "the same picture" as an answer kept before it.
+ *   1. idx (Q, depth) int32: Q lists in the order given (the call does not sort), typically the idx of cc_index_rank* for start 0
+ *      and count = depth.  An entry < 0 or >= size is absent and skipped (each entry is tested on the device), so the -1 padding of
+ *      the ranking calls passes straight through.  score (Q, depth) f32 or NULL is only passed through.  on_device: idx, score and
+ *      the three outputs are device pointers, otherwise all are host pointers.
+ *   2. With c_0, c_1, ... the present entries of a list in order and G = cc_index_gram of them: c_0 is kept; c_j is kept iff no KEPT
+ *      c_i, i < j, has G[i][j] >= same_at (compared in f32).  The greedy rule: a dropped answer suppresses nothing (unlike the
+ *      detector's mask rule).  A dropped c_j is counted to the first (lowest i) kept c_i with G[i][j] >= same_at.
+ *   3. The kept entries in order are the answers.  out_idx / out_score (Q, count) receive answers start .. start+count-1 and -1 / -inf
+ *      past the last; out_score is the input score of the kept entry (ignored when score is NULL).  out_dups (Q, count) int32, may
+ *      be NULL: the dropped entries counted to that answer, 0 in the padding.  total: Q int64 on the HOST, may be NULL: the number
+ *      of kept entries; asking for it waits for the stream, as a host caller always does.
+ *   4. same_at above every similarity drops nothing: the list with its absent entries squeezed out, windowed.  -inf keeps c_0 alone.
+ *   5. A repeated row number in a list is an ordinary pair, G of a row with itself.
+ *   6. Errors (-22, nothing written, no launch): NaN same_at; depth outside [1, CC_DISTINCT_MAX_DEPTH]; Q outside
+ *      [1, CC_DISTINCT_MAX_Q]; start < 0; count < 1 (or Q * count >= 2^40); a NULL idx or out_idx, or a score without an out_score.
+ *   7. The handle's scratch grows on demand (136 KB a list); the index is not modified.  Three launches on `stream`: squeeze, the
+ *      Gram tiles of each list compared with same_at into a bit matrix (the accumulation is cc_index_gram's, so a bit is the
+ *      comparison of the very float cc_index_gram returns), and one sequential walk per list. */
+int cc_index_distinct(cc_index* h, const int32_t* idx, const float* score, int Q, int depth, float same_at,
+                      int64_t start, int64_t count,
+                      int32_t* out_idx, float* out_score, int32_t* out_dups, int64_t* total,
+                      int on_device, void* stream);
 /* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
  * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
  * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
