@@ -72,6 +72,10 @@ struct cc_index {
   // distinct ranking (cc_index_gram / cc_index_distinct, kernels in index_distinct.hip)
   char* dist_ws = nullptr; size_t dist_ws_cap = 0;             // per list: squeezed rows, their places, the bit matrix, the counts (distinct_ws)
   char* dist_io = nullptr; size_t dist_io_cap = 0;             // a host caller's lists and answers, or its Gram matrix, on the device
+  // day digest (cc_index_digest, kernels in index_digest.hip)
+  char* digest_ws = nullptr; size_t digest_ws_cap = 0;         // the competing rows, two bit matrices of a piece, the leader tables (digest_ws)
+  char* digest_io = nullptr; size_t digest_io_cap = 0;         // a host caller's window and owner column on the device
+  int* digest_pin = nullptr;                                   // pinned: the number of competing rows, the call's one readback
 };
 
 namespace {
@@ -394,34 +398,7 @@ __device__ void block_topk(KeyFn key, long count, int K, unsigned long long* sel
   __syncthreads();
 }
 
-__device__ __forceinline__ bool row_allowed(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, long r) {
-  if (!allowed) return true;
-  const unsigned g = (unsigned)grp[r];
-  return g < (unsigned)n_allowed && allowed[g];
-}
-
-// cc_row_filter as the kernels take it (by value, in the kernel arguments): a null column = no filter on that attribute.
-// dead: one byte per row, non-zero = the row is out of the running (cc_index_rank_like's exclusion, written by like_fold_kernel); null
-// everywhere else.
-struct RowWhere { const int* ts; const int* cls; int ts_min, ts_max; unsigned long long m0, m1, m2, m3; const unsigned char* dead; };
-
-// The row competes: its group is allowed, it has the attributes the filter asks for, and it is not dead.  The mask word is chosen by
-// compares, not by an index, so the four words stay in scalar registers.
-__device__ __forceinline__ bool row_passes(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, const RowWhere& w, long r) {
-  if (!row_allowed(grp, allowed, n_allowed, r)) return false;
-  if (w.dead && w.dead[r]) return false;
-  if (w.ts) {
-    const int t = w.ts[r];
-    if (t == CC_ROW_NO_TS || t < w.ts_min || t > w.ts_max) return false;
-  }
-  if (w.cls) {
-    const unsigned c = (unsigned)w.cls[r];
-    if (c > 255u) return false;                                    // -1: no class
-    const unsigned long long m = c < 128u ? (c < 64u ? w.m0 : w.m1) : (c < 192u ? w.m2 : w.m3);
-    if (!((m >> (c & 63u)) & 1ull)) return false;
-  }
-  return true;
-}
+// row_allowed, RowWhere and row_passes (the one rule by which a row competes) stand in kernels.h: the day digest selects by them too.
 
 // Track search, pass 1: every allowed row with a track slot t raises best[q][t] to ordered(score) << 32 | ~row (a 64-bit integer
 // maximum: the best score, and among equal scores the lowest row, whatever the arrival order) and lowers first[t] to its row id.
@@ -1822,6 +1799,62 @@ int cc_index_distinct(cc_index* h, const int32_t* idx, const float* score, int Q
   CC_API_END
 }
 
+// Day digest: the kernels are index_digest.hip's (its head tells how they fit together); here the checks, the scratch, the loop over the
+// pieces and the copies.
+int cc_index_digest(cc_index* h, float same_at, int max_leaders, int order, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                    int64_t start, int64_t count, int32_t* out_row, int32_t* out_count, int32_t* out_ts_first, int32_t* out_ts_last,
+                    int32_t* owner, int64_t* totals, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && out_row, "null argument");
+  CC_CHECK(same_at == same_at, "same_at is NaN");
+  CC_CHECK(max_leaders >= 1 && max_leaders <= CC_DIGEST_MAX_LEADERS, "max_leaders must be in [1, CC_DIGEST_MAX_LEADERS]");
+  CC_CHECK(order == CC_DIGEST_BY_COUNT || order == CC_DIGEST_BY_FIRST, "unknown order");
+  CC_CHECK(start >= 0, "start must not be negative");
+  CC_CHECK(count >= 1, "count must be positive");
+  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  CC_CHECK(h->n < (1LL << 31), "a digest needs fewer than 2^31 rows");       // owner and the outputs hold row numbers in 32 bits
+  const RowWhere w = make_where(h, where);
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const long n = (long)h->n;
+  ensure((void**)&h->digest_ws, &h->digest_ws_cap, digest_ws_bytes(n));
+  const DigestWs ws = digest_ws(h->digest_ws, n);
+  if (!h->digest_pin) CC_HIP(hipHostMalloc((void**)&h->digest_pin, 64, hipHostMallocDefault));
+  // a host caller: no leader stands past entry CC_DIGEST_MAX_LEADERS, so that many entries come down and the rest is padded here
+  const int64_t wn = on_device ? count : std::min<int64_t>(count, CC_DIGEST_MAX_LEADERS);
+  int *o_row = out_row, *o_cnt = out_count, *o_t0 = out_ts_first, *o_t1 = out_ts_last, *o_own = owner;
+  if (!on_device) {
+    ensure((void**)&h->digest_io, &h->digest_io_cap, ((size_t)4 * wn + (owner ? (size_t)n : 0)) * 4);
+    o_row = reinterpret_cast<int*>(h->digest_io); o_cnt = o_row + wn; o_t0 = o_cnt + wn; o_t1 = o_t0 + wn;
+    o_own = owner ? o_t1 + wn : nullptr;
+  }
+  const unsigned char* allowed_dev = n > 0 ? upload_allowed(h, allowed, n_groups, s) : nullptr;
+  launch_digest_select(n, h->grp, allowed_dev, h->allowed_cap, w, ws, o_own, s);
+  CC_HIP(hipMemcpyAsync(h->digest_pin, ws.m, 4, hipMemcpyDeviceToHost, s));
+  CC_HIP(hipStreamSynchronize(s));                                           // the one readback: how many pieces to launch
+  const long m = (long)h->digest_pin[0];
+  for (long first = 0; first < m; first += kDigestChunk)
+    launch_digest_piece(h->emb, n, h->dim, h->storage, first, (int)std::min<long>(kDigestChunk, m - first), same_at, max_leaders, h->ts, ws, o_own, s);
+  launch_digest_finish(ws, order, start, wn, o_row, o_cnt, o_t0, o_t1, s);
+  if (!on_device) {
+    CC_HIP(hipMemcpyAsync(out_row, o_row, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+    if (out_count) CC_HIP(hipMemcpyAsync(out_count, o_cnt, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+    if (out_ts_first) CC_HIP(hipMemcpyAsync(out_ts_first, o_t0, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+    if (out_ts_last) CC_HIP(hipMemcpyAsync(out_ts_last, o_t1, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+    if (owner && n > 0) CC_HIP(hipMemcpyAsync(owner, o_own, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (totals) CC_HIP(hipMemcpyAsync(totals, ws.totals, 3 * 8, hipMemcpyDeviceToHost, s));
+  if (totals || !on_device) CC_HIP(hipStreamSynchronize(s));
+  if (!on_device)
+    for (int64_t p = wn; p < count; ++p) {
+      out_row[p] = -1;
+      if (out_count) out_count[p] = 0;
+      if (out_ts_first) out_ts_first[p] = CC_ROW_NO_TS;
+      if (out_ts_last) out_ts_last[p] = CC_ROW_NO_TS;
+    }
+  CC_API_END
+}
+
 int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
 
 int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed) { return remove_impl(h, false, drop, 0, n_groups, removed); }
@@ -1831,7 +1864,8 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->dist_ws, (void*)h->dist_io}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io}) if (p) hipFree(p);
+  if (h->digest_pin) hipHostFree(h->digest_pin);
   if (h->pin) hipHostFree(h->pin);
   if (h->rows_ev) { hipEventSynchronize(h->rows_ev); hipEventDestroy(h->rows_ev); }
   if (h->rows_pin) hipHostFree(h->rows_pin);

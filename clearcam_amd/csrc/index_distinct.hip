@@ -20,17 +20,16 @@
 //                    first keeper of; they are written back over the row, and their count is its `dups`.  All threads then place
 //                    the kept entries (rank = popcount of the kept bits before them), cut the window and pad it.
 // Nothing here uses atomics: every word and every output has one writer.
-#include "kernels.h"
-#include "mfma.h"
+// The staging, the K loop and the compare epilogue of gram_kernel stand in gram_tile.h: the day digest (index_digest.hip) runs its tiles of
+// rows against leaders through the same code, so that it compares the very floats cc_index_gram returns.
+#include "gram_tile.h"
 #include "../../include/clearcam_hip.h"
 
 namespace cc {
 
 namespace {
 
-constexpr int kTile = 64;                       // rows and columns of a Gram tile: one tile row = one word of the bit matrix
-constexpr int kBK = 64;                         // floats of K staged per step
-constexpr int kLd = kBK + 4;                    // LDS row stride in floats: 16-byte aligned, the 16 rows of a fragment read on 64 distinct banks
+constexpr int kTile = kGramTile, kLd = kGramLd;                               // gram_tile.h: the tile, its staging and its one accumulation
 constexpr size_t kWalkLds = (size_t)kDistinctMaxDepth * kDistinctWords * 8;   // the bit matrix of one list
 
 static_assert(CC_DISTINCT_MAX_DEPTH == kDistinctMaxDepth, "the header and kernels.h disagree");
@@ -53,31 +52,6 @@ __global__ __launch_bounds__(1024) void squeeze_kernel(const int* __restrict__ i
   if (t == 0) present[q] = all;
 }
 
-// 64 rows x kBK floats of K from k0 on -> dst[64][kLd].  A row outside the list or the index, and K past dim, are zeros.
-template <int STORAGE>
-__device__ __forceinline__ void stage_rows(const char* __restrict__ emb, long size, int dim, const long long* srow, int k0, float* dst, int tid) {
-  constexpr int FP = STORAGE == F32 ? 4 : STORAGE == BF16 ? 8 : 16;   // floats in one 16-byte piece of the stored row
-  constexpr int PPR = kBK / FP;
-  for (int e = tid; e < kTile * PPR; e += 256) {
-    const int r = e / PPR, k = k0 + (e % PPR) * FP;
-    float4 f[FP / 4];
-#pragma unroll
-    for (int i = 0; i < FP / 4; ++i) f[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long long row = srow[r];
-    if ((unsigned long long)row < (unsigned long long)size && k < dim) {
-      if (STORAGE == F32) f[0] = *reinterpret_cast<const float4*>(emb + ((size_t)row * dim + k) * 4);
-      else if (STORAGE == BF16) decode_bf16_piece(*reinterpret_cast<const uint4*>(emb + ((size_t)row * dim + k) * 2), f);
-      else {
-        const char* er = emb + (size_t)row * ((size_t)dim + (dim >> 3));
-        decode_i8_piece(*reinterpret_cast<const uint4*>(er + k), reinterpret_cast<const float*>(er + dim)[k >> 5], f);
-      }
-    }
-    float4* o = reinterpret_cast<float4*>(dst + r * kLd + (e % PPR) * FP);
-#pragma unroll
-    for (int i = 0; i < FP / 4; ++i) o[i] = f[i];
-  }
-}
-
 // grid (tiles, tiles, lists), 256 threads: wave w owns the 32 x 32 quadrant (w >> 1, w & 1) of tile (ti = blockIdx.y, tj = blockIdx.x).
 template <int STORAGE, bool BITS>
 __global__ __launch_bounds__(256) void gram_kernel(const char* __restrict__ emb, long size, int dim, const long long* __restrict__ rows, int n_fixed,
@@ -97,29 +71,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const char* __restrict__ emb,
   }
   __syncthreads();
   f32x4 acc[2][2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) acc[m][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < dim; k0 += kBK) {
-    stage_rows<STORAGE>(emb, size, dim, srow, k0, As, tid);
-    stage_rows<STORAGE>(emb, size, dim, srow + kTile, k0, Bs, tid);
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < kBK / 16; ++c) {
-      uint4 a[2], b[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        a[m] = *reinterpret_cast<const uint4*>(As + (wr * 32 + m * 16 + (lane & 15)) * kLd + c * 16 + (lane >> 4) * 4);
-        b[m] = *reinterpret_cast<const uint4*>(Bs + (wc * 32 + m * 16 + (lane & 15)) * kLd + c * 16 + (lane >> 4) * 4);
-      }
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2) Mma<float>::run(a[m], b[c2], acc[m][c2]);
-    }
-    __syncthreads();
-  }
+  gram_tile_accumulate<STORAGE>(emb, size, dim, srow, As, Bs, tid, acc);
   // accumulator element r of tile (m, c2): row (lane >> 4) * 4 + r, column lane & 15
   if (!BITS) {
 #pragma unroll
@@ -136,21 +88,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const char* __restrict__ emb,
           }
         }
   } else {
-    unsigned char* fl = reinterpret_cast<unsigned char*>(As);   // [64][64] answers of the tile; the K loop ended with a barrier
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          fl[(wr * 32 + m * 16 + (lane >> 4) * 4 + r) * kTile + wc * 32 + c2 * 16 + (lane & 15)] = acc[m][c2][r] >= same_at ? 1 : 0;
-    __syncthreads();
-    unsigned long long mine = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned long long word = __ballot(fl[(wave * 16 + r) * kTile + lane] != 0);
-      if (lane == r) mine = word;
-    }
+    const unsigned long long mine = gram_tile_bits(acc, same_at, reinterpret_cast<unsigned char*>(As), tid);   // the K loop ended with a barrier
     const int gi = ti * kTile + wave * 16 + lane;
     if (lane < 16 && gi < n) bits[((size_t)q * kDistinctMaxDepth + gi) * kDistinctWords + tj] = mine;
   }
@@ -257,6 +195,11 @@ DistinctWs distinct_ws(void* base, int Q) {
 
 void launch_index_gram(const void* emb, long size, int dim, int storage, const long long* rows, int n, float* out, hipStream_t stream) {
   launch_gram<false>(emb, size, dim, storage, rows, n, nullptr, 1, out, nullptr, 0.f, stream);
+}
+
+void launch_index_gram_bits(const void* emb, long size, int dim, int storage, const long long* rows, int n, unsigned long long* bits, float same_at,
+                            hipStream_t stream) {
+  launch_gram<true>(emb, size, dim, storage, rows, n, nullptr, 1, nullptr, bits, same_at, stream);
 }
 
 void launch_index_distinct(const void* emb, long size, int dim, int storage, const int* idx, const float* score, int Q, int depth, float same_at,

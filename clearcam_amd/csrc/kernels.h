@@ -241,6 +241,38 @@ __device__ __forceinline__ void decode_i8_piece(const uint4 v, float s, float4* 
 }
 #endif
 
+// ---- which rows compete (index.hip's rankings, index_digest.hip's selection) -----------------------------------------------------
+constexpr int kRowNoTs = INT32_MIN;                      // CC_ROW_NO_TS
+// cc_row_filter as the kernels take it (by value, in the kernel arguments): a null column = no filter on that attribute.
+// dead: one byte per row, non-zero = the row is out of the running (cc_index_rank_like's exclusion, written by like_fold_kernel); null
+// everywhere else.
+struct RowWhere { const int* ts; const int* cls; int ts_min, ts_max; unsigned long long m0, m1, m2, m3; const unsigned char* dead; };
+#if defined(__HIPCC__)
+__device__ __forceinline__ bool row_allowed(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, long r) {
+  if (!allowed) return true;
+  const unsigned g = (unsigned)grp[r];
+  return g < (unsigned)n_allowed && allowed[g];
+}
+
+// The row competes: its group is allowed, it has the attributes the filter asks for, and it is not dead.  The mask word is chosen by
+// compares, not by an index, so the four words stay in scalar registers.
+__device__ __forceinline__ bool row_passes(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, const RowWhere& w, long r) {
+  if (!row_allowed(grp, allowed, n_allowed, r)) return false;
+  if (w.dead && w.dead[r]) return false;
+  if (w.ts) {
+    const int t = w.ts[r];
+    if (t == kRowNoTs || t < w.ts_min || t > w.ts_max) return false;
+  }
+  if (w.cls) {
+    const unsigned c = (unsigned)w.cls[r];
+    if (c > 255u) return false;                                    // -1: no class
+    const unsigned long long m = c < 128u ? (c < 64u ? w.m0 : w.m1) : (c < 192u ? w.m2 : w.m3);
+    if (!((m >> (c & 63u)) & 1ull)) return false;
+  }
+  return true;
+}
+#endif
+
 // ---- distinct ranking: pairwise similarities of stored rows and the greedy thinning of ranked lists (index_distinct.hip) ----
 constexpr int kDistinctMaxDepth = 1024;                  // CC_DISTINCT_MAX_DEPTH: rows of one Gram matrix, entries of one list
 constexpr int kDistinctWords = kDistinctMaxDepth / 64;   // 64-bit words in one row of a list's bit matrix
@@ -256,6 +288,38 @@ void launch_index_gram(const void* emb, long size, int dim, int storage, const l
 // Three launches on `stream`: squeeze, Gram tiles compared with same_at into ws.bits, the walk.
 void launch_index_distinct(const void* emb, long size, int dim, int storage, const int* idx, const float* score, int Q, int depth, float same_at,
                            long long start, long long count, const DistinctWs& ws, int* out_idx, float* out_score, int* out_dups, hipStream_t stream);
+// The compare epilogue alone over ONE list of n <= kDistinctMaxDepth rows the device can read: bits[i][j >> 6] bit j & 63 = (<row i, row j> >= same_at)
+// for the 64 x 64 tiles at and above the diagonal, the float being the one launch_index_gram stores.  One launch.
+void launch_index_gram_bits(const void* emb, long size, int dim, int storage, const long long* rows, int n, unsigned long long* bits, float same_at,
+                            hipStream_t stream);
+
+// ---- day digest: leader clustering of the competing rows in row order (index_digest.hip) ----
+constexpr int kDigestMaxLeaders = 1024;                  // CC_DIGEST_MAX_LEADERS
+constexpr int kDigestChunk = 1024;                       // competing rows per piece: one bit matrix, one walk
+// Device scratch of one digest (the offsets are digest_ws's): the competing rows in order, the per-block counts and offsets of the
+// selection, the two bit matrices of a piece, the leader tables and the counters.
+struct DigestWs {
+  long long* sel;                                        // (n) competing row numbers, ascending; the first *m are valid
+  unsigned* bcnt; unsigned* boff;                        // (blocks of 1024 rows) competing rows in / before each block
+  unsigned long long* bits_lead;                         // (1024, 16) piece rows x leaders
+  unsigned long long* bits_self;                         // (1024, 16) piece rows x piece rows
+  long long* lead_row;                                   // (1024) leaders in order of creation
+  int* lead_cnt; int* lead_ts_min; int* lead_ts_max;     // (1024) members, and the extremes of their ts (INT32_MAX / INT32_MIN: none yet)
+  int* n_lead; int* m;                                   // leaders so far; competing rows
+  long long* totals;                                     // leaders, competing rows, left-over rows
+};
+size_t digest_ws_bytes(long n);
+DigestWs digest_ws(void* base, long n);
+// Competing rows of [0, n) -> ws.sel / ws.m, tables and counters cleared; owner (may be null): -1 for every row that does not compete.
+// Three launches.  RowWhere / allowed as rank_keys_kernel takes them.
+void launch_digest_select(long n, const int* grp, const unsigned char* allowed, int n_allowed, const RowWhere& where, const DigestWs& ws, int* owner,
+                          hipStream_t stream);
+// One piece: rows ws.sel[first .. first + len), len <= kDigestChunk.  Three launches: piece x leaders tiles, piece x piece tiles, the walk.
+void launch_digest_piece(const void* emb, long size, int dim, int storage, long first, int len, float same_at, int max_leaders, const int* ts,
+                         const DigestWs& ws, int* owner, hipStream_t stream);
+// Sort the leaders by `order` (CC_DIGEST_BY_*), write entries start .. start + count - 1 and the padding behind them, and ws.totals.
+void launch_digest_finish(const DigestWs& ws, int order, long long start, long long count, int* out_row, int* out_count, int* out_ts_first,
+                          int* out_ts_last, hipStream_t stream);
 
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;

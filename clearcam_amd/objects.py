@@ -531,6 +531,57 @@ class EmbeddingIndex:
                 t.record_stream(run)
         return oi, os_, od, total
 
+    # -- day digest: every distinct object among the competing rows once, with count and times (cc_index_digest) -----------------------
+    DIGEST_BY = {"count": _lib.DIGEST_BY_COUNT, "first": _lib.DIGEST_BY_FIRST}
+
+    def _digest(self, same_at, start, count, allowed, where, max_leaders, by, out, owner, totals, on_device, stream):
+        if by not in self.DIGEST_BY:
+            raise ValueError('by: "count" or "first"')
+        # a device caller waits for nothing: the filter bytes stay referenced until the next call replaces them
+        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_digest(self._h, float(same_at), int(max_leaders), self.DIGEST_BY[by], _lib.ptr(al) if al is not None else None,
+                                              0 if al is None else int(al.size), C.byref(where) if where is not None else None, int(start), int(count),
+                                              *(_lib.ptr(o) for o in out), _lib.ptr(owner), _lib.ptr(totals), on_device, stream))
+
+    def digest(self, same_at: float = 0.9, start: int = 0, count=None, allowed=None, ts_range=None, classes=None, max_leaders: int = 1024,
+               by: str = "count", owners: bool = False):
+        """What is in the index, every distinct object once -> (rows (count,) int32, counts (count,) int32, ts_first (count,) int32,
+        ts_last (count,) int32, totals (3,) int64[, owner (len(self),) int32]).  No query: the rows that compete are `rank`'s with
+        tracks=False (allowed, ts_range, classes), walked in row order, which is ingest order.  A row joins the first-created leader
+        whose `gram` with it is >= same_at (float32), else it becomes a leader while fewer than max_leaders (<= 1024) exist, else
+        it is left over.  Per leader: its row (the first sighting), its members (itself included) and the min / max ts among them
+        (_lib.ROW_NO_TS: none has one).  by="count": most members first, equal counts by row; "first": in order of appearance.
+        Entries start .. start+count-1 come back (count: max_leaders by default), -1 / 0 / ROW_NO_TS past the last.  totals: leaders,
+        competing rows, left-over rows; the counts of all leaders sum to totals[1] - totals[2].  owners=True: per index row its
+        leader's row, -1 where the row did not compete, -2 where it was left over (cc_index_digest)."""
+        where = self.row_filter(ts_range, classes)
+        count = int(max_leaders) if count is None else int(count)
+        k = count if count >= 1 else 1                                             # the library names the error
+        out = tuple(np.empty(k, np.int32) for _ in range(4))
+        totals = np.zeros(3, np.int64)
+        owner = np.empty(max(len(self), 1), np.int32) if owners else None
+        self._digest(same_at, start, count, allowed, where, max_leaders, by, out, owner, totals, 0, None)
+        return (*out, totals, owner[:len(self)]) if owners else (*out, totals)
+
+    def digest_device(self, same_at: float = 0.9, start: int = 0, count=None, allowed=None, ts_range=None, classes=None, max_leaders: int = 1024,
+                      by: str = "count", owners: bool = False, with_total: bool = True):
+        """`digest` with rows / counts / ts_first / ts_last (and owner) left on the GPU as CUDA torch tensors on the current torch
+        stream.  `totals` comes back as a host array, which costs one wait for the stream; with_total=False returns None in its
+        place and nothing but tensors comes back (inside, the call reads back one number, the count of competing rows)."""
+        import torch
+        where = self.row_filter(ts_range, classes)
+        dev = torch.device("cuda", self.device)
+        count = int(max_leaders) if count is None else int(count)
+        out = tuple(torch.empty(max(count, 1), dtype=torch.int32, device=dev) for _ in range(4))
+        n = len(self)
+        owner = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if owners else None
+        totals = np.zeros(3, np.int64) if with_total else None
+        cur, run = self._run_stream(dev)
+        self._digest(same_at, start, count, allowed, where, max_leaders, by, out, owner, totals, 1, C.c_void_p(run.cuda_stream))
+        if run is not cur:
+            cur.wait_stream(run)
+        return (*out, totals, owner[:n]) if owners else (*out, totals)
+
     def timeline(self, q, t0: int, bin_seconds: int, n_bins: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
                  classes=None) -> Tuple[np.ndarray, np.ndarray]:
         """How the answers of `rank` (same arguments) spread over time -> (counts (Q, n_bins) int64, total (Q,) int64), in one call
@@ -1576,3 +1627,46 @@ class ObjectFinder:
         kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
         c, total = index.timeline(q, t0, bin_seconds, n_bins, allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
         return c[0], int(total[0])
+
+    def digest(self, cam_name=None, timestamp=None, is_face=False, same_at=0.9, start=0, count=100, ts_range=None, classes=None, by="count"):
+        """"What was on this camera today?": every distinct object among the stored crops of the allowed folders once ->
+        ([(path, count, ts_first, ts_last)], {"objects", "crops", "left_over"}).  The reference shows a day's `objects/` folder crop
+        by crop, up to 20 crops per track plus one every 10 s for as long as it lives: a parked car owns a tenth of the day.  Here
+        the crops are walked in stored order on the device (`EmbeddingIndex.digest`): a crop joins the first object whose first
+        crop is at least same_at similar to it, and an entry is that first crop's path, how many crops joined it and the first /
+        last ts among their names (None: no name carries one).  by="count": the most seen first; "first": in order of appearance.
+        Folders and row filter are `search_page`'s; no query, no model.  "objects" is the number of entries there are (at most
+        1024 in one call), "crops" the crops that competed, "left_over" those that matched none of 1024 objects.  A *.jpg name the
+        reference cannot parse raises ValueError where `search` would raise on it: among the crops that compete."""
+        where = row_filter(ts_range, classes)
+        start, count = int(start), int(count)
+        if start < 0 or count < 1:
+            raise ValueError("digest needs start >= 0 and count >= 1")
+        same_at = float(same_at)
+        if same_at != same_at:
+            raise ValueError("same_at is NaN")
+        if by not in EmbeddingIndex.DIGEST_BY:
+            raise ValueError('by: "count" or "first"')
+        empty = ([], {"objects": 0, "crops": 0, "left_over": 0})
+        if not self._has_rows(is_face):
+            print("No embeddings available.")
+            return empty
+        index, table = self._index_and_table(is_face)
+        if not hasattr(index, "digest"):
+            raise RuntimeError("this index cannot summarise its rows")
+        allowed = table.allowed(cam_name, timestamp)
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return empty
+        if any(table.bad[g] for g in live):                 # names the reference raises on: raise the same way, as `search` does
+            passing = table.passing(where)
+            for r in range(len(table.paths)):
+                fn = os.path.basename(table.paths[r])
+                if allowed[table.group[r]] and passing[r] and "_" in fn:
+                    event_img_info(fn.split(".jpg")[0])
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        rows, counts, t0, t1, totals = index.digest(same_at, start, min(count, _lib.DIGEST_MAX_LEADERS), allowed, by=by, **kw)
+        none = _lib.ROW_NO_TS
+        out = [(table.paths[r], int(c), None if a == none else int(a), None if b == none else int(b))
+               for r, c, a, b in zip(rows.tolist(), counts.tolist(), t0.tolist(), t1.tolist()) if r >= 0]
+        return out, {"objects": int(totals[0]), "crops": int(totals[1]), "left_over": int(totals[2])}

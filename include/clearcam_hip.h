@@ -597,6 +597,37 @@ int cc_index_distinct(cc_index* h, const int32_t* idx, const float* score, int Q
                       int64_t start, int64_t count,
                       int32_t* out_idx, float* out_score, int32_t* out_dups, int64_t* total,
                       int on_device, void* stream);
+/* Day digest: "what was on this camera today?" - every distinct object among the competing rows once, with how often and when it was
+ * seen.  No query and no scores: leader clustering in row order, which is ingest order and therefore time order within a folder.
+ *   1. The rows that compete are those of cc_index_rank_where without CC_RANK_TRACKS: allowed / n_groups and where mean the same,
+ *      NULL means no filter.  They are walked in ascending row number.
+ *   2. A row JOINS the first-created leader l for which element [0][1] of cc_index_gram over rows (l, r) is >= same_at (compared in
+ *      f32; the accumulation is cc_index_gram's, so it is that very float).  If none matches and fewer than max_leaders leaders exist
+ *      it BECOMES a leader; if the cap is reached it is LEFT OVER: counted, owning nothing, neither suppressing nor attracting any
+ *      row.  A member never attracts rows either (the greedy rule of cc_index_distinct: in a chain a~b, b~c, a!~c, b joins a and c
+ *      leads).  The answer does not depend on how the implementation cuts the rows into pieces.
+ *   3. Per leader: row (the leader itself, the object's first sighting), count (its members, itself included), ts_first / ts_last
+ *      (the min / max ts over members that have one, CC_ROW_NO_TS if none has).  Leaders are sorted by `order`; entries
+ *      start .. start+count-1 go to the four (count,) outputs, -1 / 0 / CC_ROW_NO_TS / CC_ROW_NO_TS past the last leader.  out_count,
+ *      out_ts_first and out_ts_last may each be NULL.
+ *   4. owner, may be NULL: one int32 per index row - the leader's row number for a member (a leader owns itself), -1 for a row that
+ *      did not compete, -2 for a left-over row.  totals, may be NULL: 3 int64 on the HOST - leaders, competing rows, left-over rows;
+ *      asking for it waits for the stream.  The counts of all leaders sum to totals[1] - totals[2].
+ *   5. on_device: the five outputs are device pointers; otherwise host pointers, and the call waits.  No competing rows: success,
+ *      zero totals, all padding.  same_at = +inf makes every competing row a leader up to the cap, -inf one leader that owns all.
+ *   6. Errors (-22, nothing written, no launch): NaN same_at; max_leaders outside [1, CC_DIGEST_MAX_LEADERS]; an unknown order;
+ *      start < 0; count < 1; a NULL out_row; the n_groups and filter errors of cc_index_rank_where; an index of 2^31 rows or more.
+ *   7. The index is not modified; the handle's scratch grows on demand (8 bytes a row + 290 KB).  On `stream`: the selection (three
+ *      launches and ONE readback, the number of competing rows), then per piece of up to 1024 competing rows three launches (piece x
+ *      leaders tiles, piece x piece tiles, one sequential walk), then a sort of the leaders.  Nothing waits between the pieces. */
+#define CC_DIGEST_MAX_LEADERS 1024
+#define CC_DIGEST_BY_COUNT 0   /* count descending, equal counts: lower leader row first */
+#define CC_DIGEST_BY_FIRST 1   /* leader row ascending: order of first appearance */
+int cc_index_digest(cc_index* h, float same_at, int max_leaders, int order,
+                    const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                    int64_t start, int64_t count,
+                    int32_t* out_row, int32_t* out_count, int32_t* out_ts_first, int32_t* out_ts_last,
+                    int32_t* owner, int64_t* totals, int on_device, void* stream);
 /* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
  * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
  * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
