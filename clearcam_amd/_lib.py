@@ -28,7 +28,7 @@ SYMBOLS = [
     "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores", "cc_index_last_path",
     "cc_index_search", "cc_index_search_groups", "cc_index_add_tracked", "cc_index_search_tracks", "cc_index_rank",
     "cc_index_add_described", "cc_index_row_info", "cc_index_rank_where", "cc_index_timeline", "cc_index_fetch_rows", "cc_index_rank_like",
-    "cc_index_gram", "cc_index_distinct", "cc_index_digest",
+    "cc_index_gram", "cc_index_distinct", "cc_index_digest", "cc_index_sightings",
     "cc_index_remove_rows", "cc_index_remove_groups", "cc_index_destroy",
     "cc_watch_create", "cc_watch_set", "cc_watch_size", "cc_watch_scores", "cc_watch_match", "cc_watch_destroy",
 ]
@@ -69,6 +69,8 @@ LIKE_EXCLUDE_ROWS, LIKE_EXCLUDE_TRACK = 2, 4          # CC_LIKE_EXCLUDE_ROWS / C
 DISTINCT_MAX_DEPTH, DISTINCT_MAX_Q = 1024, 64         # CC_DISTINCT_MAX_DEPTH / CC_DISTINCT_MAX_Q
 DIGEST_MAX_LEADERS = 1024                             # CC_DIGEST_MAX_LEADERS
 DIGEST_BY_COUNT, DIGEST_BY_FIRST = 0, 1               # CC_DIGEST_BY_COUNT / CC_DIGEST_BY_FIRST
+SIGHT_MAX_OBJECTS, SIGHT_MAX_GROUPS = 1024, 4096      # CC_SIGHT_MAX_OBJECTS / CC_SIGHT_MAX_GROUPS
+SIGHT_SKIP_SELF = 1                                   # CC_SIGHT_SKIP_SELF
 
 
 class RowFilter(C.Structure):
@@ -197,6 +199,7 @@ def lib() -> C.CDLL:
         "cc_index_gram": [vp, i64p, C.c_int, vp, C.c_int, vp],
         "cc_index_distinct": [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "cc_index_digest": [vp, C.c_float, C.c_int, C.c_int, vp, C.c_int, C.POINTER(RowFilter), C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "cc_index_sightings": [vp, i64p, C.c_int, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter), vp, vp, vp, vp, C.c_int, vp, C.c_int, vp],
         "cc_index_remove_rows": [vp, vp, C.c_int64, i64p],
         "cc_index_remove_groups": [vp, vp, C.c_int, i64p],
         "cc_index_size": [vp, i64p],

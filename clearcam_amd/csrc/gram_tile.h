@@ -2,7 +2,8 @@
 // (index_digest.hip) share.  Both gather their rows with stage_rows, run gram_tile_accumulate and, where they compare, gram_tile_bits,
 // so an element is the same float wherever it is computed: ONE chain of fused multiply-adds over k on the exact f32 MFMA (16x16x4), in
 // an order that is the same for every element of every tile, and a * b is commutative.  The value of a pair depends on its two stored
-// rows alone - not on the tile, the side of the tile, the kernel or the other rows of the launch.
+// rows alone - not on the tile, the side of the tile, the kernel or the other rows of the launch.  sightings_kernel (index_sightings.hip)
+// stages with stage_rows and feeds each of its accumulators the same MFMAs in the same order over a 128-row tile of its own.
 #pragma once
 #include "kernels.h"
 #include "mfma.h"
@@ -14,12 +15,12 @@ constexpr int kGramBK = 64;                     // floats of K staged per step
 constexpr int kGramLd = kGramBK + 4;            // LDS row stride in floats: 16-byte aligned, the 16 rows of a fragment read on 64 distinct banks
 
 #if defined(__HIPCC__)
-// 64 rows x kGramBK floats of K from k0 on -> dst[64][kGramLd].  A row outside the list or the index, and K past dim, are zeros.
-template <int STORAGE>
+// ROWS rows x kGramBK floats of K from k0 on -> dst[ROWS][kGramLd].  A row outside the list or the index, and K past dim, are zeros.
+template <int STORAGE, int ROWS = kGramTile>
 __device__ __forceinline__ void stage_rows(const char* __restrict__ emb, long size, int dim, const long long* srow, int k0, float* dst, int tid) {
   constexpr int FP = STORAGE == F32 ? 4 : STORAGE == BF16 ? 8 : 16;   // floats in one 16-byte piece of the stored row
   constexpr int PPR = kGramBK / FP;
-  for (int e = tid; e < kGramTile * PPR; e += 256) {
+  for (int e = tid; e < ROWS * PPR; e += 256) {
     const int r = e / PPR, k = k0 + (e % PPR) * FP;
     float4 f[FP / 4];
 #pragma unroll

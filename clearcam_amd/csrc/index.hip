@@ -23,6 +23,9 @@
 // cc_index_rank_like takes its queries from the matrix itself ("more like this stored crop / this whole track"): fetch_rows_kernel
 // gathers and decodes them, like_fold_kernel folds their score vectors into one by the row-wise maximum and marks the excluded rows,
 // which row_passes then keeps out of the ranking like rows the filter rejects ("Query by stored rows").
+//
+// cc_index_gram / cc_index_distinct, cc_index_digest and cc_index_sightings have their entry points here and their kernels in
+// index_distinct.hip, index_digest.hip and index_sightings.hip.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -76,6 +79,9 @@ struct cc_index {
   char* digest_ws = nullptr; size_t digest_ws_cap = 0;         // the competing rows, two bit matrices of a piece, the leader tables (digest_ws)
   char* digest_io = nullptr; size_t digest_io_cap = 0;         // a host caller's window and owner column on the device
   int* digest_pin = nullptr;                                   // pinned: the number of competing rows, the call's one readback
+  // seen before (cc_index_sightings, kernels in index_sightings.hip); the selection lives in digest_ws
+  char* sight_ws = nullptr; size_t sight_ws_cap = 0;           // the objects' row numbers (1024 int64), then their best keys (1024 uint64)
+  char* sight_io = nullptr; size_t sight_io_cap = 0;           // a host caller's four outputs on the device
 };
 
 namespace {
@@ -1855,6 +1861,59 @@ int cc_index_digest(cc_index* h, float same_at, int max_leaders, int order, cons
   CC_API_END
 }
 
+// Seen before: the kernels are index_sightings.hip's (its head tells how they fit together) and the digest's selection; here the checks,
+// the scratch, the zeroing and the copies.  Nothing is read back inside the call.
+int cc_index_sightings(cc_index* h, const int64_t* rows, int n, float same_at, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                       int32_t* out_count, int32_t* out_best_row, float* out_best_score, uint32_t* out_group_counts, int n_group_counts,
+                       int64_t* total, int on_device, void* stream) {
+  CC_API_BEGIN
+  CC_CHECK(h && rows && out_count, "null argument");
+  CC_CHECK(same_at == same_at, "same_at is NaN");
+  CC_CHECK(n >= 1 && n <= CC_SIGHT_MAX_OBJECTS, "n must be in [1, CC_SIGHT_MAX_OBJECTS]");
+  CC_CHECK((flags & ~CC_SIGHT_SKIP_SELF) == 0, "unknown flag bits");
+  CC_CHECK(out_group_counts ? (n_group_counts >= 1 && n_group_counts <= CC_SIGHT_MAX_GROUPS) : n_group_counts == 0,
+           "n_group_counts must be in [1, CC_SIGHT_MAX_GROUPS] with out_group_counts and 0 without");
+  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  CC_CHECK(h->n < (1LL << 31), "sightings need fewer than 2^31 rows");       // out_best_row and the keys hold row numbers in 32 bits
+  check_rows(h, rows, n);
+  const RowWhere w = make_where(h, where);
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const long size = (long)h->n;                                              // > 0: a row passed check_rows
+  ensure((void**)&h->digest_ws, &h->digest_ws_cap, digest_ws_bytes(size));
+  const DigestWs ws = digest_ws(h->digest_ws, size);
+  ensure((void**)&h->sight_ws, &h->sight_ws_cap, (size_t)CC_SIGHT_MAX_OBJECTS * 16);
+  long long* obj = reinterpret_cast<long long*>(h->sight_ws);
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(h->sight_ws) + CC_SIGHT_MAX_OBJECTS;
+  const size_t gcn = (size_t)n * n_group_counts;
+  int* o_cnt = out_count; int* o_row = out_best_row; float* o_sc = out_best_score; unsigned* o_gc = out_group_counts;
+  if (!on_device) {
+    ensure((void**)&h->sight_io, &h->sight_io_cap, ((size_t)3 * n + gcn) * 4);
+    o_cnt = reinterpret_cast<int*>(h->sight_io); o_row = o_cnt + n; o_sc = reinterpret_cast<float*>(o_row + n);
+    o_gc = out_group_counts ? reinterpret_cast<unsigned*>(o_sc + n) : nullptr;
+    if (!out_best_row && !out_best_score) { o_row = nullptr; o_sc = nullptr; }
+  }
+  pin_rows(h, rows, n);
+  CC_HIP(hipMemcpyAsync(obj, h->rows_pin, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  CC_HIP(hipEventRecord(h->rows_ev, s));
+  const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
+  launch_digest_select(size, h->grp, allowed_dev, h->allowed_cap, w, ws, nullptr, s);
+  CC_HIP(hipMemsetAsync(o_cnt, 0, (size_t)n * 4, s));
+  CC_HIP(hipMemsetAsync(best, 0, (size_t)n * 8, s));
+  if (o_gc) CC_HIP(hipMemsetAsync(o_gc, 0, gcn * 4, s));
+  launch_sightings(h->emb, size, h->dim, h->storage, ws.sel, ws.m, obj, n, same_at, flags & CC_SIGHT_SKIP_SELF, h->grp, n_group_counts, o_cnt, best, o_gc,
+                   o_row, o_sc, s);
+  if (!on_device) {
+    CC_HIP(hipMemcpyAsync(out_count, o_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (out_best_row) CC_HIP(hipMemcpyAsync(out_best_row, o_row, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (out_best_score) CC_HIP(hipMemcpyAsync(out_best_score, o_sc, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (o_gc) CC_HIP(hipMemcpyAsync(out_group_counts, o_gc, gcn * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (total) CC_HIP(hipMemcpyAsync(total, ws.totals + 1, 8, hipMemcpyDeviceToHost, s));
+  if (total || !on_device) CC_HIP(hipStreamSynchronize(s));
+  CC_API_END
+}
+
 int cc_index_remove_rows(cc_index* h, const uint8_t* drop, int64_t n, int64_t* removed) { return remove_impl(h, true, drop, n, 0, removed); }
 
 int cc_index_remove_groups(cc_index* h, const uint8_t* drop, int n_groups, int64_t* removed) { return remove_impl(h, false, drop, 0, n_groups, removed); }
@@ -1864,7 +1923,7 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io, (void*)h->sight_ws, (void*)h->sight_io}) if (p) hipFree(p);
   if (h->digest_pin) hipHostFree(h->digest_pin);
   if (h->pin) hipHostFree(h->pin);
   if (h->rows_ev) { hipEventSynchronize(h->rows_ev); hipEventDestroy(h->rows_ev); }

@@ -321,6 +321,16 @@ void launch_digest_piece(const void* emb, long size, int dim, int storage, long 
 void launch_digest_finish(const DigestWs& ws, int order, long long start, long long count, int* out_row, int* out_count, int* out_ts_first,
                           int* out_ts_last, hipStream_t stream);
 
+// ---- seen before: up to 1024 stored rows against all competing rows, reduced per object (index_sightings.hip) ----
+constexpr int kSightMaxObjects = 1024;                   // CC_SIGHT_MAX_OBJECTS
+constexpr int kSightMaxGroups = 4096;                    // CC_SIGHT_MAX_GROUPS
+// sel / m: the competing rows and their number on the device (launch_digest_select); obj: n_obj row numbers on the device, each inside
+// [0, size).  out_count (n_obj) and gc (n_obj, n_gc; null with n_gc 0) are ADDED to and `best` (n_obj keys) is RAISED: the caller zeroes
+// all three first.  out_best_row / out_best_score (n_obj, either may be null) are written from `best`.  Two launches (one with both null).
+void launch_sightings(const void* emb, long size, int dim, int storage, const long long* sel, const int* m, const long long* obj, int n_obj, float same_at,
+                      int skip_self, const int* grp, int n_gc, int* out_count, unsigned long long* best, unsigned* gc, int* out_best_row,
+                      float* out_best_score, hipStream_t stream);
+
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;
   float iou_thr;

@@ -582,6 +582,54 @@ class EmbeddingIndex:
             cur.wait_stream(run)
         return (*out, totals, owner[:n]) if owners else (*out, totals)
 
+    # -- seen before: up to 1024 stored rows against all competing rows, reduced per object (cc_index_sightings) --------------------------
+    def _sightings(self, rows, same_at, allowed, where, skip_self, out, n_group_counts, total, on_device, stream):
+        ids = self._row_numbers(rows)
+        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_sightings(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), float(same_at),
+                                                 _lib.SIGHT_SKIP_SELF if skip_self else 0, _lib.ptr(al) if al is not None else None,
+                                                 0 if al is None else int(al.size), C.byref(where) if where is not None else None,
+                                                 *(_lib.ptr(o) for o in out), int(n_group_counts), _lib.ptr(total), on_device, stream))
+
+    @staticmethod
+    def _sightings_shape(rows, group_counts):
+        n, g = int(np.asarray(rows).size), int(group_counts)
+        return (n if 1 <= n <= _lib.SIGHT_MAX_OBJECTS else 1), (g if 0 <= g <= _lib.SIGHT_MAX_GROUPS else 1)   # outside: the library names the error
+
+    def sightings(self, rows, same_at: float = 0.9, allowed=None, ts_range=None, classes=None, skip_self: bool = False, group_counts: int = 0,
+                  with_total: bool = True):
+        """Stored rows (the objects, 1 .. 1024 of them, repeats allowed) against ALL competing rows -> (count (n,) int32, best_row (n,)
+        int32, best_score (n,) f32, group_counts (n, group_counts) uint32 or None, total).  The rows that compete are `rank`'s with
+        tracks=False (allowed, ts_range, classes); an object need not compete itself.  The value of a pair is `gram` of the two rows
+        (that very float).  count: the pairs >= same_at (float32); best: the pair with the largest value, equal values by the lower
+        row, -1 / -inf without a pair, whatever same_at; group_counts[i][g]: the matches of object i in group g (matches in groups
+        >= group_counts are in count only).  skip_self: the pair of an object with its own row number does not exist.  total: the
+        number of competing rows (cc_index_sightings)."""
+        where = self.row_filter(ts_range, classes)
+        n, g = self._sightings_shape(rows, group_counts)
+        out = (np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, g), np.uint32) if group_counts else None)
+        total = np.zeros(1, np.int64) if with_total else None
+        self._sightings(rows, same_at, allowed, where, skip_self, out, group_counts, total, 0, None)
+        return (*out, None if total is None else int(total[0]))
+
+    def sightings_device(self, rows, same_at: float = 0.9, allowed=None, ts_range=None, classes=None, skip_self: bool = False,
+                         group_counts: int = 0, with_total: bool = True):
+        """`sightings` with the four outputs left on the GPU as CUDA torch tensors on the current torch stream (rows stay a host
+        list).  with_total=False returns None for the total and waits for nothing: inside, nothing is read back."""
+        import torch
+        where = self.row_filter(ts_range, classes)
+        dev = torch.device("cuda", self.device)
+        n, g = self._sightings_shape(rows, group_counts)
+        out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.float32, device=dev),
+               torch.empty((n, g), dtype=torch.int32, device=dev) if group_counts else None)      # uint32 counts in an int32 tensor
+        total = np.zeros(1, np.int64) if with_total else None
+        cur, run = self._run_stream(dev)
+        self._sightings(rows, same_at, allowed, where, skip_self, out, group_counts, total, 1, C.c_void_p(run.cuda_stream))
+        if run is not cur:
+            cur.wait_stream(run)
+        return (*out, None if total is None else int(total[0]))
+
     def timeline(self, q, t0: int, bin_seconds: int, n_bins: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
                  classes=None) -> Tuple[np.ndarray, np.ndarray]:
         """How the answers of `rank` (same arguments) spread over time -> (counts (Q, n_bins) int64, total (Q,) int64), in one call
@@ -1670,3 +1718,85 @@ class ObjectFinder:
         out = [(table.paths[r], int(c), None if a == none else int(a), None if b == none else int(b))
                for r, c, a, b in zip(rows.tolist(), counts.tolist(), t0.tolist(), t1.tolist()) if r >= 0]
         return out, {"objects": int(totals[0]), "crops": int(totals[1]), "left_over": int(totals[2])}
+
+    SEEN_BY = ("new", "count", "first")
+
+    @staticmethod
+    def _dir_cam_day(d: str):
+        """(camera, day) of a directory group '.../cameras/<cam>/objects/<day>/'; None where the part is missing."""
+        def part(key):
+            i = d.find(key)
+            if i < 0:
+                return None
+            j = d.find("/", i + len(key))
+            return d[i + len(key):j] if j >= 0 else None
+        return part("/cameras/"), part("/objects/")
+
+    def seen_before(self, cam_name=None, timestamp=None, is_face=False, same_at=0.9, start=0, count=100, ts_range=None, classes=None,
+                    history_cam=None, by="new"):
+        """"Which of today's objects have we seen before, and which are new?" -> ([(path, count_today, ts_first, ts_last, seen_before,
+        days, cams, last_day, best_path, best_score)], {"objects", "new", "crops", "left_over", "history_crops"}).  The objects are
+        `digest`'s of (cam_name, timestamp) in order of first appearance, up to 1024 (same folders, row filter, validation and
+        behaviour on unparsable names).  The history is every folder `history_cam` allows (None: all cameras) that the digest did not
+        take, filtered by `classes` (ts_range is seconds into today and does not apply).  One `EmbeddingIndex.sightings` call scores
+        all objects against the whole history on the device: seen_before = the history crops at least same_at similar to the
+        object's first crop, days = the distinct <day> folders among them, cams = their cameras (sorted), last_day = the largest such
+        day string or None, best_path / best_score = the closest history crop whether it matches or not (None / None without
+        history).  by="new": objects never seen before first, then most crops today, then order of appearance; "count" / "first":
+        `digest`'s orders.  Entries start .. start+count-1 come back.  "new" counts the objects with seen_before == 0,
+        "history_crops" the history crops that competed."""
+        where = row_filter(ts_range, classes)
+        start, count = int(start), int(count)
+        if start < 0 or count < 1:
+            raise ValueError("seen_before needs start >= 0 and count >= 1")
+        same_at = float(same_at)
+        if same_at != same_at:
+            raise ValueError("same_at is NaN")
+        if by not in self.SEEN_BY:
+            raise ValueError('by: "new", "count" or "first"')
+        empty = ([], {"objects": 0, "new": 0, "crops": 0, "left_over": 0, "history_crops": 0})
+        if not self._has_rows(is_face):
+            print("No embeddings available.")
+            return empty
+        index, table = self._index_and_table(is_face)
+        if not hasattr(index, "digest") or not hasattr(index, "sightings"):
+            raise RuntimeError("this index cannot summarise its rows")
+        allowed = table.allowed(cam_name, timestamp)
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return empty
+        if any(table.bad[g] for g in live):                 # names the reference raises on: raise the same way, as `digest` does
+            passing = table.passing(where)
+            for r in range(len(table.paths)):
+                fn = os.path.basename(table.paths[r])
+                if allowed[table.group[r]] and passing[r] and "_" in fn:
+                    event_img_info(fn.split(".jpg")[0])
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        rows, counts, t0, t1, totals = index.digest(same_at, 0, _lib.DIGEST_MAX_LEADERS, allowed, by="first", **kw)
+        lead = [r for r in rows.tolist() if r >= 0]
+        n, none = len(lead), _lib.ROW_NO_TS
+        history = (np.asarray(table.allowed(history_cam, None)) != 0) & (np.asarray(allowed) == 0)
+        seen = np.zeros(n, np.int64)
+        best_row, best_score = np.full(n, -1, np.int64), np.full(n, -np.inf, np.float32)
+        groups = np.zeros((n, len(table.dirs)), np.int64)
+        history_crops = 0
+        if n and history.any():
+            seen, best_row, best_score, groups, history_crops = index.sightings(lead, same_at, history.astype(np.uint8), classes=classes,
+                                                                                group_counts=len(table.dirs))
+        where_of = [self._dir_cam_day(d) for d in table.dirs]
+        entries = []
+        for i, r in enumerate(lead):
+            hit = [where_of[g] for g in np.flatnonzero(np.asarray(groups[i])).tolist()]
+            days = {d for _, d in hit if d is not None}
+            b = int(best_row[i])
+            entries.append((table.paths[r], int(counts[i]), None if t0[i] == none else int(t0[i]), None if t1[i] == none else int(t1[i]),
+                            int(seen[i]), len(days), sorted({c for c, _ in hit if c is not None}), max(days) if days else None,
+                            table.paths[b] if b >= 0 else None, float(best_score[i]) if b >= 0 else None))
+        order = list(range(n))                                                # by="first": the digest's own order
+        if by == "count":
+            order.sort(key=lambda i: (-entries[i][1], lead[i]))
+        elif by == "new":
+            order.sort(key=lambda i: (entries[i][4] != 0, -entries[i][1], lead[i]))
+        info = {"objects": int(totals[0]), "new": sum(1 for e in entries if e[4] == 0), "crops": int(totals[1]), "left_over": int(totals[2]),
+                "history_crops": int(history_crops)}
+        return [entries[i] for i in order[start:start + count]], info

@@ -628,6 +628,45 @@ int cc_index_digest(cc_index* h, float same_at, int max_leaders, int order,
                     int64_t start, int64_t count,
                     int32_t* out_row, int32_t* out_count, int32_t* out_ts_first, int32_t* out_ts_last,
                     int32_t* owner, int64_t* totals, int on_device, void* stream);
+/* Seen before? - "which of today's objects have we seen before, where, and which are new?": up to CC_SIGHT_MAX_OBJECTS stored rows (the
+ * objects, typically the leaders of a cc_index_digest) against ALL competing rows, reduced per object.  Many to many, no ranking.
+ *   1. rows: n row numbers on the HOST, 1 <= n <= CC_SIGHT_MAX_OBJECTS, in any order, repeats allowed (each position is its own
+ *      object).  They are checked on the host before any launch, as cc_index_gram checks its rows.
+ *   2. The rows that compete are those of cc_index_rank_where without CC_RANK_TRACKS: allowed / n_groups and where mean the same,
+ *      NULL means no filter.  An object need not compete itself.
+ *   3. The pair value of object i and competing row r is g = element [0][1] of cc_index_gram over rows (rows[i], r): that very float
+ *      (one chain of f32 fused multiply-adds over k on the exact f32 MFMA, in cc_index_gram's accumulation order), independent of
+ *      tile, side, kernel and the rest of the launch.  With CC_SIGHT_SKIP_SELF the pair with r == rows[i] does not exist for object
+ *      i; a byte-equal copy at another row number still counts.
+ *   4. Per object, (n,) each: out_count[i] = the number of pairs with g >= same_at (compared in f32).  out_best_row[i] /
+ *      out_best_score[i] = the pair with the largest g in the total order of the ranking keys (+0 beats -0; NaN unsupported), among
+ *      equal g the lowest row number; it does not depend on same_at; -1 / -inf with no pair.  out_best_row and out_best_score may
+ *      each be NULL, out_count may not.
+ *   5. out_group_counts (n, n_group_counts) uint32, may be NULL (then n_group_counts must be 0, else 1 <= n_group_counts <=
+ *      CC_SIGHT_MAX_GROUPS): entry [i][g] = the matching pairs (g >= same_at) of object i whose row has group g.  A match in a group
+ *      >= n_group_counts is counted in out_count only.
+ *   6. total: one int64 on the HOST, may be NULL: the number of competing rows; asking for it waits for the stream.  on_device: the
+ *      four outputs are device pointers (rows stays on the host) and the call does not wait unless total is asked for; otherwise
+ *      they are host pointers and the call waits.  There is no readback inside the call: the number of competing rows stays on the
+ *      device, where the kernels read it.
+ *   7. Every reduction is an integer sum or a maximum of totally ordered keys: the answer does not depend on the arrival of the
+ *      blocks or on how the rows are cut into strips, and two calls give equal bytes.
+ *   8. No competing rows: success, zero counts, -1 / -inf.  same_at = -inf counts every pair, +inf none; best is unaffected.
+ *   9. Errors (-22, nothing written, no launch): NaN same_at; n outside [1, CC_SIGHT_MAX_OBJECTS]; a row outside [0, size); unknown
+ *      flag bits; a NULL rows or out_count; out_group_counts / n_group_counts inconsistent or out of range; the n_groups and filter
+ *      errors of cc_index_rank_where; an index of 2^31 rows or more.
+ *  10. The index is not modified; the handle's scratch grows on demand: the digest's (8 bytes a row + 290 KB, shared with
+ *      cc_index_digest) + 16 KB, and for a host caller n * (12 + 4 * n_group_counts) bytes.  On `stream`: the selection (the digest's
+ *      three launches), the zeroing of the outputs, ONE scoring launch (a persistent grid of 128-row strips x object tiles that keeps
+ *      its per-object tables in LDS and folds them into the outputs once per block) and one launch that decodes the best keys. */
+#define CC_SIGHT_MAX_OBJECTS 1024
+#define CC_SIGHT_MAX_GROUPS  4096
+#define CC_SIGHT_SKIP_SELF   1
+int cc_index_sightings(cc_index* h, const int64_t* rows, int n, float same_at, int flags,
+                       const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                       int32_t* out_count, int32_t* out_best_row, float* out_best_score,
+                       uint32_t* out_group_counts, int n_group_counts,
+                       int64_t* total, int on_device, void* stream);
 /* Remove rows; survivors keep their order and are renumbered densely (new id = survivors before the row).
  * drop: n bytes on the HOST, non-zero removes the row; n must equal the current size (else an error, index untouched).
  * *removed (may be NULL) receives the count.  Capacity and track slots are unchanged.  Synchronous like cc_index_add*. */
