@@ -28,6 +28,7 @@ SYMBOLS = [
     "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores", "cc_index_last_path",
     "cc_index_search", "cc_index_search_groups", "cc_index_add_tracked", "cc_index_search_tracks", "cc_index_rank",
     "cc_index_add_described", "cc_index_row_info", "cc_index_rank_where", "cc_index_timeline", "cc_index_fetch_rows", "cc_index_rank_like",
+    "cc_index_rank_terms", "cc_index_timeline_terms",
     "cc_index_gram", "cc_index_distinct", "cc_index_digest", "cc_index_sightings",
     "cc_index_remove_rows", "cc_index_remove_groups", "cc_index_destroy",
     "cc_watch_create", "cc_watch_set", "cc_watch_size", "cc_watch_scores", "cc_watch_match", "cc_watch_destroy",
@@ -66,7 +67,10 @@ ROW_NO_TS = -(1 << 31)                                # CC_ROW_NO_TS: a row with
 RANK_TRACKS = 1                                       # CC_RANK_TRACKS
 LIKE_MAX_ROWS = 64                                    # CC_LIKE_MAX_ROWS: the most query rows of one cc_index_rank_like
 LIKE_EXCLUDE_ROWS, LIKE_EXCLUDE_TRACK = 2, 4          # CC_LIKE_EXCLUDE_ROWS / CC_LIKE_EXCLUDE_TRACK
-DISTINCT_MAX_DEPTH, DISTINCT_MAX_Q = 1024, 64         # CC_DISTINCT_MAX_DEPTH / CC_DISTINCT_MAX_Q
+TERMS_MAX = 64                                        # CC_TERMS_MAX: the most terms of one cc_index_rank_terms
+TERM_RANK, TERM_REQUIRE, TERM_REJECT = 0, 1, 2        # CC_TERM_RANK / CC_TERM_REQUIRE / CC_TERM_REJECT
+COMBINE_MAX, COMBINE_MIN, COMBINE_SUM = 0, 1, 2       # CC_COMBINE_MAX / CC_COMBINE_MIN / CC_COMBINE_SUM
+DISTINCT_MAX_DEPTH, DISTINCT_MAX_Q = 1024, 64        # CC_DISTINCT_MAX_DEPTH / CC_DISTINCT_MAX_Q
 DIGEST_MAX_LEADERS = 1024                             # CC_DIGEST_MAX_LEADERS
 DIGEST_BY_COUNT, DIGEST_BY_FIRST = 0, 1               # CC_DIGEST_BY_COUNT / CC_DIGEST_BY_FIRST
 SIGHT_MAX_OBJECTS, SIGHT_MAX_GROUPS = 1024, 4096      # CC_SIGHT_MAX_OBJECTS / CC_SIGHT_MAX_GROUPS
@@ -76,6 +80,11 @@ SIGHT_SKIP_SELF = 1                                   # CC_SIGHT_SKIP_SELF
 class RowFilter(C.Structure):
     """cc_row_filter: the row filter of cc_index_rank_where / cc_index_timeline (include/clearcam_hip.h)."""
     _fields_ = [("use_ts", C.c_int32), ("ts_min", C.c_int32), ("ts_max", C.c_int32), ("use_cls", C.c_int32), ("cls_mask", C.c_uint64 * 4)]
+
+
+class Term(C.Structure):
+    """cc_term: what one term of cc_index_rank_terms / cc_index_timeline_terms is (include/clearcam_hip.h)."""
+    _fields_ = [("role", C.c_int32), ("weight", C.c_float), ("cut", C.c_float)]
 
 
 class CCError(RuntimeError):
@@ -196,6 +205,10 @@ def lib() -> C.CDLL:
         "cc_index_timeline": [vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter), C.c_int32, C.c_int32, C.c_int, vp, vp, C.c_int, vp],
         "cc_index_fetch_rows": [vp, i64p, C.c_int, vp, C.c_int, vp],
         "cc_index_rank_like": [vp, i64p, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter), vp, vp, vp, C.c_int, vp],
+        "cc_index_rank_terms": [vp, vp, C.c_int, i64p, C.c_int, C.POINTER(Term), C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_int, vp, C.c_int,
+                                C.POINTER(RowFilter), vp, vp, vp, vp, C.c_int, vp],
+        "cc_index_timeline_terms": [vp, vp, C.c_int, i64p, C.c_int, C.POINTER(Term), C.c_int, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter),
+                                    C.c_int32, C.c_int32, C.c_int, vp, vp, C.c_int, vp],
         "cc_index_gram": [vp, i64p, C.c_int, vp, C.c_int, vp],
         "cc_index_distinct": [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "cc_index_digest": [vp, C.c_float, C.c_int, C.c_int, vp, C.c_int, C.POINTER(RowFilter), C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],

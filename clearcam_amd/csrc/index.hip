@@ -24,6 +24,10 @@
 // gathers and decodes them, like_fold_kernel folds their score vectors into one by the row-wise maximum and marks the excluded rows,
 // which row_passes then keeps out of the ranking like rows the filter rejects ("Query by stored rows").
 //
+// cc_index_rank_terms / cc_index_timeline_terms rank a compound question: up to 64 terms (vectors the caller brings and stored rows) are
+// scored in one batch, terms_fold_kernel folds them by role (RANK through max / min / a weighted sum, REQUIRE and REJECT into the dead
+// bytes) into one vector, and the same ranking of ONE query follows ("Compound search").
+//
 // cc_index_gram / cc_index_distinct, cc_index_digest and cc_index_sightings have their entry points here and their kernels in
 // index_distinct.hip, index_digest.hip and index_sightings.hip.
 #include <algorithm>
@@ -68,10 +72,13 @@ struct cc_index {
   char* bounce = nullptr; size_t bounce_cap = 0;               // one slab of survivors: rows, then their groups, then their slots
   char* rank_ws = nullptr; size_t rank_ws_cap = 0;             // cc_index_rank: per query and select the state, a 256-bin table and a window counter; per query the total
   // query by stored rows (cc_index_fetch_rows / cc_index_rank_like)
-  unsigned char* dead = nullptr; size_t dead_cap = 0;          // (n) one byte per row of the current cc_index_rank_like: non-zero = excluded, does not compete
+  unsigned char* dead = nullptr; size_t dead_cap = 0;          // (n) one byte per row of the current cc_index_rank_like / cc_index_rank_terms: non-zero = dead, does not compete
   long long* rows_pin = nullptr; size_t rows_pin_cap = 0;      // pinned, device-visible: the row numbers of a gather of more than CC_LIKE_MAX_ROWS rows, read by fetch_rows_kernel
   hipEvent_t rows_ev = nullptr;                                // recorded behind that gather: rows_pin is rewritten only after it
   std::vector<int32_t> grp_host, trk_host;                     // the grp / trk columns on the host (n each): CC_LIKE_EXCLUDE_TRACK is checked without a device round trip
+  // compound search (cc_index_rank_terms): touched by no other call
+  unsigned char* which_row = nullptr; size_t which_row_cap = 0;   // (n) one byte per row: the RANK term that made the row's value, written by terms_fold_kernel
+  int* which_dev = nullptr; size_t which_dev_cap = 0;             // (count) a host caller's `which` on the device, when the result is too large for the pinned block
   // distinct ranking (cc_index_gram / cc_index_distinct, kernels in index_distinct.hip)
   char* dist_ws = nullptr; size_t dist_ws_cap = 0;             // per list: squeezed rows, their places, the bit matrix, the counts (distinct_ws)
   char* dist_io = nullptr; size_t dist_io_cap = 0;             // a host caller's lists and answers, or its Gram matrix, on the device
@@ -841,6 +848,138 @@ __global__ __launch_bounds__(256) void like_fold_kernel(float* __restrict__ S, i
   }
 }
 
+// ---- compound search (cc_index_rank_terms / cc_index_timeline_terms) -----------------------------------------------------------------
+// like_fold_kernel with roles: S (T, n) -> S[0][r] = the ranking value of row r from the RANK terms, dead[r] from the REQUIRE / REJECT
+// terms and the exclude flags, which[r] = the RANK term that made the value.  What each term is travels by value in the arguments.
+struct TermParam { float weight, cut; int role, pad; };                      // 16 bytes: one scalar load per term
+struct TermSpec { int T, combine, pad0, pad1; TermParam t[CC_TERMS_MAX]; };
+
+// One row's state while the terms go by: v the sum so far (SUM), k the best key so far - ordered(product) under SUM, ordered(score)
+// under MAX, its complement under MIN, so that every rule keeps the LARGEST key and 0 stands for "none yet" -, wh the term that
+// brought k (-1: no RANK term yet), dead (0 / 1).
+struct TermAcc { float v; unsigned k; int wh; unsigned dead; };
+
+// Term t (what it is: m) scores the R rows of a thread x[0..R).  The role is tested once for all of them.  The product and the sum of
+// SUM are two roundings: contraction is off in this function, so the compiler emits a multiply and an add, never an fma, and float32
+// arithmetic on the host reproduces v bit for bit.  flip: ~0 under MIN, else 0.
+template <int R>
+__device__ __forceinline__ void term_step(TermAcc (&a)[R], const TermParam m, bool sum, unsigned flip, const float (&x)[R], int t) {
+#pragma clang fp contract(off)
+  if (m.role == CC_TERM_RANK) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      unsigned k;
+      if (sum) {
+        const float p = m.weight * x[j];
+        a[j].v = a[j].v + p;
+        k = ordered(p);
+      } else {
+        k = ordered(x[j]) ^ flip;
+      }
+      const bool take = k > a[j].k || a[j].wh < 0;                           // strictly larger: equal keys stay with the lower term
+      a[j].k = take ? k : a[j].k; a[j].wh = take ? t : a[j].wh;
+    }
+  } else if (m.role == CC_TERM_REQUIRE) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) a[j].dead |= x[j] >= m.cut ? 0u : 1u;
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) a[j].dead |= x[j] >= m.cut ? 1u : 0u;
+  }
+}
+
+__device__ __forceinline__ float term_value(const TermAcc& a, bool sum, unsigned flip) { return sum ? a.v : unordered(a.k ^ flip); }
+
+// The shape of like_fold_kernel: a thread reads S[.][r] of its own rows and writes S[0][r], dead[r] (dead != null) and which[r]
+// (which != null) of those rows only: no atomics, no LDS, no second score buffer, in place over row 0.  VEC (n % 4 == 0): four
+// consecutive rows per thread, one 16-byte load per term, dead / which written as one 32-bit word each.  Otherwise one row per thread.
+// What a term is is the same for every thread (one 16-byte scalar load from the arguments, uniform branches).  mode 1: the rows of
+// `excl` are dead too (the stored rows that are RANK terms); mode 2: every row of group G and slot Tk is.
+template <bool VEC>
+__global__ __launch_bounds__(256) void terms_fold_kernel(float* __restrict__ S, long n, const int* __restrict__ grp, const int* __restrict__ trk, const TermSpec spec,
+                                                         const LikeRows excl, int mode, int G, int Tk, unsigned char* __restrict__ dead,
+                                                         unsigned char* __restrict__ which) {
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nt = (long)gridDim.x * 256;
+  const int T = spec.T;
+  const bool sum = spec.combine == CC_COMBINE_SUM;
+  const unsigned flip = spec.combine == CC_COMBINE_MIN ? ~0u : 0u;
+  if (VEC) {
+    const long n4 = n >> 2;
+    float4* S4 = reinterpret_cast<float4*>(S);
+    for (long i = tid; i < n4; i += nt) {
+      TermAcc a[4] = {{0.f, 0u, -1, 0u}, {0.f, 0u, -1, 0u}, {0.f, 0u, -1, 0u}, {0.f, 0u, -1, 0u}};
+      int t = 0;
+      for (; t + 4 <= T; t += 4) {                                           // four independent loads in flight, then the four terms in order
+        float4 x4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x4[u] = S4[(long)(t + u) * n4 + i];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float x[4] = {x4[u].x, x4[u].y, x4[u].z, x4[u].w};
+          term_step<4>(a, spec.t[t + u], sum, flip, x, t + u);
+        }
+      }
+      for (; t < T; ++t) {
+        const float4 x4 = S4[(long)t * n4 + i];
+        const float x[4] = {x4.x, x4.y, x4.z, x4.w};
+        term_step<4>(a, spec.t[t], sum, flip, x, t);
+      }
+      S4[i] = make_float4(term_value(a[0], sum, flip), term_value(a[1], sum, flip), term_value(a[2], sum, flip), term_value(a[3], sum, flip));
+      if (dead) {
+        unsigned d = a[0].dead | a[1].dead << 8 | a[2].dead << 16 | a[3].dead << 24;
+        if (mode == 2) {
+          const int4 g = reinterpret_cast<const int4*>(grp)[i], k = reinterpret_cast<const int4*>(trk)[i];
+          d |= (g.x == G && k.x == Tk ? 1u : 0u) | (g.y == G && k.y == Tk ? 1u << 8 : 0u) | (g.z == G && k.z == Tk ? 1u << 16 : 0u) | (g.w == G && k.w == Tk ? 1u << 24 : 0u);
+        } else if (mode == 1) {
+          for (int j = 0; j < excl.n; ++j) {
+            const long k = (long)excl.r[j] - 4 * i;
+            if (k >= 0 && k < 4) d |= 1u << (8 * (int)k);
+          }
+        }
+        reinterpret_cast<unsigned*>(dead)[i] = d;
+      }
+      if (which) reinterpret_cast<unsigned*>(which)[i] = ((unsigned)a[0].wh & 255u) | ((unsigned)a[1].wh & 255u) << 8 | ((unsigned)a[2].wh & 255u) << 16 | ((unsigned)a[3].wh & 255u) << 24;
+    }
+  } else {
+    for (long r = tid; r < n; r += nt) {
+      TermAcc a[1] = {{0.f, 0u, -1, 0u}};
+      int t = 0;
+      for (; t + 4 <= T; t += 4) {
+        float x4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x4[u] = S[(long)(t + u) * n + r];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float x[1] = {x4[u]};
+          term_step<1>(a, spec.t[t + u], sum, flip, x, t + u);
+        }
+      }
+      for (; t < T; ++t) {
+        const float x[1] = {S[(long)t * n + r]};
+        term_step<1>(a, spec.t[t], sum, flip, x, t);
+      }
+      S[r] = term_value(a[0], sum, flip);
+      if (dead) {
+        bool d = a[0].dead != 0u;
+        if (mode == 2) d = d || (grp[r] == G && trk[r] == Tk);
+        else if (mode == 1) for (int j = 0; j < excl.n; ++j) d = d || (long)excl.r[j] == r;
+        dead[r] = d ? 1 : 0;
+      }
+      if (which) which[r] = (unsigned char)a[0].wh;
+    }
+  }
+}
+
+// Behind the emit step: which[o] = the term byte of the row idx[o] names, -1 where idx[o] is -1 (padding).  idx may be pinned host
+// memory (the zero-copy route); the test keeps the load inside the column whatever it holds.
+__global__ __launch_bounds__(256) void which_gather_kernel(const int* __restrict__ idx, const unsigned char* __restrict__ which_row, long n, size_t cnt,
+                                                           int* __restrict__ which) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (size_t)gridDim.x * 256) {
+    const int r = idx[i];
+    which[i] = (r >= 0 && (long)r < n) ? (int)which_row[r] : -1;
+  }
+}
+
 // ---- removal: stable compaction in place -------------------------------------------------------------------------------------
 // Row r moves to pos(r) = the survivors before it, and pos(r) <= r.  Positions come from three passes: keep flags and survivor
 // counts per granule of kGran rows, an exclusive scan of the counts by ONE block (64-bit), and the place inside the granule from a
@@ -1564,13 +1703,97 @@ void like_scores(cc_index* h, const LikeQuery& like, RowWhere& w, hipStream_t s)
   CC_HIP(hipGetLastError());
 }
 
+// The query side of cc_index_rank_terms / cc_index_timeline_terms, checked: the vectors, the rows, what each term is (spec), which
+// rows the exclude bits kill (mode 0 nothing, 1 the rows of excl, 2 group G + slot Tk), whether any term or flag can kill a row, and
+// where the caller wants `which` (null: not asked for).
+struct TermsQuery { const float* q; int n_vec; const int64_t* rows; int n_rows; TermSpec spec; LikeRows excl; int mode, G, Tk; bool kills; int32_t* which; };
+
+int terms_check(cc_index* h, const float* q, int n_vec, const int64_t* rows, int n_rows, const cc_term* terms, int combine, int flags, int32_t* which,
+                TermsQuery* tq) {
+  CC_API_BEGIN
+  CC_CHECK(h && terms, "null argument");
+  CC_CHECK(n_vec >= 0 && n_rows >= 0 && n_vec <= CC_TERMS_MAX && n_rows <= CC_TERMS_MAX && n_vec + n_rows >= 1 && n_vec + n_rows <= CC_TERMS_MAX,
+           "n_vec and n_rows must not be negative and n_vec + n_rows must be in [1, CC_TERMS_MAX]");
+  CC_CHECK((q || !n_vec) && (rows || !n_rows), "null argument");
+  CC_CHECK(combine == CC_COMBINE_MAX || combine == CC_COMBINE_MIN || combine == CC_COMBINE_SUM, "unknown combine rule");
+  CC_CHECK((flags & ~(CC_RANK_TRACKS | CC_LIKE_EXCLUDE_ROWS | CC_LIKE_EXCLUDE_TRACK)) == 0, "unknown flag bits");
+  check_rows(h, rows, n_rows);
+  const int T = n_vec + n_rows;
+  *tq = TermsQuery{};
+  tq->q = q; tq->n_vec = n_vec; tq->rows = rows; tq->n_rows = n_rows; tq->which = which;
+  tq->spec.T = T; tq->spec.combine = combine;
+  tq->mode = (flags & CC_LIKE_EXCLUDE_TRACK) ? 2 : (flags & CC_LIKE_EXCLUDE_ROWS) ? 1 : 0;
+  tq->G = 0; tq->Tk = -1;
+  for (int i = 0; i < CC_LIKE_MAX_ROWS; ++i) tq->excl.r[i] = -1;
+  int n_rank = 0;
+  for (int t = 0; t < T; ++t) {
+    const cc_term& m = terms[t];
+    CC_CHECK(m.role == CC_TERM_RANK || m.role == CC_TERM_REQUIRE || m.role == CC_TERM_REJECT, "unknown term role");
+    tq->spec.t[t] = TermParam{m.weight, m.cut, m.role, 0};
+    if (m.role == CC_TERM_RANK) {
+      ++n_rank;
+      CC_CHECK(combine != CC_COMBINE_SUM || (m.weight - m.weight == 0.f), "the weight of a RANK term must be finite under CC_COMBINE_SUM");
+      if (t >= n_vec) tq->excl.r[tq->excl.n++] = (int)std::min<int64_t>(rows[t - n_vec], INT32_MAX);   // n < 2^31 is checked by rank() / timeline()
+    } else {
+      CC_CHECK(m.cut == m.cut, "the cut of a REQUIRE / REJECT term is NaN");
+      tq->kills = true;
+    }
+  }
+  CC_CHECK(n_rank >= 1, "no RANK term");
+  if (tq->mode) {
+    CC_CHECK(tq->excl.n >= 1, "an exclude bit needs a stored row that is a RANK term");
+    tq->kills = true;
+  }
+  if (tq->mode == 2) {
+    CC_CHECK(h->grp_host.size() == (size_t)h->n && h->trk_host.size() == (size_t)h->n, "the host columns are out of step with the index");
+    tq->G = h->grp_host[(size_t)tq->excl.r[0]]; tq->Tk = h->trk_host[(size_t)tq->excl.r[0]];
+    CC_CHECK(tq->Tk >= 0, "CC_LIKE_EXCLUDE_TRACK needs RANK rows with a track slot");
+    for (int i = 1; i < tq->excl.n; ++i)
+      CC_CHECK(h->grp_host[(size_t)tq->excl.r[i]] == tq->G && h->trk_host[(size_t)tq->excl.r[i]] == tq->Tk, "CC_LIKE_EXCLUDE_TRACK needs RANK rows of one group and one track slot");
+  }
+  CC_API_END
+}
+
+// What cc_index_rank_terms runs where cc_index_rank_where uploads and scores its queries: the vectors copied and the rows gathered
+// into ONE batch of T queries, scored by the route of that batch, folded.  Leaves v in row 0 of h->scores, w.dead set when a term or a
+// flag can kill a row, and h->which_row written when `which` is asked for.  One RANK vector under MAX / MIN and nothing else: no fold.
+void terms_scores(cc_index* h, const TermsQuery& tq, RowWhere& w, int on_device, hipStream_t s) {
+  const long n = (long)h->n;
+  const int T = tq.spec.T;
+  ensure_queries(h, T);
+  if (tq.n_vec) upload_queries(h, tq.q, tq.n_vec, on_device, s);
+  if (tq.n_rows) gather_rows(h, tq.rows, tq.n_rows, h->q_dev + (size_t)tq.n_vec * h->dim, s);
+  compute_scores(h, T, s);
+  if (T == 1 && tq.spec.combine != CC_COMBINE_SUM && !tq.kills && !tq.which) return;
+  unsigned char *dead = nullptr, *which = nullptr;
+  if (tq.kills) { ensure((void**)&h->dead, &h->dead_cap, (size_t)n); w.dead = dead = h->dead; }
+  if (tq.which) { ensure((void**)&h->which_row, &h->which_row_cap, (size_t)n); which = h->which_row; }
+  if (n % 4 == 0)
+    hipLaunchKernelGGL(terms_fold_kernel<true>, dim3((unsigned)std::min<long>((n / 4 + 255) / 256, 256 * 8)), dim3(256), 0, s, h->scores, n, h->grp, h->trk, tq.spec,
+                       tq.excl, tq.mode, tq.G, tq.Tk, dead, which);
+  else
+    hipLaunchKernelGGL(terms_fold_kernel<false>, dim3((unsigned)std::min<long>((n + 255) / 256, 256 * 8)), dim3(256), 0, s, h->scores, n, h->grp, h->trk, tq.spec,
+                       tq.excl, tq.mode, tq.G, tq.Tk, dead, which);
+  CC_HIP(hipGetLastError());
+}
+
+// Where the ONE score vector of a ranking comes from when it is not a caller's query: the fold of a cc_index_rank_like or that of a
+// cc_index_rank_terms / cc_index_timeline_terms.  Exactly one of the two is set.
+struct FoldQuery { const LikeQuery* like; const TermsQuery* terms; };
+
+void fold_scores(cc_index* h, const FoldQuery& f, RowWhere& w, int on_device, hipStream_t s) {
+  if (f.like) like_scores(h, *f.like, w, s);
+  else terms_scores(h, *f.terms, w, on_device, s);
+}
+
 // cc_index_rank / cc_index_rank_where.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
 // init, eight times (histogram, pick), collect, emit.  Answers past the last row the index could give are padded by one fill.
-// like (cc_index_rank_like; Q is 1 and q unused): the score vector comes from like_scores instead, everything behind it is the same.
+// fold (cc_index_rank_like, cc_index_rank_terms; Q is 1 and q unused): the score vector comes from fold_scores instead, everything behind
+// it is the same; a cc_index_rank_terms that asks for `which` adds one gather of `count` entries behind the last emit.
 int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
-         const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream, const LikeQuery* like = nullptr) {
+         const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream, const FoldQuery* fold = nullptr) {
   CC_API_BEGIN
-  CC_CHECK(h && (q || like) && idx && score, "null argument");
+  CC_CHECK(h && (q || fold) && idx && score, "null argument");
   CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
   CC_CHECK(start >= 0, "start must not be negative");
   CC_CHECK(count >= 1 && count <= (1LL << 40) / Q, "count must be positive (and Q * count below 2^40)");
@@ -1584,14 +1807,18 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const long n = (long)h->n;
   const size_t ob = (size_t)Q * (size_t)count;
-  const size_t qbytes = ((size_t)Q * h->dim * 4 + 255) & ~(size_t)255;
+  const int nq = fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
+  int32_t* which = fold && fold->terms ? fold->terms->which : nullptr;
+  const size_t qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255;
   const bool zero_copy = !on_device && ob * 8 <= kPinResultBytes;            // small host results: written into pinned memory, as search() does
-  const size_t res_bytes = zero_copy ? (ob * 8 + 255) & ~(size_t)255 : 0;
+  const size_t res_bytes = zero_copy ? (ob * (which ? 12 : 8) + 255) & ~(size_t)255 : 0;   // idx, score and, asked for, `which` in a slot of its own
   ensure_pinned(h, qbytes + res_bytes + (size_t)Q * 4);
   unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes + res_bytes);
   int* idx_out = idx; float* sc_out = score;
-  if (zero_copy) { idx_out = reinterpret_cast<int*>(h->pin + qbytes); sc_out = reinterpret_cast<float*>(h->pin + qbytes + ob * 4); }
+  int* which_out = which;
+  if (zero_copy) { idx_out = reinterpret_cast<int*>(h->pin + qbytes); sc_out = reinterpret_cast<float*>(h->pin + qbytes + ob * 4); which_out = reinterpret_cast<int*>(h->pin + qbytes + ob * 8); }
   else if (!on_device) {
+    if (which) { ensure((void**)&h->which_dev, &h->which_dev_cap, ob * 4); which_out = h->which_dev; }
     if (h->out_cap < ob) {
       if (h->idx_dev) hipFree(h->idx_dev);
       if (h->sc_dev) hipFree(h->sc_dev);
@@ -1613,7 +1840,7 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
     hipLaunchKernelGGL(rank_pad_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, sc_out, ob);
   if (n > 0) {
     const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    if (like) like_scores(h, *like, w, s);
+    if (fold) fold_scores(h, *fold, w, on_device, s);
     else {
       upload_queries(h, q, Q, on_device, s);
       compute_scores(h, Q, s);
@@ -1637,23 +1864,27 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
       else hipLaunchKernelGGL(rank_emit_kernel<false>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, nullptr, nullptr, 0);
     }
   }
+  if (which)   // every entry of idx is written by now (an emit or the padding): one term byte per answer, -1 behind the last one
+    hipLaunchKernelGGL(which_gather_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, h->which_row, n, ob, which_out);
   CC_HIP(hipGetLastError());
   if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
   if (!on_device && !zero_copy) {
     CC_HIP(hipMemcpyAsync(idx, h->idx_dev, ob * 4, hipMemcpyDeviceToHost, s));
     CC_HIP(hipMemcpyAsync(score, h->sc_dev, ob * 4, hipMemcpyDeviceToHost, s));
+    if (which) CC_HIP(hipMemcpyAsync(which, h->which_dev, ob * 4, hipMemcpyDeviceToHost, s));
   }
   if (!on_device || total) CC_HIP(hipStreamSynchronize(s));
-  if (zero_copy) { memcpy(idx, idx_out, ob * 4); memcpy(score, sc_out, ob * 4); }
+  if (zero_copy) { memcpy(idx, idx_out, ob * 4); memcpy(score, sc_out, ob * 4); if (which) memcpy(which, which_out, ob * 4); }
   if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
   CC_API_END
 }
 
 // cc_index_timeline.  Launches on one stream: scan, (track reduction,) keys + totals as in rank(), then the histogram kernel.
+// fold (cc_index_timeline_terms; Q is 1 and q unused): the score vector comes from fold_scores, as in rank().
 int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
-             int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int on_device, void* stream) {
+             int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int on_device, void* stream, const FoldQuery* fold = nullptr) {
   CC_API_BEGIN
-  CC_CHECK(h && q && counts, "null argument");
+  CC_CHECK(h && (q || fold) && counts, "null argument");
   CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
   CC_CHECK(min_score == min_score, "min_score is NaN");
   CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
@@ -1662,11 +1893,12 @@ int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, con
   CC_CHECK(n_bins >= 1 && n_bins <= 4096, "n_bins must be in [1, 4096]");
   CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");
   const bool tracks = (flags & CC_RANK_TRACKS) != 0;
-  const RowWhere w = make_where(h, where);
+  RowWhere w = make_where(h, where);
   CC_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const long n = (long)h->n;
-  const size_t qbytes = ((size_t)Q * h->dim * 4 + 255) & ~(size_t)255, cbytes = (size_t)Q * n_bins * 4;
+  const int nq = fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
+  const size_t qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255, cbytes = (size_t)Q * n_bins * 4;
   ensure_pinned(h, qbytes + (size_t)Q * 4);
   unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes);
   ensure((void**)&h->rank_ws, &h->rank_ws_cap, (size_t)Q * 4 + cbytes);     // per query the total, then (host caller) the bins
@@ -1676,8 +1908,11 @@ int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, con
   CC_HIP(hipMemsetAsync(cnt_dev, 0, cbytes, s));
   if (n > 0) {
     const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    upload_queries(h, q, Q, on_device, s);
-    compute_scores(h, Q, s);
+    if (fold) fold_scores(h, *fold, w, on_device, s);
+    else {
+      upload_queries(h, q, Q, on_device, s);
+      compute_scores(h, Q, s);
+    }
     rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
     const dim3 grid((unsigned)((n + kRankRows - 1) / kRankRows), Q);
     const size_t lds = (size_t)n_bins * 4;
@@ -1749,7 +1984,26 @@ int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t sta
                        int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
   LikeQuery like{};
   if (const int rc = like_check(h, rows, n_rows, flags, &like)) return rc;
-  return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &like);
+  const FoldQuery fold{&like, nullptr};
+  return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &fold);
+}
+
+int cc_index_rank_terms(cc_index* h, const float* q, int n_vec, const int64_t* rows, int n_rows, const cc_term* terms, int combine,
+                        int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                        int32_t* idx, float* score, int32_t* which, int64_t* total, int on_device, void* stream) {
+  TermsQuery tq{};
+  if (const int rc = terms_check(h, q, n_vec, rows, n_rows, terms, combine, flags, which, &tq)) return rc;
+  const FoldQuery fold{nullptr, &tq};
+  return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &fold);
+}
+
+int cc_index_timeline_terms(cc_index* h, const float* q, int n_vec, const int64_t* rows, int n_rows, const cc_term* terms, int combine, float min_score, int flags,
+                            const uint8_t* allowed, int n_groups, const cc_row_filter* where, int32_t t0, int32_t bin_seconds, int n_bins,
+                            uint32_t* counts, int64_t* total, int on_device, void* stream) {
+  TermsQuery tq{};
+  if (const int rc = terms_check(h, q, n_vec, rows, n_rows, terms, combine, flags, nullptr, &tq)) return rc;
+  const FoldQuery fold{nullptr, &tq};
+  return timeline(h, nullptr, 1, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, t0, bin_seconds, n_bins, counts, total, on_device, stream, &fold);
 }
 
 // Distinct ranking: the kernels are index_distinct.hip's (its head tells how they fit together); here the checks, the scratch and the copies.
@@ -1923,7 +2177,7 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io, (void*)h->sight_ws, (void*)h->sight_io}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->which_row, (void*)h->which_dev, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io, (void*)h->sight_ws, (void*)h->sight_io}) if (p) hipFree(p);
   if (h->digest_pin) hipHostFree(h->digest_pin);
   if (h->pin) hipHostFree(h->pin);
   if (h->rows_ev) { hipEventSynchronize(h->rows_ev); hipEventDestroy(h->rows_ev); }

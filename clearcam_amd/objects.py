@@ -165,6 +165,19 @@ def row_filter(ts_range=None, classes=None) -> Optional["_lib.RowFilter"]:
     return f
 
 
+class Term(NamedTuple):
+    """One term of `ObjectFinder.compound`: exactly one of text (a query string, encoded by the CLIP text tower), path (a stored
+    crop, by its key or the endpoint's form, as `similar` takes it) or embedding (a vector of the index's width).  role "rank": the
+    term contributes to the ranking value (weight: its factor under combine="sum"); "require": only crops it scores >= cut compete;
+    "reject": crops it scores >= cut do not."""
+    text: Optional[str] = None
+    path: Optional[str] = None
+    embedding: object = None
+    role: str = "rank"
+    weight: float = 1.0
+    cut: Optional[float] = None
+
+
 def pick_track_rows(row: int, members) -> np.ndarray:
     """The query rows of `ObjectFinder.similar(..., whole_track=True)`: `members` are the rows of the clicked crop's track (`row`
     among them).  Up to _lib.LIKE_MAX_ROWS rows: all of them.  More: the clicked row plus 63 of the m - 1 others, those at
@@ -461,6 +474,120 @@ class EmbeddingIndex:
         if run is not cur:
             cur.wait_stream(run)
         return idx, sc, total
+
+    # -- compound search: weighted, all-of and negative terms in one ranking (cc_index_rank_terms / cc_index_timeline_terms) -----------
+    TERM_ROLE = {"rank": _lib.TERM_RANK, "require": _lib.TERM_REQUIRE, "reject": _lib.TERM_REJECT}
+    COMBINE = {"max": _lib.COMBINE_MAX, "min": _lib.COMBINE_MIN, "sum": _lib.COMBINE_SUM}
+
+    def _terms(self, q, rows, roles, weights, cuts, combine, exclude, tracks):
+        """The query side of a compound call, checked -> (vectors (n_vec, dim) f32 or None, row numbers int64, (T,) _lib.Term array,
+        the combine rule, the flags).  Terms 0 .. n_vec-1 are the vectors, the stored rows follow; roles / weights / cuts have one
+        entry per term in that order (roles None: every term ranks; weights None: 1.0; a cut None: 0, read only for "require" /
+        "reject", where it is `cut_f32` of the value given)."""
+        if exclude not in self.LIKE_EXCLUDE:
+            raise ValueError('exclude: None, "rows" or "track"')
+        if combine not in self.COMBINE:
+            raise ValueError('combine: "max", "min" or "sum"')
+        qa = None
+        if q is not None:
+            if bool(getattr(q, "is_cuda", False)):
+                qa = q.contiguous().float().reshape(-1, self.dim)
+            else:
+                qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
+        ids = self._row_numbers([] if rows is None else rows)
+        n_vec = 0 if qa is None else int(qa.shape[0])
+        T = n_vec + int(ids.size)
+        roles = ["rank"] * T if roles is None else list(roles)
+        weights = [1.0] * T if weights is None else list(weights)
+        cuts = [None] * T if cuts is None else list(cuts)
+        if not (len(roles) == len(weights) == len(cuts) == T):
+            raise ValueError(f"roles, weights and cuts need one entry per term ({T})")
+        terms = (_lib.Term * max(T, 1))()
+        for t, (role, wt, cut) in enumerate(zip(roles, weights, cuts)):
+            if role not in self.TERM_ROLE:
+                raise ValueError('role: "rank", "require" or "reject"')
+            terms[t].role, terms[t].weight = self.TERM_ROLE[role], float(wt)
+            terms[t].cut = 0.0 if cut is None else float(self.cut_f32(cut))
+        return qa, ids, terms, self.COMBINE[combine], (_lib.RANK_TRACKS if tracks else 0) | self.LIKE_EXCLUDE[exclude]
+
+    def _rank_terms(self, spec, start, count, allowed, min_score, where, out, which, total, on_device, stream):
+        qa, ids, terms, combine, flags = spec
+        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_rank_terms(self._h, _lib.ptr(qa), 0 if qa is None else int(qa.shape[0]),
+                                                  ids.ctypes.data_as(C.POINTER(C.c_int64)) if ids.size else None, int(ids.size), terms, combine,
+                                                  int(start), int(count), float(self.cut_f32(min_score)), flags, _lib.ptr(al) if al is not None else None,
+                                                  0 if al is None else int(al.size), C.byref(where) if where is not None else None,
+                                                  _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(which), _lib.ptr(total) if total is not None else None,
+                                                  on_device, stream))
+
+    def rank_terms(self, q=None, rows=None, roles=None, weights=None, cuts=None, combine: str = "max", start: int = 0, count: int = 100,
+                   allowed=None, min_score=None, tracks: bool = True, exclude=None, ts_range=None, classes=None, which: bool = False):
+        """`rank` for ONE compound question of up to 64 terms -> (idx (1, count) int32, score (1, count) f32, total (1,) int64[, which
+        (1, count) int32]).  The terms are the vectors `q` ((n_vec, dim), e.g. text embeddings) followed by the stored rows `rows`,
+        scored in one batch as `scores(np.vstack([q, fetch(rows)]))` scores them.  roles[t]: "rank" - the term contributes to the
+        ranking value through `combine` ("max" / "min" of the rank terms' scores, or "sum": the float32 sum of weights[t] * score in
+        term order, negative weights allowed); "require" - a row competes only if the term scores it >= cuts[t]; "reject" - a row
+        scored >= cuts[t] does not compete ("white van, but not this one").  The value vector is ranked exactly as `rank` ranks a
+        query's among the rows left: same answers per track (reduced among the surviving rows, placed by the first of them), tie
+        rules, cut, filters and padding.  exclude="rows" / "track": as in `rank_like`, for the stored rows that are rank terms.  A
+        copy of a rejected crop elsewhere is rejected with it; a copy of an excluded one still answers.  which=True: per answer
+        the term that made its value (max / min: the lowest-numbered one attaining it; sum: the one with the largest product),
+        -1 past the last answer (cc_index_rank_terms)."""
+        spec = self._terms(q, rows, roles, weights, cuts, combine, exclude, tracks)
+        where = self.row_filter(ts_range, classes)
+        start, count = int(start), int(count)
+        shape = (1, count) if count >= 1 and start >= 0 else (1, 1)                 # the library names the error
+        idx, sc, total = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
+        wh = np.empty(shape, np.int32) if which else None
+        if spec[0] is not None and not isinstance(spec[0], np.ndarray):
+            spec = (spec[0].cpu().numpy(),) + spec[1:]
+        self._rank_terms(spec, start, count, allowed, min_score, where, (idx, sc), wh, total, 0, None)
+        return (idx, sc, total, wh) if which else (idx, sc, total)
+
+    def rank_terms_device(self, q=None, rows=None, roles=None, weights=None, cuts=None, combine: str = "max", start: int = 0, count: int = 100,
+                          allowed=None, min_score=None, tracks: bool = True, exclude=None, with_total: bool = True, ts_range=None, classes=None,
+                          which: bool = False):
+        """`rank_terms` with idx / score (and which) left on the GPU, as `rank_like_device` leaves them, on the current torch stream
+        (`distinct_device` can run behind it); with_total=False returns None for the total and waits for nothing."""
+        import torch
+        spec = self._terms(q, rows, roles, weights, cuts, combine, exclude, tracks)
+        where = self.row_filter(ts_range, classes)
+        dev = torch.device("cuda", self.device)
+        if isinstance(spec[0], np.ndarray):                                         # on_device: the vectors are a device pointer too
+            spec = (torch.as_tensor(spec[0]).to(dev),) + spec[1:]
+        k = max(int(count), 1)
+        idx = torch.empty((1, k), dtype=torch.int32, device=dev)
+        sc = torch.empty((1, k), dtype=torch.float32, device=dev)
+        wh = torch.empty((1, k), dtype=torch.int32, device=dev) if which else None
+        total = np.zeros(1, np.int64) if with_total else None
+        cur, run = self._run_stream(dev)
+        self._rank_terms(spec, start, count, allowed, min_score, where, (idx, sc), wh, total, 1, C.c_void_p(run.cuda_stream))
+        if run is not cur:
+            cur.wait_stream(run)
+            if spec[0] is not None:
+                spec[0].record_stream(run)
+        return (idx, sc, total, wh) if which else (idx, sc, total)
+
+    def timeline_terms(self, t0: int, bin_seconds: int, n_bins: int, q=None, rows=None, roles=None, weights=None, cuts=None, combine: str = "max",
+                       allowed=None, min_score=None, tracks: bool = True, exclude=None, ts_range=None, classes=None) -> Tuple[np.ndarray, np.ndarray]:
+        """How the answers of `rank_terms` (same terms and arguments) spread over time -> (counts (1, n_bins) int64, total (1,) int64),
+        binned as `timeline` bins them; `total` equals `rank_terms`' total (cc_index_timeline_terms)."""
+        qa, ids, terms, comb, flags = self._terms(q, rows, roles, weights, cuts, combine, exclude, tracks)
+        if qa is not None and not isinstance(qa, np.ndarray):
+            qa = qa.cpu().numpy()
+        where = self.row_filter(ts_range, classes)
+        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+        if not -(1 << 31) <= t0 < 1 << 31 or not -(1 << 31) <= bin_seconds < 1 << 31 or not -(1 << 31) <= n_bins < 1 << 31:
+            raise ValueError("t0, bin_seconds and n_bins must fit in int32")
+        counts = np.zeros((1, min(max(n_bins, 1), 4096)), np.uint32)               # outside [1, 4096]: the library names the error
+        total = np.zeros(1, np.int64)
+        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        _lib.check(_lib.lib().cc_index_timeline_terms(self._h, _lib.ptr(qa), 0 if qa is None else int(qa.shape[0]),
+                                                      ids.ctypes.data_as(C.POINTER(C.c_int64)) if ids.size else None, int(ids.size), terms, comb,
+                                                      float(self.cut_f32(min_score)), flags, _lib.ptr(al) if al is not None else None,
+                                                      0 if al is None else int(al.size), C.byref(where) if where is not None else None,
+                                                      t0, bin_seconds, n_bins, _lib.ptr(counts), _lib.ptr(total), 0, None))
+        return counts.astype(np.int64), total
 
     # -- distinct answers: near-duplicate answers of a ranked list folded into the first of them (cc_index_gram / cc_index_distinct) ----
     def gram(self, rows, device_out: bool = False):
@@ -1584,6 +1711,110 @@ class ObjectFinder:
             return self._distinct_page(index, table, idx, sc, distinct, start, count)
         idx, sc, total = index.rank_like(rows, start, min(count, len(table.paths)), allowed, min_score, tracks=grouped, exclude=exclude, **kw)
         return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
+
+    def _compound_setup(self, terms, combine, cam_name, timestamp, is_face, min_score, exclude):
+        """What `compound` and `compound_timeline` share, everything checked before any GPU work -> (index, table, the keyword
+        arguments of `EmbeddingIndex.rank_terms` that say what is asked, order) or None when there is nothing to search.  The index
+        takes the vectors before the stored rows: order[t] is the position in `terms` of the index's term t."""
+        terms = [t if isinstance(t, Term) else Term(*t) for t in terms]
+        if not 1 <= len(terms) <= _lib.TERMS_MAX:
+            raise ValueError(f"compound needs 1 .. {_lib.TERMS_MAX} terms")
+        for t in terms:
+            if sum(x is not None for x in (t.text, t.path, t.embedding)) != 1:
+                raise ValueError("a Term needs exactly one of text, path and embedding")
+            if t.role not in EmbeddingIndex.TERM_ROLE:
+                raise ValueError('a Term\'s role: "rank", "require" or "reject"')
+            if t.role != "rank" and (t.cut is None or t.cut != t.cut):
+                raise ValueError("a require / reject Term needs a cut")
+        if not any(t.role == "rank" for t in terms):
+            raise ValueError("compound needs at least one rank Term")
+        if combine not in EmbeddingIndex.COMBINE:
+            raise ValueError('combine: "max", "min" or "sum"')
+        if exclude not in (None, "rows", "track"):
+            raise ValueError('exclude: None, "rows" or "track"')
+        if min_score is not None and min_score != min_score:
+            raise ValueError("min_score is NaN")
+        if not self._has_rows(is_face):
+            print("No embeddings available.")
+            return None
+        index, table = self._index_and_table(is_face)
+        if not hasattr(index, "rank_terms"):
+            raise RuntimeError("this index cannot rank compound questions")
+        vec_at = [i for i, t in enumerate(terms) if t.path is None]
+        row_at = [i for i, t in enumerate(terms) if t.path is not None]
+        rows = np.array([self._stored_row(table, terms[i].path) for i in row_at], np.int64)
+        for i in vec_at:
+            if terms[i].embedding is not None and np.size(as_numpy(terms[i].embedding)) != index.dim:
+                raise ValueError(f"a Term's embedding has {np.size(as_numpy(terms[i].embedding))} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
+        allowed = table.allowed(cam_name, timestamp)
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return None
+        for g in live:
+            if table.bad[g]:                        # names the reference raises on: no host ranking is grown for this call
+                raise ValueError(f"compound search cannot rank the folder {table.dirs[g]}: it holds crop names that do not parse")
+        vecs = [np.asarray(as_numpy(self.model._encode_text(terms[i].text).numpy() if terms[i].text is not None else terms[i].embedding),
+                           np.float32).reshape(-1) for i in vec_at]
+        order = vec_at + row_at
+        ranked = [int(r) for r, i in zip(rows, row_at) if terms[i].role == "rank"]
+        if exclude == "track" and ranked and all(table.slot[r] < 0 for r in ranked):
+            exclude = "rows"                        # crops without a track id stand alone, as in `similar`
+        ask = dict(q=np.stack(vecs) if vecs else None, rows=rows if rows.size else None, roles=[terms[i].role for i in order],
+                   weights=[terms[i].weight for i in order], cuts=[terms[i].cut for i in order], combine=combine, allowed=allowed,
+                   min_score=min_score, tracks=any(table.truthy[g] for g in live), exclude=exclude)
+        return index, table, ask, order
+
+    def compound(self, terms, start=0, count=100, combine="max", cam_name=None, timestamp=None, is_face=False, min_score=None, ts_range=None,
+                 classes=None, exclude=None, explain=False, distinct=None, distinct_depth=1024):
+        """One ranking for a question made of several terms -> (results, total) as `search_page` returns them.  `terms`: 1 .. 64
+        `Term`s - texts, stored crops and embeddings, each with a role: "rank" terms make a crop's score (combine="max" / "min" of
+        their scores, or "sum" of weight * score, where a negative weight means "less of this"), a "require" term must score the
+        crop >= its cut ("person, AND it looks like this clicked crop"), a "reject" term must not ("white van, but not this one":
+        the clicked van and every crop that looks like it leave the results).  Folders, cut, row filter and grouping per track are
+        `search_page`'s; exclude="rows" / "track" is `similar`'s, for the stored crops that are rank terms; distinct /
+        distinct_depth as in `search_page`.  explain=True appends to each result the position in `terms` of the term that made its
+        score (max / min: the first one attaining it; sum: the one with the largest product).  An unknown path raises KeyError;
+        a folder with crop names the reference raises on raises ValueError.  One `EmbeddingIndex.rank_terms` call: only `count`
+        answers leave the GPU, no score matrix."""
+        where = row_filter(ts_range, classes)
+        start, count = int(start), int(count)
+        if start < 0 or count < 1:
+            raise ValueError("compound needs start >= 0 and count >= 1")
+        distinct, distinct_depth = self._distinct_args(distinct, distinct_depth)
+        setup = self._compound_setup(terms, combine, cam_name, timestamp, is_face, min_score, exclude)
+        if setup is None:
+            return [], 0
+        index, table, ask, order = setup
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        if distinct is not None:
+            depth = min(distinct_depth, len(table.paths))
+            out = index.rank_terms_device(start=0, count=depth, with_total=False, which=explain, **ask, **kw)
+            res, total = self._distinct_page(index, table, out[0], out[1], distinct, start, count)
+            if explain:                             # a row answers once: the term of a kept answer is that of its row in the list walked
+                term_of = dict(zip(out[0][0].cpu().tolist(), out[3][0].cpu().tolist()))
+                res = [r + (order[term_of[table.row_of(r[0])]],) for r in res]
+            return res, total
+        out = index.rank_terms(start=start, count=min(count, len(table.paths)), which=explain, **ask, **kw)
+        res = [(table.paths[r], float(v)) for r, v in zip(out[0][0].tolist(), out[1][0]) if r >= 0]
+        if explain:
+            res = [r + (order[w],) for r, w in zip(res, out[3][0].tolist())]
+        return res, int(out[2][0])
+
+    def compound_timeline(self, terms, t0=0, bin_seconds=3600, n_bins=24, combine="max", cam_name=None, timestamp=None, is_face=False,
+                          min_score=None, ts_range=None, classes=None, exclude=None):
+        """How the results of `compound` (same terms and arguments) spread over the day -> (counts (n_bins,) int64, total), binned as
+        `timeline` bins them; `total` is `compound`'s.  One `EmbeddingIndex.timeline_terms` call."""
+        where = row_filter(ts_range, classes)
+        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+        if bin_seconds < 1 or not 1 <= n_bins <= 4096:
+            raise ValueError("compound_timeline needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
+        setup = self._compound_setup(terms, combine, cam_name, timestamp, is_face, min_score, exclude)
+        if setup is None:
+            return np.zeros(n_bins, np.int64), 0
+        index, table, ask, _ = setup
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        c, total = index.timeline_terms(t0, bin_seconds, n_bins, **ask, **kw)
+        return c[0], int(total[0])
 
     def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False, ts_range=None, classes=None):
         """:356-390.  ts_range / classes: the row filter of `search_page`; with one given the device ranks (`EmbeddingIndex.rank`),

@@ -561,6 +561,62 @@ int cc_index_fetch_rows(cc_index* h, const int64_t* rows, int n, float* out, int
 int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t start, int64_t count, float min_score, int flags,
                        const uint8_t* allowed, int n_groups, const cc_row_filter* where,
                        int32_t* idx, float* score, int64_t* total, int on_device, void* stream);
+/* Compound search: up to CC_TERMS_MAX terms in ONE ranking.  A term is a vector the caller brings (a text or image embedding) or a
+ * stored row, and it has a role: it contributes to the ranking value (RANK, through the combine rule and its weight), it must hold
+ * (REQUIRE: "person AND it looks like this crop") or it must not (REJECT: "white van, but not this one").  ONE answer list comes
+ * back, as from cc_index_rank_like, and optionally the term that made each answer's value.
+ *   1. Terms.  T = n_vec + n_rows, 1 <= T <= CC_TERMS_MAX.  Terms 0 .. n_vec-1 are the vectors q ((n_vec, dim) f32, on the device
+ *      with on_device, as cc_index_rank's queries); terms n_vec .. T-1 are the stored rows `rows` (numbers on the HOST, gathered on
+ *      the device as cc_index_fetch_rows decodes them).  terms[t] describes term t; the array is read on the host at the call.
+ *   2. Scores.  S (T, N) is bit for bit what cc_index_scores returns for those T vectors in that order, by the same route for that
+ *      batch size and index size (scan passes, the f32 / bf16 GEMM, the int8 MFMA kernel); cc_index_last_path reports it.  No
+ *      embedding crosses the bus for a stored row.
+ *   3. Ranking value v[r], from the RANK terms only, in ascending term order:
+ *        CC_COMBINE_MAX / CC_COMBINE_MIN: the maximum / minimum of S[t][r] in the total order of the ranking keys (+0 above -0);
+ *        CC_COMBINE_SUM: v = +0.0f; then for each RANK term v = v + weight_t * S[t][r], the product and the sum each rounded to f32
+ *        on its own (never fused), so plain float32 arithmetic in that order reproduces v bit for bit.
+ *      weight is ignored for MAX / MIN; a negative weight ("less of this") is allowed.
+ *   4. Dead rows.  A row is dead when a REQUIRE term scores it below its cut (NOT S[t][r] >= cut), when a REJECT term scores it at
+ *      or above its cut (S[t][r] >= cut; IEEE f32 compares, -0 == +0), or by cc_index_rank_like's two exclude bits, which here act
+ *      on the stored rows that are RANK terms: CC_LIKE_EXCLUDE_ROWS: those rows are dead; CC_LIKE_EXCLUDE_TRACK: every row that
+ *      shares their common group and slot is dead (they must share one group and one slot >= 0, as in cc_index_rank_like).  A score
+ *      depends on its (vector, row) pair alone, so a byte-equal copy of a REJECT row elsewhere is rejected with it, while a copy of
+ *      an EXCLUDED row still competes, as in cc_index_rank_like: "not this object" against "not this stored crop".
+ *   5. Result.  That of cc_index_rank_where for a single query whose score vector is v, among the rows that are not dead, allowed
+ *      and passing `where`: the same keys, tie rules, min_score cut (on v), total, -1 / -inf padding, on_device and stream
+ *      semantics.  A track is reduced among its surviving rows and placed by its first surviving row: the call answers as an index
+ *      built from the surviving rows would.
+ *   6. which may be NULL.  Otherwise `count` int32 (on the device with on_device): for each answer the term that made v at the row
+ *      idx names (a track: its best surviving crop).  MAX / MIN: the lowest-numbered RANK term attaining v.  SUM: the RANK term with
+ *      the largest product weight_t * S[t][r] in key order, the lowest-numbered on ties.  -1 where idx is -1.
+ *   7. cc_index_timeline_terms is cc_index_timeline (one query) on the same v and the same dead rows; its total equals
+ *      cc_index_rank_terms'.
+ *   8. Errors (-22, nothing changed, checked on the host before any launch): those of cc_index_rank_where / cc_index_timeline; T out
+ *      of range, a negative n_vec / n_rows, a null q / rows with a positive count, a null terms; no RANK term; an unknown role or
+ *      combine; a non-finite weight on a RANK term under SUM; a NaN cut on a REQUIRE / REJECT term; a row number outside [0, size);
+ *      an exclude bit without a stored-row RANK term; unknown flag bits.  NaN scores are not supported, as everywhere.
+ * Launches: the vectors are copied and the rows gathered where queries stand, ONE scoring call scores all T, one pass
+ * (terms_fold_kernel) folds S into v in place over its row 0 and writes one dead byte a row (only when a term or a flag can kill a
+ * row) and one `which` byte a row (only when asked for), then the launches of cc_index_rank_where / cc_index_timeline for one query
+ * follow unchanged, plus a gather of `count` entries for `which`.  One RANK vector, MAX or MIN, nothing else: no fold at all. */
+#define CC_TERMS_MAX 64
+#define CC_TERM_RANK    0   /* contributes to the ranking value v through the combine rule */
+#define CC_TERM_REQUIRE 1   /* a row competes only if S[t][r] >= cut  (IEEE f32 compare) */
+#define CC_TERM_REJECT  2   /* a row is dead if S[t][r] >= cut */
+#define CC_COMBINE_MAX 0
+#define CC_COMBINE_MIN 1
+#define CC_COMBINE_SUM 2
+typedef struct { int32_t role; float weight; float cut; } cc_term;
+int cc_index_rank_terms(cc_index* h, const float* q, int n_vec, const int64_t* rows, int n_rows,
+                        const cc_term* terms, int combine,
+                        int64_t start, int64_t count, float min_score, int flags,
+                        const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                        int32_t* idx, float* score, int32_t* which, int64_t* total, int on_device, void* stream);
+int cc_index_timeline_terms(cc_index* h, const float* q, int n_vec, const int64_t* rows, int n_rows,
+                            const cc_term* terms, int combine, float min_score, int flags,
+                            const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                            int32_t t0, int32_t bin_seconds, int n_bins,
+                            uint32_t* counts, int64_t* total, int on_device, void* stream);
 /* Distinct answers: thin ranked lists so that the same picture, stored under many track ids, on many days or by many cameras,
  * answers once.  The embedding-space counterpart of what the detector does with boxes, behind any of the ranking calls above. */
 #define CC_DISTINCT_MAX_DEPTH 1024
