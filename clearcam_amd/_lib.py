@@ -15,7 +15,7 @@ SYMBOLS = [
     "cc_yolo_get_tensor", "cc_yolo_get_tensor_frames", "cc_yolo_nonfinite",
     "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv2d_ex", "cc_route_log_take", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
     "cc_dev_decode", "cc_dev_head_tail", "cc_dev_topk_nms", "cc_dev_blaze_post",
-    "cc_dev_pool", "cc_dev_pool_choice", "cc_dev_fuse", "cc_dev_conv_src", "cc_dev_affine", "cc_dev_face_pre",
+    "cc_dev_pool", "cc_dev_pool_choice", "cc_dev_fuse", "cc_dev_conv_src", "cc_dev_conv_det", "cc_dev_conv_det_choice", "cc_dev_affine", "cc_dev_face_pre",
     "cc_dev_csp", "cc_dev_csp_choice", "cc_dev_stem",
     "cc_dev_attention", "cc_dev_layernorm", "cc_dev_assemble_ln", "cc_dev_patchify", "cc_dev_embed", "cc_dev_l2norm",
     "cc_clip_create", "cc_clip_load", "cc_clip_finalize", "cc_clip_encode_image", "cc_clip_encode_text",
@@ -53,7 +53,7 @@ class SrcDesc(C.Structure):
 
 DEV_CSP_LAYERS = 3                                    # CC_DEV_CSP_LAYERS: *choice of cc_dev_csp for the four conv launches
 DEV_CONV_ADOWN = 100                                  # CC_DEV_CONV_ADOWN: choice[0] of cc_dev_conv_src for the averaging kernel
-ROUTE_REC_INTS = 18                                   # ints per cc_route_log_take record
+ROUTE_REC_INTS = 23                                   # ints per cc_route_log_take record
 
 
 class FaceAlignRec(C.Structure):
@@ -146,6 +146,8 @@ def lib() -> C.CDLL:
         "cc_dev_pool_choice": [C.c_int, vp, C.c_int, C.c_int, vp] + [C.c_int] * 12 + [ip],
         "cc_dev_fuse": [C.c_int, C.c_int, vp, ip, ip, ip, ip, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp],
         "cc_dev_conv_src": [C.POINTER(ConvDesc), C.POINTER(SrcDesc), C.POINTER(SrcDesc), vp, vp, vp, ip, vp],
+        "cc_dev_conv_det": [C.POINTER(ConvDesc), C.POINTER(SrcDesc), C.POINTER(SrcDesc), vp, vp, vp, vp, ip, vp],
+        "cc_dev_conv_det_choice": [C.POINTER(ConvDesc), C.POINTER(SrcDesc), C.POINTER(SrcDesc), vp, vp, ip],
         "cc_dev_affine": [C.c_int, vp, vp, vp, vp, C.c_longlong, C.c_int, vp],
         "cc_dev_face_pre": [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp],
         "cc_dev_csp": [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp),

@@ -827,7 +827,8 @@ void route_log_append(const ConvP& p, const ConvChoice& c) {
   const int rec[ROUTE_REC_INTS] = {(int)c.kernel, c.sched, c.bm, c.bn, p.ks, p.stride, (p.Ho > sym_ho || p.Wo > sym_wo) ? 1 : 0, p.act,
                                    p.res ? (p.res_f32 ? 2 : 1) : 0, p.out_f32 ? 1 : 0,
                                    (p.Cout % 8 == 0 && p.out_coff % 8 == 0 && p.out_cstride % 8 == 0) ? 1 : 0,
-                                   p.B, p.Hin, p.Win, p.Cin, p.Cout, p.Ho, p.Wo};
+                                   p.B, p.Hin, p.Win, p.Cin, p.Cout, p.Ho, p.Wo,
+                                   p.split ? 1 : 0, c.simple ? 1 : 0, c.two ? 1 : 0, c.cprw, c.ns};
   std::lock_guard<std::mutex> lock(g_route_mutex);
   g_route_recs.insert(g_route_recs.end(), rec, rec + ROUTE_REC_INTS);
 }

@@ -59,8 +59,8 @@ void launch_conv_chosen(int dt, const ConvP& p, hipStream_t stream, ConvChoice* 
 // process-wide, mutex-guarded list; cc_route_log_take reads and clears it.  Off by default: one relaxed load per launch.
 // A record is ROUTE_REC_INTS ints: kernel, sched, bm, bn, ks, stride, asym (Ho / Wo exceed the symmetric formula), act, residual kind
 // (0 none, 1 storage type, 2 f32), out_f32, aligned8 (Cout, out_coff, out_cstride all multiples of 8), then the layer's shape
-// B, Hin, Win, Cin, Cout, Ho, Wo.
-constexpr int ROUTE_REC_INTS = 18;
+// B, Hin, Win, Cin, Cout, Ho, Wo, then what picks the K loop: split (two weight planes), simple, two, cprw, ns of the ConvChoice.
+constexpr int ROUTE_REC_INTS = 23;
 extern std::atomic<int> g_route_log;
 void route_log_append(const ConvP& p, const ConvChoice& c);
 int route_log_take(int* recs, int cap);                // moves up to `cap` records out (the rest stay), returns how many the list held

@@ -229,6 +229,15 @@ int cc_dev_l2norm(float* x_dev, int rows, int D, float eps, void* stream);
  * already representable are kept; two planes for dtype 3).  choice (int[6] or null) receives ConvKernel, phase schedule, tile pixels,
  * tile channels, simple loader, two-source eight-wave loader (csrc/conv_select.h); the averaging kernel reports CC_DEV_CONV_ADOWN,
  * 0, 128, its channel tile (64 / 128), 0, 0.
+ * cc_dev_conv_det: the same launch as the detector's plans build it: the same two views and descriptor, and also d->groups (weights
+ * (Cout, Cin / groups, k, k), densified to block-diagonal rows as the detector packs its DDetect box branch) and a residual res_dev (null:
+ * none) read through d->res_f32 / res_cstride / res_coff on the output's pixel grid, added after the activation.  res_dev may be out_dev
+ * (RepNBottleneck's x + cv2(cv1(x)) in place) when it is the output's own view (same type, cstride and coff); not with the averaging
+ * loader.  choice (int[8] or null) receives ConvKernel, phase schedule, tile pixels, tile channels, simple loader, two-source loader, then
+ * the generic kernel's 16-byte chunks per LDS row and LDS stages (cprw, ns of ConvChoice, csrc/conv_select.h).  Everything is validated,
+ * and the selector asked, before the first HIP call.
+ * cc_dev_conv_det_choice: the same checks on the same arguments without weights, no launch and no HIP call: choice = what
+ * cc_dev_conv_det would run (the pointers are only checked for null and alignment).
  * cc_dev_affine: affine_kernel (AdaFace's BatchNorm in front of a padded conv): y = x * scale[c] + shift[c] over n elements of C-channel
  * pixels in the storage type (x may be y); scale / shift device float32[C]; C whole 16-byte chunks.
  * cc_dev_face_pre: face_pre_kernel: (B,112,112,3) uint8 or float32 frames -> (B,112,112,cpad) storage type, channels reversed,
@@ -243,6 +252,9 @@ int cc_dev_fuse(int dtype, int n, const void* const* in_dev, const int* H, const
                 void* out_dev, int out_cstride, int out_coff, int B, int Ho, int Wo, int C, void* stream);
 int cc_dev_conv_src(const cc_conv_desc* d, const cc_src_desc* s0, const cc_src_desc* s1, const float* w_oihw, const float* bias, void* out_dev,
                     int* choice, void* stream);
+int cc_dev_conv_det(const cc_conv_desc* d, const cc_src_desc* s0, const cc_src_desc* s1, const float* w_oihw, const float* bias,
+                    const void* res_dev, void* out_dev, int* choice, void* stream);
+int cc_dev_conv_det_choice(const cc_conv_desc* d, const cc_src_desc* s0, const cc_src_desc* s1, const void* res_dev, void* out_dev, int* choice);
 int cc_dev_affine(int dtype, const void* x_dev, void* y_dev, const float* scale_dev, const float* shift_dev, long long n, int C, void* stream);
 int cc_dev_face_pre(int dtype, const void* img_dev, int img_f32, void* out_dev, int B, int cpad, void* stream);
 /* Single-launch entries of the fused multi-conv kernels (csrc/dev_fused.hip): ONE launch of a kernel that keeps its intermediates on
@@ -273,10 +285,11 @@ int cc_dev_csp_choice(int dtype, int split, int hid, int B, int H, int W, int va
 int cc_dev_stem(int dtype, int split, const void* frames_dev, int frame_f32, const int64_t* offsets, const int32_t* heights, const int32_t* widths,
                 int B, int res, int ragged, const float* w_oihw, const float* bias, int Cout, void* out_dev, int out_cstride, int out_coff,
                 int* info, void* stream);
-/* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 18 ints each into `records` and sets *n to the number of records
+/* Route log (cc_dev_set key "route_log"): moves up to `cap` records of 23 ints each into `records` and sets *n to the number of records
  * the log held; records that did not fit (*n > cap) stay in the log for the next call.  A record: kernel, schedule, tile pixels, tile channels, k, stride, Ho / Wo beyond the symmetric formula,
  * act, residual (0 none / 1 storage type / 2 float32), out_f32, Cout / out_coff / out_cstride all multiples of 8, then B, H, W, Cin,
- * Cout, Ho, Wo of the layer. */
+ * Cout, Ho, Wo of the layer, then what picks the K loop: two weight planes, simple loader, two-source loader, 16-byte chunks per LDS row and
+ * LDS stages of the generic kernel. */
 int cc_route_log_take(int* records, int cap, int* n);
 /* Diagnostic (kernel tuning, tools/dev/stream_ab.py, variant_sweep.py): average device milliseconds of one launch of the conv above on random
  * 16-bit data resident in HBM, weights packed once, `iters` launches between two events.  Not part of the drop-in surface. */

@@ -42,7 +42,8 @@ class Case:
     pad: int = -1                       # -1: k // 2
     Ho: int = 0                         # 0: the symmetric formula
     Wo: int = 0
-    res: Optional[str] = None           # None | "storage" | "f32" | "inplace" (f32 residual that IS the f32 output buffer)
+    res: Optional[str] = None           # None | "storage" | "f32" | "inplace" (f32 residual that IS the f32 output buffer) | "inplace16" (a
+                                        # storage-type residual that IS the 16-bit output buffer: RepNBottleneck's x + cv2(cv1(x)))
     out_f32: bool = False
     out_cstride: int = 0                # 0: Cout
     out_coff: int = 0
@@ -70,7 +71,7 @@ class Case:
 
     def route_key(self) -> Tuple[int, ...]:
         (ho, wo), (sh, sw) = self.out_hw, self.sym_out
-        res = RES_NONE if self.res is None else (RES_STORAGE if self.res == "storage" else RES_F32)
+        res = RES_NONE if self.res is None else (RES_STORAGE if self.res in ("storage", "inplace16") else RES_F32)
         al8 = int(self.Cout % 8 == 0 and self.out_coff % 8 == 0 and self.ocs % 8 == 0)
         return self.expect + (self.k, self.stride, int(ho > sh or wo > sw), self.act, res, int(self.out_f32), al8)
 
@@ -199,6 +200,29 @@ def _plan_cases() -> List[Case]:
 
 
 CASES += _plan_cases()
+
+
+def _detector_cases() -> List[Case]:
+    """The detector's epilogues on the families above that had none of them: SiLU (act 1) wherever a family ran act 0 / 2 / 3 / 4 only, and
+    SiLU followed by a 16-bit residual that is the output buffer itself (yolo.hip csp_branch: x1 = x1 + cv2(cv1(x1)) in place) on the
+    generic 128 x 32 tile, the four-wave 128 x 128 kernel and the persistent loop."""
+    by_name = {c.name: c for c in CASES}
+    out = []
+    silu_of = ["gen_3x3_64_80-staged_act2", "gen_3x3_64_20-staged_gelu", "gen_3x3_64_80-slice_staged_prelu", "gen_1x1_s2_64_128"]
+    silu_of += [f"small{v}_1x1_64_40-staged_prelu" for v in (9, 94, 95, 96, 97)]
+    silu_of += [f"{nm}-{tag}-gelu" for nm in ("big_1x1", "big_3x3_odd") for tag in ("tile256", "tile128", "phase_one_tile", "phase_sched0", "phase_buffer", "persist")]
+    silu_of += ["persist_gemm_m33300_k64_n512-gelu", "wave_64_64_ragged-prelu", "ws_64_64_ragged-prelu", "stream_256_256_ragged-gelu", "direct_1x1_28_32-gelu"]
+    for n in silu_of:
+        b = by_name[n]
+        out.append(replace(b, name=b.name.rsplit("-", 1)[0] + ("-slice_silu" if b.out_cstride else "-silu"), act=1))
+    for n in ("gen_3x3_64_80-res16", "big_3x3_odd-tile128-res16", "big_3x3_odd-persist-res16", "persist_gemm_m33300_k64_n512-gelu"):
+        b = by_name[n]
+        out.append(replace(b, name=b.name.rsplit("-", 1)[0] + "-silu_inplace16", act=1, res="inplace16"))
+    out.append(replace(by_name["tile64_ragged-res16_silu"], name="tile64_ragged-silu", res=None))
+    return out
+
+
+CASES += _detector_cases()
 
 assert len({c.name for c in CASES}) == len(CASES)
 

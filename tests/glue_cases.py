@@ -392,7 +392,8 @@ def _conv_cases() -> List[ConvCase]:
         base = ConvCase(nm, s0, s1, 10, 14, 64, 1, G32, ex_variant=V_PIX32_4)
         cs += both_acts(replace(base, name=nm + "-auto_c64"))
         for tag, pf, sched in (("sched0", 0, SCHED0), ("one_tile", 32, ONE_TILE), ("persist", 512, PERSIST)):
-            cs += both_acts(replace(base, name=f"{nm}-phase_{tag}", Cout=256, variant=V_PHASE, phase_flags=pf, expect=(PHASE, sched, 256, 256, 0, 1), ex_variant=V_PHASE))
+            cs += both_acts(replace(base, name=f"{nm}-phase_{tag}", Cout=256, variant=V_PHASE, phase_flags=pf, expect=(PHASE, sched, 256, 256, 0, 1), ex_variant=V_PHASE,
+                                         dtypes=("f16", "bf16", "f16s")))
         cs += both_acts(replace(base, name=nm + "-direct", variant=V_DIRECT, expect=DIR, ex_variant=None, dtypes=("f16", "bf16", "f32")))
         cs += both_acts(replace(base, name=nm + "-generic", variant=V_GENERIC, expect=(GENERIC, 0, 128, 64, 0, 0), ex_variant=V_GENERIC, dtypes=("f16", "bf16", "f32", "f16s")))
         cs.append(replace(base, name=nm + "-direct_split", variant=V_DIRECT, expect=DIR, ex_variant=None, dtypes=("f16s",)))

@@ -187,7 +187,7 @@ def test_calibration_aware_rounding_generalises_to_held_out_pixels(lib_path):
 
 
 def test_route_record_width_matches_the_library_source():
-    """The route-log record is 18 ints in three places: the C++ constant, the header's comment and the Python binding."""
+    """The route-log record is as wide in three places: the C++ constant, the header's comment and the Python binding."""
     src = open(os.path.join(ROOT, "clearcam_amd", "csrc", "conv_select.h")).read()
     width = int(re.search(r"constexpr int ROUTE_REC_INTS = (\d+);", src).group(1))
     hdr = open(os.path.join(ROOT, "include", "clearcam_hip.h")).read()
@@ -196,4 +196,6 @@ def test_route_record_width_matches_the_library_source():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import epilogue_cases as ec
-    assert len(ec.KEY_FIELDS) + 7 == width               # the key, then B, H, W, Cin, Cout, Ho, Wo
+    import detector_route_cases as drc
+    assert drc.EXT_FIELDS == ("split", "simple", "two", "cprw", "ns")
+    assert len(ec.KEY_FIELDS) + 7 + len(drc.EXT_FIELDS) == width      # the key, then B, H, W, Cin, Cout, Ho, Wo, then what picks the K loop

@@ -15,7 +15,7 @@ approximates.
                   sum in any order, doubled for the matrix unit's unspecified internal rounding; 2K for f32 storage (the products round
                   too), plus 16 * 2^-24 |y64| for expf / tanhf where f32 storage runs act 1 / 2.
 Output buffers start as NaN (a kernel that stores nothing, or not everywhere, fails; a channel-slice case must leave the channels
-outside its slice NaN); in-place cases start as the residual.
+outside its slice NaN); in-place cases (f32, and the detector's 16-bit one) start as the residual.
 
 Measured on the MI355X: the comment above BARS and docs/measurement.md ("Conv epilogues against float64").
 """
@@ -44,6 +44,8 @@ U24 = 2.0 ** -24
 # D exceeds the detector's bar where the epilogue puts many outputs near zero (conv + N(0,1) residual, PReLU with small slopes): there
 # the f32 accumulation noise of a K-term sum of O(1) magnitude (~2^-24) is a larger share of the output's quantum.  Bar 1 stays strict
 # on every case (each element is one of the two storage values around y64; max 0.509 ulp).  D = 3 x 0.0094.  R and R_cell stay.
+# The detector's epilogues added later (SiLU on every family, SiLU + a 16-bit residual that is the output buffer; 64 tests): R 0.118 %,
+# R_cell 1.04 %, D 0.0051 ulp (big_3x3_odd-tile128-silu_inplace16, f16) - under the figures above.
 # f32 outputs: the largest err / bound was 0.0163 (the persistent kernel's M = 33 300, K = 64 GEMM with the in-place residual).
 BARS = dict(R=rc.BARS["R"], R_cell=rc.BARS["R_cell"], D=2.8e-2)
 
@@ -77,7 +79,7 @@ def run_case(c: ec.Case, dtype: str):
     L = _lib.lib()
     t = TDT[dtype]
     Ho, Wo = c.out_hw
-    res_kind = None if c.res is None else ("storage" if c.res == "storage" else "f32")
+    res_kind = None if c.res is None else ("storage" if c.res in ("storage", "inplace16") else "f32")
     x, w, b, slope, res, y64, mag = _problem(c.ref_id, dtype, res_kind)
     xd = x.permute(0, 2, 3, 1).contiguous().to("cuda", t)
     out_f32 = c.out_f32 or dtype == "f32"
@@ -85,6 +87,10 @@ def run_case(c: ec.Case, dtype: str):
     resd, rcs = None, c.res_cstride or c.Cout
     if c.res == "inplace":
         assert out_f32 and c.ocs == c.Cout and rcs == c.Cout
+        out.copy_(res.permute(0, 2, 3, 1))
+        resd = out
+    elif c.res == "inplace16":                         # the 16-bit residual IS the output buffer (the detector's RepNBottleneck)
+        assert not out_f32 and c.ocs == c.Cout and rcs == c.Cout
         out.copy_(res.permute(0, 2, 3, 1))
         resd = out
     elif c.res is not None:
