@@ -13,7 +13,7 @@ SYMBOLS = [
     "cc_yolo_create", "cc_yolo_load", "cc_yolo_calibrate", "cc_yolo_calibration_info", "cc_gptq_round_f16", "cc_yolo_finalize", "cc_yolo_detect", "cc_yolo_set_in_flight", "cc_yolo_submit", "cc_yolo_wait",
     "cc_yolo_detect_ragged", "cc_yolo_submit_ragged", "cc_letterbox_geometry", "cc_yolo_plans_built",
     "cc_yolo_get_tensor", "cc_yolo_get_tensor_frames", "cc_yolo_nonfinite",
-    "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv2d_ex", "cc_route_log_take", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
+    "cc_yolo_last_gpu_ms", "cc_yolo_profile", "cc_yolo_profile_graph", "cc_yolo_destroy", "cc_conv2d_nhwc", "cc_conv2d_ex", "cc_conv2d_ex_route", "cc_route_log_take", "cc_conv_bench", "cc_dev_set", "cc_round_weights", "cc_attn_bench",
     "cc_dev_decode", "cc_dev_head_tail", "cc_dev_topk_nms", "cc_dev_blaze_post",
     "cc_dev_pool", "cc_dev_pool_choice", "cc_dev_fuse", "cc_dev_conv_src", "cc_dev_conv_det", "cc_dev_conv_det_choice", "cc_dev_affine", "cc_dev_face_pre",
     "cc_dev_csp", "cc_dev_csp_choice", "cc_dev_stem",
@@ -54,6 +54,7 @@ class SrcDesc(C.Structure):
 DEV_CSP_LAYERS = 3                                    # CC_DEV_CSP_LAYERS: *choice of cc_dev_csp for the four conv launches
 DEV_CONV_ADOWN = 100                                  # CC_DEV_CONV_ADOWN: choice[0] of cc_dev_conv_src for the averaging kernel
 ROUTE_REC_INTS = 23                                   # ints per cc_route_log_take record
+CONV_CHOICE_INTS = 8                                  # ints cc_conv2d_ex_route and cc_dev_conv_det write to `choice`: kernel, sched, bm, bn, simple, two, cprw, ns (cc_conv2d_ex: the first four)
 
 
 class FaceAlignRec(C.Structure):
@@ -137,6 +138,7 @@ def lib() -> C.CDLL:
         "cc_conv2d_nhwc": [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                            C.c_int, vp, C.c_int, vp],
         "cc_conv2d_ex": [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, ip, vp],
+        "cc_conv2d_ex_route": [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, ip, vp],
         "cc_route_log_take": [ip, C.c_int, ip],
         "cc_dev_decode": [vp, ip, ip, C.c_int, vp, C.c_float, vp, ip, vp],
         "cc_dev_head_tail": [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, ip, ip, C.c_int, vp, C.c_float, vp, ip, vp],

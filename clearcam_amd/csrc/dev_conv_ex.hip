@@ -1,17 +1,19 @@
 // Development entry cc_conv2d_ex: ONE conv launch with any ConvP the CLIP, AdaFace and BlazeFace plans build (every activation, PReLU
 // slopes, a 16-bit or f32 residual that may alias the output, f32 output, channel-slice views, asymmetric padding through Ho / Wo),
-// weights packed by the face nets' own pack_conv.  Reports the ConvChoice the launch ran with.  A translation unit of its own because
-// net_common.h and yolo_plan.h (dev_bench.hip) each define the host tensor type.
+// weights packed by the face nets' own pack_conv.  Reports the ConvChoice the launch ran with: four ints (kernel, sched, bm, bn), as its
+// callers have always sized the buffer; cc_conv2d_ex_route is the same launch reporting the eight ints of cc_dev_conv_det.
+// A translation unit of its own because net_common.h and yolo_plan.h (dev_bench.hip) each define the host tensor type.
 #include "conv_select.h"
 #include "net_common.h"
 #include "../../include/clearcam_hip.h"
 
 using namespace cc;
 
-extern "C" {
+namespace {
 
-int cc_conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
-                 const void* res_dev, void* out_dev, int* choice, void* stream) {
+// nchoice: ints of `choice` the caller's buffer holds (4 or 8)
+int conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
+              const void* res_dev, void* out_dev, int* choice, int nchoice, void* stream) {
   std::vector<void*> owner;
   auto release = [&]() { for (void* q : owner) hipFree(q); owner.clear(); };
   try {
@@ -38,11 +40,28 @@ int cc_conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, 
     ConvChoice ch;
     launch_conv_chosen(d->dtype, c, (hipStream_t)stream, &ch);
     CC_HIP(hipStreamSynchronize((hipStream_t)stream));
-    if (choice) { choice[0] = (int)ch.kernel; choice[1] = ch.sched; choice[2] = ch.bm; choice[3] = ch.bn; }
+    if (choice) {                                        // the order cc_dev_conv_det reports them in
+      const int got[8] = {(int)ch.kernel, ch.sched, ch.bm, ch.bn, ch.simple ? 1 : 0, ch.two ? 1 : 0, ch.cprw, ch.ns};
+      for (int i = 0; i < nchoice; ++i) choice[i] = got[i];
+    }
     release();
     return 0;
   } catch (const cc::Error& e) { release(); cc::set_error(e.what()); return e.code; }
   catch (const std::exception& e) { release(); cc::set_error(e.what()); return -1; }
+}
+
+}  // namespace
+
+extern "C" {
+
+int cc_conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
+                 const void* res_dev, void* out_dev, int* choice, void* stream) {
+  return conv2d_ex(d, x_dev, w_oihw, bias, slope, res_dev, out_dev, choice, 4, stream);
+}
+
+int cc_conv2d_ex_route(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
+                       const void* res_dev, void* out_dev, int* choice, void* stream) {
+  return conv2d_ex(d, x_dev, w_oihw, bias, slope, res_dev, out_dev, choice, 8, stream);
 }
 
 int cc_route_log_take(int* records, int cap, int* n) {

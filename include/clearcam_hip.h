@@ -151,7 +151,10 @@ int cc_conv2d_nhwc(int dtype, const void* x_dev, int B, int H, int W, int Cin, c
  * out: pixels of out_cstride channels (<= 0: Cout), the result in channels [out_coff, out_coff + Cout), float32 if out_f32 else the
  * storage type.  res (null: none): the same pixel grid, res_cstride (<= 0: Cout) / res_coff, float32 if res_f32; it may be `out` itself.
  * variant: as cc_conv2d_nhwc's force_direct.  choice (int[4] or null) receives the kernel that ran: ConvKernel, phase schedule, tile
- * pixels, tile channels (csrc/conv_select.h).  Synchronises the stream. */
+ * pixels, tile channels (csrc/conv_select.h).  Synchronises the stream.
+ * cc_conv2d_ex_route: the same launch, choice (int[8] or null) receiving those four and then what picks the K loop: simple, two, cprw
+ * (16-byte chunks per LDS row), ns (LDS stages) - the eight ints cc_dev_conv_det reports.  An entry of its own so that cc_conv2d_ex
+ * never writes past the four ints its callers hand it. */
 typedef struct {
   int dtype, B, H, W, Cin, Cout, k, stride, groups, act;
   int pad, Ho, Wo;
@@ -161,6 +164,8 @@ typedef struct {
 } cc_conv_desc;
 int cc_conv2d_ex(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
                  const void* res_dev, void* out_dev, int* choice, void* stream);
+int cc_conv2d_ex_route(const cc_conv_desc* d, const void* x_dev, const float* w_oihw, const float* bias, const float* slope,
+                       const void* res_dev, void* out_dev, int* choice, void* stream);
 /* Single-launch entries of the post-processing tests: ONE launch of a detector / face post-processing kernel through its production
  * launcher, on inputs the caller crafts.  Device pointers end in _dev; everything else is host memory.  Each validates its arguments
  * (an error, and no launch, on null pointers, B <= 0, an empty level, an unsupported dtype / ch, or a misaligned map), synchronises

@@ -1,14 +1,19 @@
 """Case table of tests/test_gpu_conv_epilogues.py and the route keys tests/test_gpu_plan_routes.py holds the production plans to
 (helper module; not a conftest).
 
-A case is ONE conv launch through cc_conv2d_ex.  It names the kernel it must reach - `expect` = (kernel, sched, bm, bn), the ConvChoice
+A case is ONE conv launch through cc_conv2d_ex_route (cc_conv2d_ex's launch; it reports the K loop too).  It names the kernel it must reach - `expect` = (kernel, sched, bm, bn), the ConvChoice
 fields the entry reports - and the test fails when the selector lands anywhere else.  A case's ROUTE KEY adds what decides the epilogue
 code that runs: (kernel, sched, bm, bn, ks, stride, asym, act, residual kind, out_f32, aligned8), the fields of a route-log record
 (clearcam_amd/csrc/conv_select.h) without the layer's shape.
 
-The key does not tell apart instantiations of the generic kernel that differ only in LDS stages (`ns`: variants 94 / 95, 96 / 97; the
-plans take six stages on 32 x 32 tiles for K >= 4096, four below), chunks per row (`cprw`) or loader (`simple`): the K loop differs, the
-epilogue (conv_tile.h conv_epilogue, instantiated on the tile and the wave layout) is the same code.  The few-tile cases run both stage counts.
+That key does not tell apart instantiations of the generic kernel that differ in LDS stages (`ns`: variants 94 / 95, 96 / 97; the plans
+take six stages on 32 x 32 tiles for K >= 4096, four below), chunks per row (`cprw`) or loader (`simple`).  The K loop differs - and the
+staged epilogues reuse the K ring's LDS (conv_tile.h), so whether stores overtake prefetches still in flight depends on `ns`.  The plans
+are therefore held to the EXTENDED key, the eleven fields plus (split, simple, two, cprw, ns) (tests/plan_route_cases.py): every extended
+key AdaFace, BlazeFace and CLIP L/14 log has a case here, and the deepest case of a key runs at least min(S_plan, 2 ns + 1) K steps,
+S_plan being the steps of the plans' deepest layer under that key (tests/plan_route_table.py).  The cases added for that (the _DEEP_*
+tables) name their full route in `ext` = (simple, two, cprw, ns); the older ones keep asserting (kernel, sched, bm, bn) and take the rest
+of their extended key from the selector (cc_dev_conv_det_choice answers without a device).
 """
 from __future__ import annotations
 
@@ -51,6 +56,7 @@ class Case:
     res_coff: int = 0
     phase_flags: Optional[int] = None   # cc_dev_set("phase_flags") around the launch
     dtypes: Tuple[str, ...] = ("f16", "bf16")
+    ext: Optional[Tuple[int, int, int, int]] = None   # (simple, two, cprw, ns) the launch must report too (the deep-K cases name their full route)
 
     @property
     def padv(self) -> int:
@@ -74,6 +80,11 @@ class Case:
         res = RES_NONE if self.res is None else (RES_STORAGE if self.res in ("storage", "inplace16") else RES_F32)
         al8 = int(self.Cout % 8 == 0 and self.out_coff % 8 == 0 and self.ocs % 8 == 0)
         return self.expect + (self.k, self.stride, int(ho > sh or wo > sw), self.act, res, int(self.out_f32), al8)
+
+    @property
+    def ktot(self) -> int:
+        """Elements of one packed weight row that hold weights: groups are densified (net_common.h pack_conv)."""
+        return self.k * self.k * self.Cin
 
     @property
     def ref_id(self):
@@ -224,15 +235,89 @@ def _detector_cases() -> List[Case]:
 
 CASES += _detector_cases()
 
+
+# ---- the plans' K loops at their own depth (tests/plan_route_cases.py, tests/plan_route_table.py) -------------------------------------------
+# The EXTENDED key adds (split, simple, two, cprw, ns) to the route key: LDS stages and chunks per row pick another instantiation of the
+# generic kernel, and the staged epilogues reuse the K ring's LDS, so (stages x epilogue) is what a launch can get wrong.  One case per
+# extended key the plans log that the tables above do not reach - or reach with a single K step where the plan's layer runs tens of them.
+# K is the only large dimension: the deepest case of a key runs at least min(S_plan, 2 ns + 1) K steps of 8 cprw elements.  These cases
+# name their full route (`ext`), and fail when the selector lands elsewhere.
+#   tile -> (variant, phase_flags, Cout, expect, cprw, ns);  91 / 93 / 95 / 96 / 97 force the few-tile configurations the selector picks
+#   by M, 2 with Cout 24 / 64 / 128 its plain 128-pixel tiles (64-byte rows where a row of K is at most 512 bytes)
+_DEEP_TILES = {
+    "g32_4": (97, None, 40, (GENERIC, 0, 32, 32), 8, 4), "g32_6": (96, None, 40, (GENERIC, 0, 32, 32), 8, 6),
+    "g64_4": (95, None, 40, (GENERIC, 0, 64, 32), 8, 4), "g128x32_4": (91, None, 40, (GENERIC, 0, 128, 32), 8, 4),
+    "g128x32_2": (2, None, 24, (GENERIC, 0, 128, 32), 8, 2), "g128x64_3": (93, None, 64, (GENERIC, 0, 128, 64), 8, 3),
+    "g128x64_row64": (2, None, 64, (GENERIC, 0, 128, 64), 4, 2), "g128x128": (2, None, 128, (GENERIC, 0, 128, 128), 8, 2),
+    "g128x128_row64": (2, None, 128, (GENERIC, 0, 128, 128), 4, 2), "big128": (6, None, 128, (BIG, 0, 128, 128), 8, 2),
+    "one_tile": (7, 32, 256, (PHASE, ONE_TILE, 256, 256), 8, 2), "persist": (7, 512, 256, (PHASE, PERSIST, 256, 256), 8, 2),
+}
+# loader -> (k, stride, pad, Cin, H, W, Ho, Wo): B = 2 on a 13 x 21 map, M = 546 (stride 2: 154; the asymmetric one: 162) is ragged
+# against every pixel tile; Cin 96 / 48 / 24 / 592 leave the last K step partly padding
+_DEEP_LOADERS = {
+    "1x1_k96": (1, 1, 0, 96, 13, 21, 0, 0), "1x1_k592": (1, 1, 0, 592, 13, 21, 0, 0), "1x1_k1024": (1, 1, 0, 1024, 13, 21, 0, 0),
+    "1x1_k4096": (1, 1, 0, 4096, 13, 21, 0, 0), "1x1s2_k256": (1, 2, 0, 256, 13, 21, 0, 0),
+    "3x3_c8": (3, 1, 1, 8, 13, 21, 0, 0), "3x3_c24": (3, 1, 1, 24, 13, 21, 0, 0), "3x3_c48": (3, 1, 1, 48, 13, 21, 0, 0),
+    "3x3_c256": (3, 1, 1, 256, 13, 21, 0, 0), "3x3_c512": (3, 1, 1, 512, 13, 21, 0, 0), "3x3s2_c256": (3, 2, 1, 256, 13, 21, 0, 0),
+    "3x3s2_asym_c96": (3, 2, 0, 96, 18, 18, 9, 9),
+}
+# (plan that logs the key, tile, loader, act, residual, f32 output)
+_DEEP_ROUTES = [
+    # 32 x 32, four stages: CLIP's text tower and B = 1 (K 768 .. 3072), BlazeFace's 96-channel blocks, AdaFace's shortcut convs
+    ("clip", "g32_4", "1x1_k1024", 0, None, False), ("clip", "g32_4", "1x1_k1024", 2, None, False), ("clip", "g32_4", "1x1_k1024", 0, "inplace", True),
+    ("blazeface", "g32_4", "1x1_k96", 4, None, False), ("blazeface", "g32_4", "1x1_k96", 4, "storage", False),
+    ("blazeface", "g32_4", "3x3s2_asym_c96", 0, None, False), ("adaface", "g32_4", "1x1s2_k256", 0, None, False),
+    # 32 x 32, six stages (K >= 4096): CLIP's mlp c_proj at B = 1, AdaFace's 512-channel layers at B = 1
+    ("clip", "g32_6", "1x1_k4096", 0, "inplace", True), ("adaface", "g32_6", "3x3_c512", 3, None, False),
+    ("adaface", "g32_6", "3x3_c512", 0, "storage", False), ("adaface", "g32_6", "3x3s2_c256", 0, "storage", False),
+    # 64 x 32, four stages
+    ("clip", "g64_4", "1x1_k1024", 0, None, False), ("adaface", "g64_4", "1x1s2_k256", 0, None, False),
+    # 128 x 32, four stages: the selector's own few-tile choice (variant 9 lands on six)
+    ("clip", "g128x32_4", "1x1_k1024", 0, None, False), ("clip", "g128x32_4", "1x1_k1024", 2, None, False),
+    ("blazeface", "g128x32_4", "1x1_k96", 4, "storage", False), ("blazeface", "g128x32_4", "3x3_c48", 0, None, False),
+    ("adaface", "g128x32_4", "1x1s2_k256", 0, None, False), ("adaface", "g128x32_4", "3x3_c256", 3, None, False),
+    ("adaface", "g128x32_4", "3x3_c256", 0, "storage", False), ("adaface", "g128x32_4", "3x3s2_c256", 0, "storage", False),
+    # 128 x 32, two stages: BlazeFace's 24-channel layers at B = 32 (too many tiles for the few-tile configurations)
+    ("blazeface", "g128x32_2", "1x1_k96", 4, "storage", False), ("blazeface", "g128x32_2", "3x3_c24", 0, None, False),
+    # 128 x 64, three stages
+    ("clip", "g128x64_3", "1x1_k4096", 0, "inplace", True), ("adaface", "g128x64_3", "1x1s2_k256", 0, None, False),
+    ("adaface", "g128x64_3", "3x3_c256", 3, None, False), ("adaface", "g128x64_3", "3x3_c256", 0, "storage", False),
+    ("adaface", "g128x64_3", "3x3s2_c256", 0, "storage", False),
+    # 64-byte rows: AdaFace's conv0 (Cin padded to 8, K = 72) and its widest shortcut conv (K = 256) at B = 256
+    ("adaface", "g128x64_row64", "3x3_c8", 3, None, False), ("adaface", "g128x128_row64", "1x1s2_k256", 0, None, False),
+    # 128 x 128, two stages: CLIP's patch GEMM at B = 64 (K = 592 keeps it off the single-barrier kernel)
+    ("clip", "g128x128", "1x1_k592", 0, None, False),
+    # the wide kernels' plain GEMM at CLIP's K, AdaFace's shortcut conv on the eight-wave kernel
+    ("clip", "big128", "1x1_k1024", 0, None, False), ("clip", "persist", "1x1_k1024", 0, None, False),
+    ("adaface", "one_tile", "1x1s2_k256", 0, None, False),
+]
+
+
+def _deep_cases() -> List[Case]:
+    out = []
+    for plan, tile, loader, act, res, o32 in _DEEP_ROUTES:
+        v, pf, cout, exp, cprw, ns = _DEEP_TILES[tile]
+        k, stride, pad, cin, H, W, Ho, Wo = _DEEP_LOADERS[loader]
+        tag = f"act{act}" + ("" if res is None else "_res16" if res == "storage" else "_res32_inplace")
+        out.append(Case(f"{plan}-deep-{tile}-{loader}-{tag}", 2, cin, H, W, cout, k, exp, stride=stride, act=act, variant=v, pad=pad, Ho=Ho, Wo=Wo,
+                        res=res, out_f32=o32, phase_flags=pf, ext=(1, 0, cprw, ns)))
+    # CLIP's final projection, M = B: ONE valid row in the pixel tile at B = 1, 24 channel tiles, f32 output without a residual
+    out.append(Case("clip-deep-g32_4-projection_m1_k1024_n768-out32", 1, 1024, 1, 1, 768, 1, (GENERIC, 0, 32, 32), variant=97, pad=0, out_f32=True,
+                    ext=(1, 0, 8, 4)))
+    return out
+
+
+CASES += _deep_cases()
+
 assert len({c.name for c in CASES}) == len(CASES)
 
-# Route keys a production plan may log that no case above reaches with the same key, and the covered key whose code they run.  One line
-# each: the reason the SAME kernel instantiation and epilogue code runs.
+# What the production plans log is held to the EXTENDED key: plan_route_cases.covered_cases / MERGED (tests/test_gpu_plan_routes.py).
+# The eleven-field view below stays for whoever reads a case table by epilogue alone; nothing may be merged on it any more.
 MERGED: Dict[Tuple[int, ...], Tuple[Tuple[int, ...], str]] = {}
 
 
 def covered_keys() -> Dict[Tuple[int, ...], str]:
-    """route key -> the name of a 16-bit case that reaches it (the production plans under test are 16-bit)."""
+    """eleven-field route key -> the name of a 16-bit case that reaches it."""
     out: Dict[Tuple[int, ...], str] = {}
     for c in CASES:
         if "f16" in c.dtypes:

@@ -1,4 +1,4 @@
-"""Every conv epilogue the CLIP, AdaFace and BlazeFace plans reach, ONE launch per case through cc_conv2d_ex, against float64.
+"""Every conv epilogue the CLIP, AdaFace and BlazeFace plans reach, ONE launch per case through cc_conv2d_ex_route, against float64.
 
 The per-kernel tests of tests/test_gpu_yolo.py run "bias + SiLU or nothing, dense 16-bit output" only; the other plans share the
 selector and the kernels but use tanh-GELU, PReLU with per-channel slopes, ReLU after a 16-bit residual, an f32 residual that is the f32
@@ -46,6 +46,10 @@ U24 = 2.0 ** -24
 # on every case (each element is one of the two storage values around y64; max 0.509 ulp).  D = 3 x 0.0094.  R and R_cell stay.
 # The detector's epilogues added later (SiLU on every family, SiLU + a 16-bit residual that is the output buffer; 64 tests): R 0.118 %,
 # R_cell 1.04 %, D 0.0051 ulp (big_3x3_odd-tile128-silu_inplace16, f16) - under the figures above.
+# The plans' K loops at their own depth added later (epilogue_cases._DEEP_ROUTES, K up to 4608 where 1728 was the deepest measured; 62
+# 16-bit tests; docs/measurement.md, "Plan conv routes at their own K depth"): bar 1 holds on every case (max 0.520 ulp), R 0.276 %
+# (adaface-deep-g32_6-3x3s2_c256-act0_res16, f16), R_cell 0.49 %, D 0.0194 ulp (adaface-deep-g128x64_3-3x3_c256-act0_res16, bf16; f16
+# worst 0.0106) - under the bars, which stay.  f32 outputs there: err / bound at most 0.0008 (K = 1024 with the in-place residual).
 # f32 outputs: the largest err / bound was 0.0163 (the persistent kernel's M = 33 300, K = 64 GEMM with the in-place residual).
 BARS = dict(R=rc.BARS["R"], R_cell=rc.BARS["R_cell"], D=2.8e-2)
 
@@ -75,7 +79,7 @@ def _problem(ref_id, dtype, res_kind):
 
 
 def run_case(c: ec.Case, dtype: str):
-    """Launch the case; returns (rc, choice, NCHW result as float64, channels outside the output slice as a tensor or None)."""
+    """Launch the case; returns (rc, the eight ints of choice, NCHW result as float64, channels outside the output slice as a tensor or None)."""
     L = _lib.lib()
     t = TDT[dtype]
     Ho, Wo = c.out_hw
@@ -100,12 +104,13 @@ def run_case(c: ec.Case, dtype: str):
                       int(c.out_f32), c.out_cstride, c.out_coff, int(c.res in ("f32", "inplace")), c.res_cstride, c.res_coff, c.variant)
     wn, bn = np.ascontiguousarray(w.numpy()), np.ascontiguousarray(b.numpy())
     sn = None if slope is None else np.ascontiguousarray(slope.numpy())
-    choice = (C.c_int * 4)(-1, -1, -1, -1)
+    choice = (C.c_int * _lib.CONV_CHOICE_INTS)(*([-1] * _lib.CONV_CHOICE_INTS))      # kernel, sched, bm, bn, simple, two, cprw, ns
     torch.cuda.synchronize()
     try:
         if c.phase_flags is not None:
             _lib.check(L.cc_dev_set(b"phase_flags", c.phase_flags))
-        code = L.cc_conv2d_ex(C.byref(d), _lib.ptr(xd), _lib.ptr(wn), _lib.ptr(bn), _lib.ptr(sn), _lib.ptr(resd), _lib.ptr(out), choice, None)
+        # cc_conv2d_ex_route: cc_conv2d_ex's launch, reporting the K loop too (cc_conv2d_ex itself keeps its four-int choice)
+        code = L.cc_conv2d_ex_route(C.byref(d), _lib.ptr(xd), _lib.ptr(wn), _lib.ptr(bn), _lib.ptr(sn), _lib.ptr(resd), _lib.ptr(out), choice, None)
     finally:
         if c.phase_flags is not None:
             _lib.check(L.cc_dev_set(b"phase_flags", -1))
@@ -128,7 +133,9 @@ def test_conv_epilogue_matches_float64(case, dtype):
     c = case
     code, choice, got, outside, y64, mag = run_case(c, dtype)
     assert code == 0, (c.name, _lib.lib().cc_last_error().decode(errors="replace"))
-    assert choice == c.expect, (c.name, "the selector ran", choice, "not the kernel this case is about", c.expect)
+    assert choice[:4] == c.expect, (c.name, "the selector ran", choice, "not the kernel this case is about", c.expect)
+    if c.ext is not None:                              # the deep-K cases name their K loop too: simple, two, cprw, ns
+        assert choice == c.expect + c.ext, (c.name, "the selector ran", choice, "not the route this case is about", c.expect + c.ext)
     if outside is not None:
         assert bool(torch.isnan(outside).all()), (c.name, "channels outside the output slice were written")
     if c.out_f32 or dtype == "f32":

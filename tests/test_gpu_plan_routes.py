@@ -1,9 +1,13 @@
-"""The single-launch cases of tests/epilogue_cases.py cover what the production plans reach.
+"""The single-launch cases of tests/epilogue_cases.py cover what the production plans reach - K loop included, at the plans' own depth.
 
-With the route log on (cc_dev_set("route_log", 1)) every conv / GEMM launch records the kernel the selector chose and what decides its
-epilogue.  AdaFace, BlazeFace and CLIP L/14 are built and run once per batch size in f16 and bf16; every route key they log must be
-one a case of tests/test_gpu_conv_epilogues.py reaches (or be merged into one, with the reason, in epilogue_cases.MERGED).  The
-selector picks by M = B Ho Wo, so the log at B = 1 must differ from the log at the largest batch - otherwise the log does not see it.
+With the route log on (cc_dev_set("route_log", 1)) every conv / GEMM launch records the kernel the selector chose, what decides its
+epilogue and what picks its K loop.  AdaFace, BlazeFace and CLIP L/14 are built and run once per batch size in f16 and bf16.  Every
+EXTENDED route key they log - the eleven fields of epilogue_cases plus split, simple, two, cprw, ns (tests/plan_route_cases.py) - must be
+one a single-launch case reaches, or be merged into one, with the reason, in plan_route_cases.MERGED (a merge never crosses the kernel,
+the tile, the planes, the residual kind, f32 output, `ns` or `act`).  The deepest case of a key must run at least min(S_plan, 2 ns + 1) K
+steps, S_plan computed from the log.  The table of what the plans log is committed (tests/plan_route_table.py) so that
+tests/test_plan_route_cases_host.py can hold the cases to it without a device; here it must equal the log.
+The selector picks by M = B Ho Wo, so the log at B = 1 must differ from the log at the largest batch - otherwise the log does not see it.
 """
 import ctypes as C
 
@@ -11,17 +15,18 @@ import numpy as np
 import pytest
 
 import epilogue_cases as ec
+import plan_route_cases as prc
 from clearcam_amd import _lib
 from clearcam_amd.arch import CLIP_L14
 from clearcam_amd.weights import synthetic_adaface_state_dict, synthetic_blazeface_state_dict, synthetic_clip_state_dict
 
 pytestmark = pytest.mark.gpu
 NREC = _lib.ROUTE_REC_INTS
-NKEY = len(ec.KEY_FIELDS)
+NHEAD = len(ec.KEY_FIELDS)                              # a record: the eleven fields, the layer's seven-int shape, then split, simple, two, cprw, ns
 
 
 def take_log():
-    """Read and clear the route log: {route key: (B, H, W, Cin, Cout, Ho, Wo) of the first layer that logged it}."""
+    """Read and clear the route log: {extended route key: the set of (B, H, W, Cin, Cout, Ho, Wo) of the layers that logged it}."""
     cap = 1 << 12
     buf = (C.c_int * (cap * NREC))()
     out = {}
@@ -30,7 +35,8 @@ def take_log():
         _lib.check(_lib.lib().cc_route_log_take(buf, cap, C.byref(n)))
         got = min(n.value, cap)
         for r in np.frombuffer(buf, np.int32, got * NREC).reshape(got, NREC):
-            out.setdefault(tuple(int(v) for v in r[:NKEY]), tuple(int(v) for v in r[NKEY:]))
+            key = tuple(int(v) for v in r[:NHEAD]) + tuple(int(v) for v in r[NHEAD + 7:])
+            out.setdefault(key, set()).add(tuple(int(v) for v in r[NHEAD:NHEAD + 7]))
         if n.value <= cap:
             return out
 
@@ -90,6 +96,7 @@ def _clip_text(weights, clip_handles, dtype):
 
 PLANS = [("adaface", _adaface, (1, 3, 12, 40, 256)), ("blazeface", _blazeface, (1, 32)),
          ("clip_image", _clip_image, (1, 8, 64)), ("clip_text", _clip_text, (1, 8))]
+assert tuple(p[0] for p in PLANS) == prc.PLANS
 
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
@@ -97,9 +104,9 @@ PLANS = [("adaface", _adaface, (1, 3, 12, 40, 256)), ("blazeface", _blazeface, (
 def test_every_route_of_the_plan_has_a_single_launch_case(plan, dtype, weights, clip_handles):
     name, make, batches = plan
     L = _lib.lib()
-    covered = ec.covered_keys()
-    for k, (to, why) in ec.MERGED.items():
-        assert to in covered and why.strip(), ("a merged key needs a covered key and a reason", k)
+    covered = prc.covered_cases()
+    for k, (to, why) in prc.MERGED.items():
+        assert k not in covered and to in covered and why.strip() and prc.merge_is_legal(k, to), ("a merged key needs a covered key it may merge into and a reason", k)
     logs = {}
     run, close = make(weights, clip_handles, dtype)
     try:
@@ -115,12 +122,13 @@ def test_every_route_of_the_plan_has_a_single_launch_case(plan, dtype, weights, 
         take_log()
         close()
     assert all(logs[B] for B in batches), (name, "no conv launch was logged", {B: len(v) for B, v in logs.items()})
-    missing = {}
-    for B in batches:
-        for key, shape in logs[B].items():
-            if key not in covered and key not in ec.MERGED:
-                missing.setdefault(key, (B,) + shape)
-    lines = [f"  {ec.describe(k)}   first at batch {v[0]}: B,H,W,Cin,Cout,Ho,Wo = {v[1:]}" for k, v in sorted(missing.items())]
-    print(f"{name} {dtype}: " + ", ".join(f"B={B}: {len(logs[B])} keys" for B in batches))
-    assert not missing, f"{name} {dtype}: {len(missing)} route keys no case of tests/epilogue_cases.py reaches:\n" + "\n".join(lines)
+    table = prc.table_of(logs)                            # extended key -> (deepest Ktot, batch, shape): S_plan comes from it
+    direct, merged, missing, shallow = prc.audit(table, covered)
+    print(f"{name} {dtype}: " + ", ".join(f"B={B}: {len(logs[B])} keys" for B in batches)
+          + f"; {len(table)} extended keys: {len(direct)} covered directly, {len(merged)} merged, {len(missing)} missing, {len(shallow)} too shallow")
+    lines = [f"  {prc.describe(k)}   deepest at batch {table[k][1]}: K = {table[k][0]}, B,H,W,Cin,Cout,Ho,Wo = {table[k][2]}" for k in missing]
+    assert not missing, f"{name} {dtype}: {len(missing)} extended route keys no single-launch case reaches:\n" + "\n".join(lines)
+    lines = [f"  {prc.describe(k)}   the plan runs K = {table[k][0]}: {need} K steps asked, the deepest case ({who}) runs {have}" for k, need, have, who in shallow]
+    assert not shallow, f"{name} {dtype}: {len(shallow)} extended route keys whose deepest case is too shallow:\n" + "\n".join(lines)
+    assert table == prc.TABLE[name], (f"{name} {dtype}: tests/plan_route_table.py is not what the plan logs; this is:\n" + prc.format_table({name: table}))
     assert set(logs[batches[0]]) != set(logs[batches[-1]]), (name, "the log is the same at B = 1 and at the largest batch: it does not see the selector")
