@@ -28,7 +28,7 @@ SYMBOLS = [
     "cc_index_create", "cc_index_create_ex", "cc_index_add", "cc_index_add_grouped", "cc_index_size", "cc_index_info", "cc_index_scores", "cc_index_last_path",
     "cc_index_search", "cc_index_search_groups", "cc_index_add_tracked", "cc_index_search_tracks", "cc_index_rank",
     "cc_index_add_described", "cc_index_row_info", "cc_index_rank_where", "cc_index_timeline", "cc_index_fetch_rows", "cc_index_rank_like",
-    "cc_index_rank_terms", "cc_index_timeline_terms",
+    "cc_index_rank_terms", "cc_index_timeline_terms", "cc_index_rank_near", "cc_index_timeline_near",
     "cc_index_gram", "cc_index_distinct", "cc_index_digest", "cc_index_sightings",
     "cc_index_remove_rows", "cc_index_remove_groups", "cc_index_destroy",
     "cc_watch_create", "cc_watch_set", "cc_watch_size", "cc_watch_scores", "cc_watch_match", "cc_watch_destroy",
@@ -71,6 +71,8 @@ LIKE_EXCLUDE_ROWS, LIKE_EXCLUDE_TRACK = 2, 4          # CC_LIKE_EXCLUDE_ROWS / C
 TERMS_MAX = 64                                        # CC_TERMS_MAX: the most terms of one cc_index_rank_terms
 TERM_RANK, TERM_REQUIRE, TERM_REJECT = 0, 1, 2        # CC_TERM_RANK / CC_TERM_REQUIRE / CC_TERM_REJECT
 COMBINE_MAX, COMBINE_MIN, COMBINE_SUM = 0, 1, 2       # CC_COMBINE_MAX / CC_COMBINE_MIN / CC_COMBINE_SUM
+NEAR_MAX_PARTNERS, NEAR_DEFAULT_PARTNERS = 16384, 4096   # CC_NEAR_MAX_PARTNERS / CC_NEAR_DEFAULT_PARTNERS
+NEAR_VALUE = {"a": 0, "min": 1}                       # CC_NEAR_VALUE_A / CC_NEAR_VALUE_MIN
 DISTINCT_MAX_DEPTH, DISTINCT_MAX_Q = 1024, 64        # CC_DISTINCT_MAX_DEPTH / CC_DISTINCT_MAX_Q
 DIGEST_MAX_LEADERS = 1024                             # CC_DIGEST_MAX_LEADERS
 DIGEST_BY_COUNT, DIGEST_BY_FIRST = 0, 1               # CC_DIGEST_BY_COUNT / CC_DIGEST_BY_FIRST
@@ -213,6 +215,10 @@ def lib() -> C.CDLL:
                                 C.POINTER(RowFilter), vp, vp, vp, vp, C.c_int, vp],
         "cc_index_timeline_terms": [vp, vp, C.c_int, i64p, C.c_int, C.POINTER(Term), C.c_int, C.c_float, C.c_int, vp, C.c_int, C.POINTER(RowFilter),
                                     C.c_int32, C.c_int32, C.c_int, vp, vp, C.c_int, vp],
+        "cc_index_rank_near": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_int, vp, C.c_int,
+                               C.POINTER(RowFilter), C.POINTER(RowFilter), vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "cc_index_timeline_near": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, vp, C.c_int,
+                                   C.POINTER(RowFilter), C.POINTER(RowFilter), C.c_int32, C.c_int32, C.c_int, vp, vp, vp, C.c_int, vp],
         "cc_index_gram": [vp, i64p, C.c_int, vp, C.c_int, vp],
         "cc_index_distinct": [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "cc_index_digest": [vp, C.c_float, C.c_int, C.c_int, vp, C.c_int, C.POINTER(RowFilter), C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],

@@ -28,6 +28,10 @@
 // scored in one batch, terms_fold_kernel folds them by role (RANK through max / min / a weighted sum, REQUIRE and REJECT into the dead
 // bytes) into one vector, and the same ranking of ONE query follows ("Compound search").
 //
+// cc_index_rank_near / cc_index_timeline_near rank the rows of one question that have an answer of a second question nearby in time:
+// both are scored in one batch, the selection below leaves B's first answers on the device as the partner list, near_fold_kernel
+// (index_near.hip) joins every row against it, and the same ranking of ONE query follows ("Together").
+//
 // cc_index_gram / cc_index_distinct, cc_index_digest and cc_index_sightings have their entry points here and their kernels in
 // index_distinct.hip, index_digest.hip and index_sightings.hip.
 #include <algorithm>
@@ -79,6 +83,10 @@ struct cc_index {
   // compound search (cc_index_rank_terms): touched by no other call
   unsigned char* which_row = nullptr; size_t which_row_cap = 0;   // (n) one byte per row: the RANK term that made the row's value, written by terms_fold_kernel
   int* which_dev = nullptr; size_t which_dev_cap = 0;             // (count) a host caller's `which` on the device, when the result is too large for the pinned block
+  // together (cc_index_rank_near / cc_index_timeline_near, kernels in index_near.hip): touched by no other call
+  char* near_ws = nullptr; size_t near_ws_cap = 0;             // the partner list (near_list), then the selects, bin tables and window counters of its selection, then its total
+  int* near_pos = nullptr; size_t near_pos_cap = 0;            // (n) the place of each row's partner in the list, -1 = none, written by near_fold_kernel
+  int* near_dev = nullptr; size_t near_dev_cap = 0;            // (2, count) a host caller's partner / partner_score on the device, when the result is too large for the pinned block
   // distinct ranking (cc_index_gram / cc_index_distinct, kernels in index_distinct.hip)
   char* dist_ws = nullptr; size_t dist_ws_cap = 0;             // per list: squeezed rows, their places, the bit matrix, the counts (distinct_ws)
   char* dist_io = nullptr; size_t dist_io_cap = 0;             // a host caller's lists and answers, or its Gram matrix, on the device
@@ -1777,19 +1785,119 @@ void terms_scores(cc_index* h, const TermsQuery& tq, RowWhere& w, int on_device,
   CC_HIP(hipGetLastError());
 }
 
-// Where the ONE score vector of a ranking comes from when it is not a caller's query: the fold of a cc_index_rank_like or that of a
-// cc_index_rank_terms / cc_index_timeline_terms.  Exactly one of the two is set.
-struct FoldQuery { const LikeQuery* like; const TermsQuery* terms; };
+// The selection of rank() over the keys in h->key_hi (Q, n): per batch of up to 16 windows of kMaxK answers init, eight times (histogram,
+// pick), collect, emit into idx_out / sc_out (Q, count).  sel / ghist / wcnt: the selects, bin tables and window counters of one batch
+// (kRankSel per query).  avail: the answers from `start` on that are not padding whatever the scores are.
+void rank_select(cc_index* h, int Q, bool tracks, int64_t start, int64_t avail, int64_t count, RankSel* sel, unsigned* ghist, unsigned* wcnt,
+                 int* idx_out, float* sc_out, hipStream_t s) {
+  const long n = (long)h->n;
+  const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
+  const int T = std::max(h->n_slots, 1);
+  const int* trk = tracks ? h->trk : nullptr;
+  const int64_t nwin = (avail + kMaxK - 1) / kMaxK;
+  if (nwin) ensure((void**)&h->cand, &h->cand_cap, (size_t)Q * kRankSel * kMaxK * 8);
+  for (int64_t w0 = 0; w0 < nwin; w0 += kRankSel - 1) {
+    const int nw = (int)std::min<int64_t>(kRankSel - 1, nwin - w0), S = nw + 1;
+    const long r0 = (long)(start + w0 * kMaxK), r_last = (long)(start + std::min<int64_t>(avail, (w0 + nw) * kMaxK));
+    hipLaunchKernelGGL(rank_init_kernel, dim3(Q), dim3(256), 0, s, r0, r_last, sel, ghist, wcnt);
+    for (int byte = 7; byte >= 0; --byte) {
+      hipLaunchKernelGGL(rank_hist_kernel, dim3(nblk, S, Q), dim3(256), 0, s, h->key_hi, n, trk, byte, sel, ghist);
+      hipLaunchKernelGGL(rank_pick_kernel, dim3(S, Q), dim3(64), 0, s, byte, sel, ghist);
+    }
+    hipLaunchKernelGGL(rank_collect_kernel, dim3(nblk, Q), dim3(256), 0, s, h->key_hi, n, trk, S, r0 == 0 ? 1 : 0, sel, wcnt, h->cand);
+    if (tracks) hipLaunchKernelGGL(rank_emit_kernel<true>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, h->trk, h->best, T);
+    else hipLaunchKernelGGL(rank_emit_kernel<false>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, nullptr, nullptr, 0);
+  }
+}
 
-void fold_scores(cc_index* h, const FoldQuery& f, RowWhere& w, int on_device, hipStream_t s) {
+// The query side of cc_index_rank_near / cc_index_timeline_near, checked: the two sides (a vector, or a stored row beside a null vector),
+// the join, B's filter as the kernels take it (rows with a ts only), and where the caller wants the partners and the list's full length.
+struct NearQuery { const float* qa; int64_t row_a; const float* qb; int64_t row_b; int within, cap, value; float cut_b; RowWhere wb;
+                   int32_t* partner; float* partner_score; int64_t* n_partners; };
+
+int near_check(cc_index* h, const float* qa, int64_t row_a, const float* qb, int64_t row_b, int32_t within, int max_partners, float cut_b, int value, int flags,
+               const cc_row_filter* where_b, int32_t* partner, float* partner_score, int64_t* n_partners, NearQuery* nq) {
+  CC_API_BEGIN
+  CC_CHECK(h, "null argument");
+  CC_CHECK((qa != nullptr) != (row_a >= 0) && (qb != nullptr) != (row_b >= 0), "each side needs exactly one of a vector and a stored row");
+  CC_CHECK((qa || row_a < h->n) && (qb || row_b < h->n), "a row number outside the index");
+  CC_CHECK(within >= 0, "within must not be negative");
+  CC_CHECK(max_partners >= 1 && max_partners <= CC_NEAR_MAX_PARTNERS, "max_partners must be in [1, CC_NEAR_MAX_PARTNERS]");
+  CC_CHECK(cut_b == cut_b, "cut_b is NaN");
+  CC_CHECK(value == CC_NEAR_VALUE_A || value == CC_NEAR_VALUE_MIN, "unknown value rule");
+  CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
+  *nq = NearQuery{qa, row_a, qb, row_b, within, max_partners, value, cut_b, make_where(h, where_b), partner, partner_score, n_partners};
+  if (!nq->wb.ts) { nq->wb.ts = h->ts; nq->wb.ts_min = INT32_MIN; nq->wb.ts_max = INT32_MAX; }   // no window: still only rows that have a ts
+  CC_API_END
+}
+
+// The scratch of a together call that is its own (h->near_ws): the list, the state of its selection, its total.
+struct NearWs { NearList L; RankSel* sel; unsigned* ghist; unsigned* wcnt; unsigned* total; };
+
+NearWs near_ws(cc_index* h) {
+  const size_t list_bytes = near_list_bytes(), sel_bytes = (kRankSel * sizeof(RankSel) + 255) & ~(size_t)255, hist_bytes = (size_t)kRankSel * 256 * 4,
+               cnt_bytes = (size_t)kRankSel * 4;
+  ensure((void**)&h->near_ws, &h->near_ws_cap, list_bytes + sel_bytes + hist_bytes + cnt_bytes + 4);
+  NearWs ws;
+  ws.L = near_list(h->near_ws);
+  ws.sel = reinterpret_cast<RankSel*>(h->near_ws + list_bytes);
+  ws.ghist = reinterpret_cast<unsigned*>(h->near_ws + list_bytes + sel_bytes);
+  ws.wcnt = reinterpret_cast<unsigned*>(h->near_ws + list_bytes + sel_bytes + hist_bytes);
+  ws.total = reinterpret_cast<unsigned*>(h->near_ws + list_bytes + sel_bytes + hist_bytes + cnt_bytes);
+  return ws;
+}
+
+// What cc_index_rank_near runs where cc_index_rank_where uploads and scores its queries: both sides where queries stand, ONE scoring
+// call, the ungrouped selection of cc_index_rank_where on B's score row (cut_b, B's filter, rows with a ts) into the list, the pack and
+// the fold.  Leaves v in row 0 of h->scores, w.dead set, h->near_pos written and the list's full length in ws.total (cleared by the
+// caller).  w comes in as A's filter without dead bytes; min_score / tracks: what the ranking behind will cut and reduce by.  n > 0.
+void near_scores(cc_index* h, const NearQuery& nq, RowWhere& w, bool tracks, float min_score, const unsigned char* allowed_dev, int on_device, hipStream_t s) {
+  const long n = (long)h->n;
+  const NearWs ws = near_ws(h);
+  ensure_queries(h, 2);
+  const float* vec[2] = {nq.qa, nq.qb};
+  const int64_t row[2] = {nq.row_a, nq.row_b};
+  const size_t qb = (size_t)h->dim * 4;
+  for (int i = 0; i < 2; ++i) {
+    float* dst = h->q_dev + (size_t)i * h->dim;
+    if (!vec[i]) gather_rows(h, &row[i], 1, dst, s);              // one number: it travels in the kernel arguments
+    else if (on_device) CC_HIP(hipMemcpyAsync(dst, vec[i], qb, hipMemcpyDeviceToDevice, s));
+    else {                                                        // through the pinned block, as upload_queries does
+      memcpy(h->pin + i * qb, vec[i], qb);
+      CC_HIP(hipMemcpyAsync(dst, h->pin + i * qb, qb, hipMemcpyHostToDevice, s));
+    }
+  }
+  compute_scores(h, 2, s);
+  ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)n * 4);
+  hipLaunchKernelGGL(rank_keys_kernel<false>, dim3((unsigned)((n + kRankRows - 1) / kRankRows), 1), dim3(256), 0, s, h->scores + n, n, h->grp, allowed_dev,
+                     h->allowed_cap, nullptr, nullptr, nullptr, 0, nq.cut_b, nq.wb, h->key_hi, ws.total);
+  const int64_t avail = std::min<int64_t>(nq.cap, n);
+  if (avail < nq.cap) hipLaunchKernelGGL(rank_pad_kernel, dim3((unsigned)((nq.cap + 255) / 256)), dim3(256), 0, s, ws.L.row, ws.L.score, (size_t)nq.cap);
+  rank_select(h, 1, false, 0, avail, nq.cap, ws.sel, ws.ghist, ws.wcnt, ws.L.row, ws.L.score, s);
+  CC_HIP(hipGetLastError());
+  launch_near_pack(ws.L, nq.cap, n, h->grp, h->ts, h->trk, s);
+  ensure((void**)&h->dead, &h->dead_cap, (size_t)n);
+  ensure((void**)&h->near_pos, &h->near_pos_cap, (size_t)n * 4);
+  launch_near_fold(h->scores, n, h->grp, h->trk, h->ts, allowed_dev, h->allowed_cap, w, min_score, tracks ? 0 : 1, ws.L, ws.total, nq.cap, nq.within, nq.value,
+                   h->dead, h->near_pos, s);
+  w.dead = h->dead;
+}
+
+// Where the ONE score vector of a ranking comes from when it is not a caller's query: the fold of a cc_index_rank_like, that of a
+// cc_index_rank_terms / cc_index_timeline_terms or the join of a cc_index_rank_near / cc_index_timeline_near.  Exactly one of the three is set.
+struct FoldQuery { const LikeQuery* like; const TermsQuery* terms; const NearQuery* near; };
+
+void fold_scores(cc_index* h, const FoldQuery& f, RowWhere& w, bool tracks, float min_score, const unsigned char* allowed_dev, int on_device, hipStream_t s) {
   if (f.like) like_scores(h, *f.like, w, s);
-  else terms_scores(h, *f.terms, w, on_device, s);
+  else if (f.terms) terms_scores(h, *f.terms, w, on_device, s);
+  else near_scores(h, *f.near, w, tracks, min_score, allowed_dev, on_device, s);
 }
 
 // cc_index_rank / cc_index_rank_where.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
 // init, eight times (histogram, pick), collect, emit.  Answers past the last row the index could give are padded by one fill.
 // fold (cc_index_rank_like, cc_index_rank_terms; Q is 1 and q unused): the score vector comes from fold_scores instead, everything behind
-// it is the same; a cc_index_rank_terms that asks for `which` adds one gather of `count` entries behind the last emit.
+// it is the same; a cc_index_rank_terms that asks for `which` adds one gather of `count` entries behind the last emit, and so does a
+// cc_index_rank_near for its partners.
 int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
          const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream, const FoldQuery* fold = nullptr) {
   CC_API_BEGIN
@@ -1807,18 +1915,25 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const long n = (long)h->n;
   const size_t ob = (size_t)Q * (size_t)count;
-  const int nq = fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
+  const NearQuery* near = fold ? fold->near : nullptr;
+  const int nq = near ? 2 : fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
   int32_t* which = fold && fold->terms ? fold->terms->which : nullptr;
   const size_t qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255;
   const bool zero_copy = !on_device && ob * 8 <= kPinResultBytes;            // small host results: written into pinned memory, as search() does
-  const size_t res_bytes = zero_copy ? (ob * (which ? 12 : 8) + 255) & ~(size_t)255 : 0;   // idx, score and, asked for, `which` in a slot of its own
-  ensure_pinned(h, qbytes + res_bytes + (size_t)Q * 4);
+  // idx, score and, asked for, `which` in a slot of its own; a together call: partner and partner_score in two slots behind score
+  const size_t res_bytes = zero_copy ? (ob * (near ? 16 : which ? 12 : 8) + 255) & ~(size_t)255 : 0;
+  ensure_pinned(h, qbytes + res_bytes + (size_t)(Q + (near ? 1 : 0)) * 4);   // the totals, and behind them the full length of a together call's list
   unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes + res_bytes);
   int* idx_out = idx; float* sc_out = score;
   int* which_out = which;
-  if (zero_copy) { idx_out = reinterpret_cast<int*>(h->pin + qbytes); sc_out = reinterpret_cast<float*>(h->pin + qbytes + ob * 4); which_out = reinterpret_cast<int*>(h->pin + qbytes + ob * 8); }
-  else if (!on_device) {
+  int* partner_out = near ? near->partner : nullptr; float* pscore_out = near ? near->partner_score : nullptr;
+  const bool want_partner = partner_out || pscore_out;
+  if (zero_copy) {
+    idx_out = reinterpret_cast<int*>(h->pin + qbytes); sc_out = reinterpret_cast<float*>(h->pin + qbytes + ob * 4); which_out = reinterpret_cast<int*>(h->pin + qbytes + ob * 8);
+    if (want_partner) { partner_out = reinterpret_cast<int*>(h->pin + qbytes + ob * 8); pscore_out = reinterpret_cast<float*>(h->pin + qbytes + ob * 12); }
+  } else if (!on_device) {
     if (which) { ensure((void**)&h->which_dev, &h->which_dev_cap, ob * 4); which_out = h->which_dev; }
+    if (want_partner) { ensure((void**)&h->near_dev, &h->near_dev_cap, ob * 8); partner_out = h->near_dev; pscore_out = reinterpret_cast<float*>(h->near_dev + ob); }
     if (h->out_cap < ob) {
       if (h->idx_dev) hipFree(h->idx_dev);
       if (h->sc_dev) hipFree(h->sc_dev);
@@ -1838,44 +1953,41 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   const int64_t avail = std::max<int64_t>(0, std::min<int64_t>(count, (int64_t)n - start));
   if (avail < count)
     hipLaunchKernelGGL(rank_pad_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, sc_out, ob);
+  NearWs nws{};
+  if (near) { nws = near_ws(h); CC_HIP(hipMemsetAsync(nws.total, 0, 4, s)); }
   if (n > 0) {
     const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    if (fold) fold_scores(h, *fold, w, on_device, s);
+    if (fold) fold_scores(h, *fold, w, tracks, min_score, allowed_dev, on_device, s);
     else {
       upload_queries(h, q, Q, on_device, s);
       compute_scores(h, Q, s);
     }
     rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
-    const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
-    const int T = std::max(h->n_slots, 1);
-    const int* trk = tracks ? h->trk : nullptr;
-    const int64_t nwin = (avail + kMaxK - 1) / kMaxK;
-    if (nwin) ensure((void**)&h->cand, &h->cand_cap, (size_t)Q * kRankSel * kMaxK * 8);
-    for (int64_t w0 = 0; w0 < nwin; w0 += kRankSel - 1) {
-      const int nw = (int)std::min<int64_t>(kRankSel - 1, nwin - w0), S = nw + 1;
-      const long r0 = (long)(start + w0 * kMaxK), r_last = (long)(start + std::min<int64_t>(avail, (w0 + nw) * kMaxK));
-      hipLaunchKernelGGL(rank_init_kernel, dim3(Q), dim3(256), 0, s, r0, r_last, sel, ghist, wcnt);
-      for (int byte = 7; byte >= 0; --byte) {
-        hipLaunchKernelGGL(rank_hist_kernel, dim3(nblk, S, Q), dim3(256), 0, s, h->key_hi, n, trk, byte, sel, ghist);
-        hipLaunchKernelGGL(rank_pick_kernel, dim3(S, Q), dim3(64), 0, s, byte, sel, ghist);
-      }
-      hipLaunchKernelGGL(rank_collect_kernel, dim3(nblk, Q), dim3(256), 0, s, h->key_hi, n, trk, S, r0 == 0 ? 1 : 0, sel, wcnt, h->cand);
-      if (tracks) hipLaunchKernelGGL(rank_emit_kernel<true>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, h->trk, h->best, T);
-      else hipLaunchKernelGGL(rank_emit_kernel<false>, dim3(nw, Q), dim3(1024), 0, s, h->cand, wcnt, (long)(w0 * kMaxK), (long)count, idx_out, sc_out, n, nullptr, nullptr, 0);
-    }
+    rank_select(h, Q, tracks, start, avail, count, sel, ghist, wcnt, idx_out, sc_out, s);
   }
   if (which)   // every entry of idx is written by now (an emit or the padding): one term byte per answer, -1 behind the last one
     hipLaunchKernelGGL(which_gather_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, h->which_row, n, ob, which_out);
   CC_HIP(hipGetLastError());
+  if (want_partner)   // the same for a together call: the partner of the row each answer names, from the fold's places (an empty index: all padding)
+    launch_near_gather(idx_out, h->near_pos, nws.L, n, ob, near->cap, partner_out, pscore_out, s);
   if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+  const bool want_np = near && near->n_partners;
+  if (want_np) CC_HIP(hipMemcpyAsync(tot_host + Q, nws.total, 4, hipMemcpyDeviceToHost, s));
   if (!on_device && !zero_copy) {
     CC_HIP(hipMemcpyAsync(idx, h->idx_dev, ob * 4, hipMemcpyDeviceToHost, s));
     CC_HIP(hipMemcpyAsync(score, h->sc_dev, ob * 4, hipMemcpyDeviceToHost, s));
     if (which) CC_HIP(hipMemcpyAsync(which, h->which_dev, ob * 4, hipMemcpyDeviceToHost, s));
+    if (near && near->partner) CC_HIP(hipMemcpyAsync(near->partner, partner_out, ob * 4, hipMemcpyDeviceToHost, s));
+    if (near && near->partner_score) CC_HIP(hipMemcpyAsync(near->partner_score, pscore_out, ob * 4, hipMemcpyDeviceToHost, s));
   }
-  if (!on_device || total) CC_HIP(hipStreamSynchronize(s));
-  if (zero_copy) { memcpy(idx, idx_out, ob * 4); memcpy(score, sc_out, ob * 4); if (which) memcpy(which, which_out, ob * 4); }
+  if (!on_device || total || want_np) CC_HIP(hipStreamSynchronize(s));
+  if (zero_copy) {
+    memcpy(idx, idx_out, ob * 4); memcpy(score, sc_out, ob * 4); if (which) memcpy(which, which_out, ob * 4);
+    if (near && near->partner) memcpy(near->partner, partner_out, ob * 4);
+    if (near && near->partner_score) memcpy(near->partner_score, pscore_out, ob * 4);
+  }
   if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
+  if (want_np) *near->n_partners = (int64_t)tot_host[Q];
   CC_API_END
 }
 
@@ -1897,18 +2009,21 @@ int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, con
   CC_HIP(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const long n = (long)h->n;
-  const int nq = fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
+  const NearQuery* near = fold ? fold->near : nullptr;
+  const int nq = near ? 2 : fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
   const size_t qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255, cbytes = (size_t)Q * n_bins * 4;
-  ensure_pinned(h, qbytes + (size_t)Q * 4);
+  ensure_pinned(h, qbytes + (size_t)(Q + (near ? 1 : 0)) * 4);               // the totals, and behind them the full length of a together call's list
   unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes);
   ensure((void**)&h->rank_ws, &h->rank_ws_cap, (size_t)Q * 4 + cbytes);     // per query the total, then (host caller) the bins
   unsigned* tot_dev = reinterpret_cast<unsigned*>(h->rank_ws);
   unsigned* cnt_dev = on_device ? counts : tot_dev + Q;
   CC_HIP(hipMemsetAsync(tot_dev, 0, (size_t)Q * 4, s));
   CC_HIP(hipMemsetAsync(cnt_dev, 0, cbytes, s));
+  NearWs nws{};
+  if (near) { nws = near_ws(h); CC_HIP(hipMemsetAsync(nws.total, 0, 4, s)); }
   if (n > 0) {
     const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    if (fold) fold_scores(h, *fold, w, on_device, s);
+    if (fold) fold_scores(h, *fold, w, tracks, min_score, allowed_dev, on_device, s);
     else {
       upload_queries(h, q, Q, on_device, s);
       compute_scores(h, Q, s);
@@ -1923,9 +2038,12 @@ int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, con
   }
   CC_HIP(hipGetLastError());
   if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+  const bool want_np = near && near->n_partners;
+  if (want_np) CC_HIP(hipMemcpyAsync(tot_host + Q, nws.total, 4, hipMemcpyDeviceToHost, s));
   if (!on_device) CC_HIP(hipMemcpyAsync(counts, cnt_dev, cbytes, hipMemcpyDeviceToHost, s));
-  if (!on_device || total) CC_HIP(hipStreamSynchronize(s));
+  if (!on_device || total || want_np) CC_HIP(hipStreamSynchronize(s));
   if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
+  if (want_np) *near->n_partners = (int64_t)tot_host[Q];
   CC_API_END
 }
 
@@ -2004,6 +2122,27 @@ int cc_index_timeline_terms(cc_index* h, const float* q, int n_vec, const int64_
   if (const int rc = terms_check(h, q, n_vec, rows, n_rows, terms, combine, flags, nullptr, &tq)) return rc;
   const FoldQuery fold{nullptr, &tq};
   return timeline(h, nullptr, 1, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, t0, bin_seconds, n_bins, counts, total, on_device, stream, &fold);
+}
+
+// Together: the kernels that are new are index_near.hip's (its head tells how they fit together); the checks of the two sides and the join stand
+// in near_check, everything else is rank() / timeline() with the join as the fold.
+int cc_index_rank_near(cc_index* h, const float* qa, int64_t row_a, const float* qb, int64_t row_b, int32_t within, int max_partners, float cut_b, int value,
+                       int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where_a,
+                       const cc_row_filter* where_b, int32_t* idx, float* score, int32_t* partner, float* partner_score, int64_t* total, int64_t* n_partners,
+                       int on_device, void* stream) {
+  NearQuery nq{};
+  if (const int rc = near_check(h, qa, row_a, qb, row_b, within, max_partners, cut_b, value, flags, where_b, partner, partner_score, n_partners, &nq)) return rc;
+  const FoldQuery fold{nullptr, nullptr, &nq};
+  return rank(h, nullptr, 1, start, count, min_score, flags, allowed, n_groups, where_a, idx, score, total, on_device, stream, &fold);
+}
+
+int cc_index_timeline_near(cc_index* h, const float* qa, int64_t row_a, const float* qb, int64_t row_b, int32_t within, int max_partners, float cut_b, int value,
+                           float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where_a, const cc_row_filter* where_b,
+                           int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int64_t* n_partners, int on_device, void* stream) {
+  NearQuery nq{};
+  if (const int rc = near_check(h, qa, row_a, qb, row_b, within, max_partners, cut_b, value, flags, where_b, nullptr, nullptr, n_partners, &nq)) return rc;
+  const FoldQuery fold{nullptr, nullptr, &nq};
+  return timeline(h, nullptr, 1, min_score, flags, allowed, n_groups, where_a, t0, bin_seconds, n_bins, counts, total, on_device, stream, &fold);
 }
 
 // Distinct ranking: the kernels are index_distinct.hip's (its head tells how they fit together); here the checks, the scratch and the copies.
@@ -2177,7 +2316,7 @@ void cc_index_destroy(cc_index* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->emb, (void*)h->grp, (void*)h->trk, (void*)h->ts, (void*)h->cls, (void*)h->attr_tmp, (void*)h->best, (void*)h->first, (void*)h->key_hi, (void*)h->allowed, (void*)h->q16, (void*)h->q_planes, (void*)h->q_dev, (void*)h->scores, (void*)h->cand, (void*)h->idx_dev, (void*)h->sc_dev,
-                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->which_row, (void*)h->which_dev, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io, (void*)h->sight_ws, (void*)h->sight_io}) if (p) hipFree(p);
+                  (void*)h->keep, (void*)h->drop_grp, (void*)h->gcnt, (void*)h->goff, (void*)h->bounce, (void*)h->rank_ws, (void*)h->dead, (void*)h->which_row, (void*)h->which_dev, (void*)h->near_ws, (void*)h->near_pos, (void*)h->near_dev, (void*)h->dist_ws, (void*)h->dist_io, (void*)h->digest_ws, (void*)h->digest_io, (void*)h->sight_ws, (void*)h->sight_io}) if (p) hipFree(p);
   if (h->digest_pin) hipHostFree(h->digest_pin);
   if (h->pin) hipHostFree(h->pin);
   if (h->rows_ev) { hipEventSynchronize(h->rows_ev); hipEventDestroy(h->rows_ev); }

@@ -331,6 +331,24 @@ void launch_sightings(const void* emb, long size, int dim, int storage, const lo
                       int skip_self, const int* grp, int n_gc, int* out_count, unsigned long long* best, unsigned* gc, int* out_best_row,
                       float* out_best_score, hipStream_t stream);
 
+// ---- together: rows with a partner nearby in time (index_near.hip) ----
+constexpr int kNearMaxPartners = 16384;                  // CC_NEAR_MAX_PARTNERS
+// The partner list on the device, kNearMaxPartners entries a column (the offsets are near_list's): row and score as the ranking's emit
+// kernel writes them (-1 / -inf behind the last entry), then what launch_near_pack reads beside each row.
+struct NearList { int* row; int* grp; int* ts; int* trk; float* score; };
+size_t near_list_bytes();
+NearList near_list(void* base);
+// L.row[0 .. cap) -> L.grp / L.ts / L.trk.  One launch.
+void launch_near_pack(const NearList& L, int cap, long n, const int* grp, const int* ts, const int* trk, hipStream_t stream);
+// S[0 .. n) = Sa -> v in place, dead (n bytes) and pos (n int32: the partner's place in the list, -1 none).  n_list: one word on the
+// device, the rows the list would hold without the cap.  where_a / allowed as rank_keys_kernel takes them (where_a.dead null); skip_cut:
+// a row with Sa < min_score may skip the walk (a ranking without track reduction).  One launch.
+void launch_near_fold(float* S, long n, const int* grp, const int* trk, const int* ts, const unsigned char* allowed, int n_allowed, const RowWhere& where_a,
+                      float min_score, int skip_cut, const NearList& L, const unsigned* n_list, int cap, int within, int value, unsigned char* dead, int* pos,
+                      hipStream_t stream);
+// partner / partner_score (cnt each, either may be null) of the answers idx names; -1 / -inf where idx is -1.  One launch.
+void launch_near_gather(const int* idx, const int* pos, const NearList& L, long n, size_t cnt, int cap, int* partner, float* partner_score, hipStream_t stream);
+
 struct NmsP {                 // top-300 + mask NMS + scale_boxes: detection/yolov9.py:406-458
   const float* det; int B, A;
   float iou_thr;

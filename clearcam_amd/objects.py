@@ -589,6 +589,103 @@ class EmbeddingIndex:
                                                       t0, bin_seconds, n_bins, _lib.ptr(counts), _lib.ptr(total), 0, None))
         return counts.astype(np.int64), total
 
+    # -- together: rows with a partner nearby in time (cc_index_rank_near / cc_index_timeline_near) ----------------------------------------
+    def _near_side(self, x, device: bool):
+        """One side of a together call -> (vector or None, row number or -1): an int is a stored row, anything else a (dim,) vector
+        (a numpy array for a host call, a CUDA tensor for a device call)."""
+        if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+            return None, int(x)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if not bool(getattr(x, "is_cuda", False)):
+                x = torch.as_tensor(np.ascontiguousarray(as_numpy(x), dtype=np.float32)).to(dev)
+            v = x.contiguous().float().reshape(-1)
+        else:
+            v = np.ascontiguousarray(as_numpy(x), dtype=np.float32).reshape(-1)
+        if int(v.shape[0]) != self.dim:
+            raise ValueError(f"a side of a together call is one vector of {self.dim} floats or one stored row")
+        return v, -1
+
+    def _near_question(self, a, b, within, partners, cut_b, value, min_score, tracks, device: bool):
+        """The question of a together call, checked -> the arguments h .. flags of cc_index_rank_near without start / count, and the
+        vectors to keep alive"""
+        if value not in _lib.NEAR_VALUE:
+            raise ValueError('value: "a" or "min"')
+        within, partners = int(within), int(partners)
+        if not -(1 << 31) <= within < 1 << 31 or not -(1 << 31) <= partners < 1 << 31:
+            raise ValueError("within and partners must fit in int32")
+        (va, ra), (vb, rb) = self._near_side(a, device), self._near_side(b, device)
+        head = (self._h, _lib.ptr(va), ra, _lib.ptr(vb), rb, within, partners, float(self.cut_f32(cut_b)), _lib.NEAR_VALUE[value])
+        return head, (float(self.cut_f32(min_score)), _lib.RANK_TRACKS if tracks else 0), (va, vb)
+
+    def _near_filters(self, allowed, where_a, where_b):
+        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
+        return (_lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size),
+                C.byref(where_a) if where_a is not None else None, C.byref(where_b) if where_b is not None else None)
+
+    def rank_near(self, a, b, within, start: int = 0, count: int = 100, partners: int = _lib.NEAR_DEFAULT_PARTNERS, cut_b=None, value: str = "min",
+                  allowed=None, min_score=None, tracks: bool = True, ts_range=None, classes=None, b_ts_range=None, b_classes=None):
+        """`rank` for the rows of question `a` that have a partner - an answer of question `b` - within `within` seconds in the same
+        group -> (idx (1, count) int32, score (1, count) f32, total (1,) int64, partner (1, count) int32, partner_score (1, count) f32,
+        n_partners int).  `a` / `b`: a (dim,) vector or an int, a stored row.  The partner list is the first `partners` (at most 16384)
+        answers of an ungrouped `rank` of `b` with the cut `cut_b` and the filter b_ts_range / b_classes, among rows that have a ts;
+        n_partners is its length without the cap.  A row's partner is the first entry of that list - the best-scoring one - that is
+        another row of the same group, at most `within` seconds away (64-bit difference) and not a crop of the row's own track; a row
+        without one does not compete.  value "a": the ranking value is `a`'s score; "min": the smaller of that and the partner's
+        score for `b`.  Everything else - answers per track, tie rules, `min_score` (on the value), ts_range / classes (for `a`),
+        `allowed` (for both), padding - is `rank`'s.  partner / partner_score: per answer the partner's row and its score for `b`, -1 /
+        -inf past the last answer (cc_index_rank_near)."""
+        head, tail, _keep = self._near_question(a, b, within, partners, cut_b, value, min_score, tracks, False)
+        wa, wb = self.row_filter(ts_range, classes), self.row_filter(b_ts_range, b_classes)
+        start, count = int(start), int(count)
+        shape = (1, count) if count >= 1 and start >= 0 else (1, 1)                 # the library names the error
+        idx, sc, total = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
+        pr, ps, n_partners = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
+        _lib.check(_lib.lib().cc_index_rank_near(*head, start, count, *tail, *self._near_filters(allowed, wa, wb), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(pr),
+                                                 _lib.ptr(ps), _lib.ptr(total), _lib.ptr(n_partners), 0, None))
+        return idx, sc, total, pr, ps, int(n_partners[0])
+
+    def rank_near_device(self, a, b, within, start: int = 0, count: int = 100, partners: int = _lib.NEAR_DEFAULT_PARTNERS, cut_b=None, value: str = "min",
+                         allowed=None, min_score=None, tracks: bool = True, with_total: bool = True, ts_range=None, classes=None, b_ts_range=None,
+                         b_classes=None):
+        """`rank_near` with idx / score / partner / partner_score left on the GPU, as `rank_device` leaves them, on the current torch
+        stream; with_total=False returns None for total and n_partners and waits for nothing."""
+        import torch
+        head, tail, keep = self._near_question(a, b, within, partners, cut_b, value, min_score, tracks, True)
+        wa, wb = self.row_filter(ts_range, classes), self.row_filter(b_ts_range, b_classes)
+        dev = torch.device("cuda", self.device)
+        k = max(int(count), 1)
+        idx, pr = (torch.empty((1, k), dtype=torch.int32, device=dev) for _ in range(2))
+        sc, ps = (torch.empty((1, k), dtype=torch.float32, device=dev) for _ in range(2))
+        total, n_partners = (np.zeros(1, np.int64), np.zeros(1, np.int64)) if with_total else (None, None)
+        cur, run = self._run_stream(dev)
+        _lib.check(_lib.lib().cc_index_rank_near(*head, int(start), int(count), *tail, *self._near_filters(allowed, wa, wb), _lib.ptr(idx), _lib.ptr(sc),
+                                                 _lib.ptr(pr), _lib.ptr(ps), _lib.ptr(total) if with_total else None,
+                                                 _lib.ptr(n_partners) if with_total else None, 1, C.c_void_p(run.cuda_stream)))
+        if run is not cur:
+            cur.wait_stream(run)
+            for v in keep:
+                if v is not None:
+                    v.record_stream(run)
+        return idx, sc, total, pr, ps, (int(n_partners[0]) if with_total else None)
+
+    def timeline_near(self, a, b, within, t0: int, bin_seconds: int, n_bins: int, partners: int = _lib.NEAR_DEFAULT_PARTNERS, cut_b=None,
+                      value: str = "min", allowed=None, min_score=None, tracks: bool = True, ts_range=None, classes=None, b_ts_range=None,
+                      b_classes=None):
+        """How the answers of `rank_near` (same question) spread over time -> (counts (1, n_bins) int64, total (1,) int64, n_partners
+        int), binned as `timeline` bins them; total and n_partners equal `rank_near`'s (cc_index_timeline_near)."""
+        head, tail, _keep = self._near_question(a, b, within, partners, cut_b, value, min_score, tracks, False)
+        wa, wb = self.row_filter(ts_range, classes), self.row_filter(b_ts_range, b_classes)
+        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+        if not -(1 << 31) <= t0 < 1 << 31 or not -(1 << 31) <= bin_seconds < 1 << 31 or not -(1 << 31) <= n_bins < 1 << 31:
+            raise ValueError("t0, bin_seconds and n_bins must fit in int32")
+        counts = np.zeros((1, min(max(n_bins, 1), 4096)), np.uint32)               # outside [1, 4096]: the library names the error
+        total, n_partners = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        _lib.check(_lib.lib().cc_index_timeline_near(*head, *tail, *self._near_filters(allowed, wa, wb), t0, bin_seconds, n_bins, _lib.ptr(counts),
+                                                     _lib.ptr(total), _lib.ptr(n_partners), 0, None))
+        return counts.astype(np.int64), total, int(n_partners[0])
+
     # -- distinct answers: near-duplicate answers of a ranked list folded into the first of them (cc_index_gram / cc_index_distinct) ----
     def gram(self, rows, device_out: bool = False):
         """Pairwise similarities of stored rows -> (n, n) float32, out[i][j] = <fetch(rows)[i], fetch(rows)[j]> in f32, 1 <= n <= 1024
@@ -1814,6 +1911,110 @@ class ObjectFinder:
         index, table, ask, _ = setup
         kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
         c, total = index.timeline_terms(t0, bin_seconds, n_bins, **ask, **kw)
+        return c[0], int(total[0])
+
+    @staticmethod
+    def _together_source(x):
+        """What a side of `together` is given as -> "text", "path" or "embedding": a str that names a crop file ('*.jpg', a stored
+        key or the endpoint's form) is a path, any other str a query text, everything else an embedding.  A `Term` names its one
+        source itself."""
+        if isinstance(x, Term):
+            if sum(v is not None for v in (x.text, x.path, x.embedding)) != 1:
+                raise ValueError("a side of together needs exactly one of text, path and embedding")
+            return "text" if x.text is not None else "path" if x.path is not None else "embedding"
+        if isinstance(x, str):
+            return "path" if x.lower().endswith(".jpg") else "text"
+        if x is None:
+            raise ValueError("a side of together needs exactly one of text, path and embedding")
+        return "embedding"
+
+    def _together_setup(self, a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners):
+        """What `together` and `together_timeline` share, everything checked before any GPU work -> (index, table, the keyword
+        arguments of `EmbeddingIndex.rank_near` that say what is asked) or None when there is nothing to search."""
+        kinds = [self._together_source(a), self._together_source(b)]
+        if value not in _lib.NEAR_VALUE:
+            raise ValueError('value: "a" or "min"')
+        within, partners = int(within), int(partners)
+        if not 0 <= within < 1 << 31:
+            raise ValueError("within: seconds in [0, 2^31)")
+        if not 1 <= partners <= _lib.NEAR_MAX_PARTNERS:
+            raise ValueError(f"partners must be in [1, {_lib.NEAR_MAX_PARTNERS}]")
+        for cut in (min_score, min_partner):
+            if cut is not None and cut != cut:
+                raise ValueError("min_score / min_partner is NaN")
+        if not self._has_rows(is_face):
+            print("No embeddings available.")
+            return None
+        index, table = self._index_and_table(is_face)
+        if not hasattr(index, "rank_near"):
+            raise RuntimeError("this index cannot join two questions")
+        sides = []
+        for x, kind in zip((a, b), kinds):
+            src = getattr(x, kind) if isinstance(x, Term) else x
+            if kind == "path":
+                sides.append(self._stored_row(table, src))
+            else:
+                v = np.asarray(as_numpy(self.model._encode_text(src).numpy() if kind == "text" else src), np.float32).reshape(-1)
+                if v.size != index.dim:
+                    raise ValueError(f"a side of together has {v.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
+                sides.append(v)
+        allowed = table.allowed(cam_name, timestamp)
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return None
+        for g in live:
+            if table.bad[g]:                        # names the reference raises on: no host ranking is grown for this call
+                raise ValueError(f"together cannot rank the folder {table.dirs[g]}: it holds crop names that do not parse")
+        ask = dict(a=sides[0], b=sides[1], within=within, partners=partners, cut_b=min_partner, value=value, allowed=allowed, min_score=min_score,
+                   tracks=any(table.truthy[g] for g in live))
+        return index, table, ask
+
+    def together(self, a, b, within=30, start=0, count=100, cam_name=None, timestamp=None, is_face=False, min_score=0.21, min_partner=0.21, value="min",
+                 ts_range=None, classes=None, with_classes=None, partners=_lib.NEAR_DEFAULT_PARTNERS):
+        """Two objects at once: the crops that answer `a` while something that answers `b` is seen within `within` seconds in the
+        same folder ("a person while a white van is at the gate") -> ([(path, score, partner_path, partner_score, dt_seconds)],
+        {"total", "partners", "partners_left"}).  `a` / `b`: a query string, a stored crop's path (its key or the endpoint's form; a
+        string ending in .jpg) or an embedding - or a `Term` naming exactly one of text / path / embedding - resolved as `compound`
+        resolves its terms; an unknown path raises KeyError.  The partners are the best `partners` crops for `b` scoring >=
+        min_partner (with_classes: only crops of those classes) that have a time; a crop's partner is the best of them near it that is
+        neither the crop nor a crop of its own track, dt_seconds the partner's time minus the crop's.  value="min": a result scores
+        the smaller of its own score for `a` and its partner's for `b`; "a": its own alone.  Folders, min_score, ts_range / classes
+        (for `a`) and grouping per track are `search_page`'s.  "partners": the crops that qualified as partners, "partners_left":
+        those beyond the cap, which took no part.  One `EmbeddingIndex.rank_near` call: only the page leaves the GPU."""
+        where = row_filter(ts_range, classes)
+        where_b = row_filter(None, with_classes)
+        start, count = int(start), int(count)
+        if start < 0 or count < 1:
+            raise ValueError("together needs start >= 0 and count >= 1")
+        setup = self._together_setup(a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners)
+        if setup is None:
+            return [], {"total": 0, "partners": 0, "partners_left": 0}
+        index, table, ask = setup
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        if where_b is not None:
+            kw["b_classes"] = with_classes
+        idx, sc, total, pr, ps, n_partners = index.rank_near(start=start, count=min(count, len(table.paths)), **ask, **kw)
+        res = [(table.paths[r], float(v), table.paths[p], float(w), int(table.ts[p]) - int(table.ts[r]))
+               for r, v, p, w in zip(idx[0].tolist(), sc[0], pr[0].tolist(), ps[0]) if r >= 0]
+        return res, {"total": int(total[0]), "partners": min(n_partners, ask["partners"]), "partners_left": max(n_partners - ask["partners"], 0)}
+
+    def together_timeline(self, a, b, within=30, t0=0, bin_seconds=3600, n_bins=24, cam_name=None, timestamp=None, is_face=False, min_score=0.21,
+                          min_partner=0.21, value="min", ts_range=None, classes=None, with_classes=None, partners=_lib.NEAR_DEFAULT_PARTNERS):
+        """How the results of `together` (same question) spread over the day -> (counts (n_bins,) int64, total), binned as `timeline`
+        bins them; `total` is `together`'s.  One `EmbeddingIndex.timeline_near` call."""
+        where = row_filter(ts_range, classes)
+        where_b = row_filter(None, with_classes)
+        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+        if bin_seconds < 1 or not 1 <= n_bins <= 4096:
+            raise ValueError("together_timeline needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
+        setup = self._together_setup(a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners)
+        if setup is None:
+            return np.zeros(n_bins, np.int64), 0
+        index, table, ask = setup
+        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
+        if where_b is not None:
+            kw["b_classes"] = with_classes
+        c, total, _ = index.timeline_near(t0=t0, bin_seconds=bin_seconds, n_bins=n_bins, **ask, **kw)
         return c[0], int(total[0])
 
     def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False, ts_range=None, classes=None):

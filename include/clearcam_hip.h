@@ -635,6 +635,59 @@ int cc_index_timeline_terms(cc_index* h, const float* q, int n_vec, const int64_
                             const uint8_t* allowed, int n_groups, const cc_row_filter* where,
                             int32_t t0, int32_t bin_seconds, int n_bins,
                             uint32_t* counts, int64_t* total, int on_device, void* stream);
+/* Together: rank the rows of one question that have a partner - an answer of a second question - nearby in time in the same folder
+ * ("a person while a white van is at the gate", "someone near my car").  Two objects at once, one ranking; the join runs on the device
+ * over the ts, group and track columns.
+ *   1. Sides.  A is what is ranked, B is what must be nearby.  Each side is either a vector (qa / qb: dim f32, on the device with
+ *      on_device) or a stored row (row_a / row_b with a NULL vector; gathered on the device as cc_index_fetch_rows decodes it; -1 beside a
+ *      vector).  A side needs exactly one of the two.
+ *   2. Scores.  Sa, Sb (N each) are bit for bit what cc_index_scores returns for the batch of the two vectors (A first).  Two queries go
+ *      by the scan route in every storage, so these are also the bits of the single-query calls.
+ *   3. Partner list.  The first max_partners answers of an ungrouped ranking of B: cc_index_rank_where(qb, start 0, count max_partners,
+ *      min_score cut_b, flags 0, allowed, where_b), restricted to rows that have a ts: a row with CC_ROW_NO_TS is never a partner and
+ *      takes no place in the list.  The order is that ranking's: score descending, equal scores by ascending row.
+ *      1 <= max_partners <= CC_NEAR_MAX_PARTNERS; CC_NEAR_DEFAULT_PARTNERS is what callers pass who have no opinion.  n_partners (one
+ *      int64 on the HOST, may be NULL; asking for it waits for the stream as total does) receives the number of rows that would be in the
+ *      list without the cap, so a caller sees a truncated list.
+ *   4. Join.  Entry p of the list qualifies for row r when p != r, grp[p] == grp[r], r has a ts, |ts[p] - ts[r]| <= within with the
+ *      difference taken in 64 bits, and NOT (trk[r] >= 0 and trk[p] == trk[r]): a crop of the same track in the same folder is nobody's
+ *      partner ("person near a red thing" must not answer with the person's own red jacket).  within: seconds, in [0, INT32_MAX].  The
+ *      partner of r is the FIRST qualifying entry in list order, which is the best-scoring one.
+ *   5. Value and dead rows.  A row without a partner is dead.  Otherwise CC_NEAR_VALUE_A: v[r] = Sa[r]; CC_NEAR_VALUE_MIN: v[r] = the
+ *      smaller of Sa[r] and Sb[partner] in the total order of the ranking keys (+0 above -0), the fuzzy AND of CC_COMBINE_MIN.
+ *   6. Result.  That of cc_index_rank_where for a single query whose score vector is v, among the rows that are not dead, allowed and
+ *      passing where_a: the same keys, tie rules, min_score cut (on v), total, -1 / -inf padding, on_device and stream semantics.  With
+ *      CC_RANK_TRACKS a track is reduced among its surviving rows and placed by its first surviving row.  partner (count int32) and
+ *      partner_score (count f32; either may be NULL; on the device with on_device) name for each answer the partner of the row idx names
+ *      and its Sb, -1 / -inf where idx is -1.
+ *   7. cc_index_timeline_near is cc_index_timeline (one query) on the same v and the same dead rows; its total and n_partners equal
+ *      cc_index_rank_near's.
+ *   8. Errors (-22, nothing changed, checked on the host before any launch): those of cc_index_rank_where / cc_index_timeline (for both
+ *      filters); both or neither of vector and row on a side; a row number outside [0, size); within < 0; max_partners out of range; a
+ *      NaN cut_b; an unknown value; unknown flag bits (CC_RANK_TRACKS is the only one).
+ * Launches: the vectors are copied and the rows gathered where queries stand, ONE scoring call scores both, the selection launches of
+ * cc_index_rank_where run on B's score row and leave the list on the device, one small kernel packs it into columns, near_fold_kernel
+ * (one thread per row, the list staged through LDS 1024 entries at a time, the walk stopped at the first qualifying entry) writes v in
+ * place over score row 0, one dead byte and the partner's place per row, then the launches of cc_index_rank_where / cc_index_timeline
+ * for one query follow unchanged, plus a gather of `count` partner entries.  Nothing is read back inside the call.  Scratch: 4 bytes a
+ * row and 350 KB beside what cc_index_rank_terms uses.  The walk costs up to N x max_partners compares when nothing qualifies anywhere;
+ * a row that cannot be an answer (a forbidden group, rejected by where_a, no ts, or - without CC_RANK_TRACKS - Sa below min_score) skips
+ * it. */
+#define CC_NEAR_MAX_PARTNERS     16384
+#define CC_NEAR_DEFAULT_PARTNERS 4096
+#define CC_NEAR_VALUE_A   0   /* v = Sa: rank by A alone, B only decides who competes */
+#define CC_NEAR_VALUE_MIN 1   /* v = min(Sa, Sb[partner]) in key order */
+int cc_index_rank_near(cc_index* h, const float* qa, int64_t row_a, const float* qb, int64_t row_b,
+                       int32_t within, int max_partners, float cut_b, int value,
+                       int64_t start, int64_t count, float min_score, int flags,
+                       const uint8_t* allowed, int n_groups, const cc_row_filter* where_a, const cc_row_filter* where_b,
+                       int32_t* idx, float* score, int32_t* partner, float* partner_score, int64_t* total, int64_t* n_partners,
+                       int on_device, void* stream);
+int cc_index_timeline_near(cc_index* h, const float* qa, int64_t row_a, const float* qb, int64_t row_b,
+                           int32_t within, int max_partners, float cut_b, int value, float min_score, int flags,
+                           const uint8_t* allowed, int n_groups, const cc_row_filter* where_a, const cc_row_filter* where_b,
+                           int32_t t0, int32_t bin_seconds, int n_bins,
+                           uint32_t* counts, int64_t* total, int64_t* n_partners, int on_device, void* stream);
 /* Distinct answers: thin ranked lists so that the same picture, stored under many track ids, on many days or by many cameras,
  * answers once.  The embedding-space counterpart of what the detector does with boxes, behind any of the ranking calls above. */
 #define CC_DISTINCT_MAX_DEPTH 1024
