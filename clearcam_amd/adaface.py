@@ -67,7 +67,7 @@ class ADAFACE:
         cur = run = torch.cuda.current_stream(f.device)
         if cur.cuda_stream == 0:
             # torch's default stream has the handle 0, which the library reads as "no stream given": run on a side stream fenced by the
-            # current one on both sides instead (as EmbeddingIndex._search_device does)
+            # current one on both sides instead (as EmbeddingIndex._call does)
             if getattr(self, "_side_stream", None) is None:
                 self._side_stream = torch.cuda.Stream(f.device)
             run = self._side_stream

@@ -21,8 +21,9 @@
 // cc_index_timeline counts the answers of a ranking into bins of their ts (timeline_kernel) instead of selecting a window.
 //
 // cc_index_rank_like takes its queries from the matrix itself ("more like this stored crop / this whole track"): fetch_rows_kernel
-// gathers and decodes them, like_fold_kernel folds their score vectors into one by the row-wise maximum and marks the excluded rows,
-// which row_passes then keeps out of the ranking like rows the filter rejects ("Query by stored rows").
+// gathers and decodes them, terms_fold_kernel (every row a RANK term under MAX) folds their score vectors into one by the row-wise
+// maximum and marks the excluded rows, which row_passes then keeps out of the ranking like rows the filter rejects (DESIGN.md
+// section 4, "Query by stored rows").
 //
 // cc_index_rank_terms / cc_index_timeline_terms rank a compound question: up to 64 terms (vectors the caller brings and stored rows) are
 // scored in one batch, terms_fold_kernel folds them by role (RANK through max / min / a weighted sum, REQUIRE and REJECT into the dead
@@ -766,8 +767,9 @@ __global__ __launch_bounds__(256) void timeline_kernel(const unsigned* __restric
 
 // ---- query by stored rows (cc_index_fetch_rows / cc_index_rank_like) ------------------------------------------------------------
 // The queries are rows of the matrix: a gather decodes them to f32 where upload_queries would have copied them, the scoring routes
-// of compute_scores run as for any batch, one pass folds the (Q, n) score matrix into one vector (the row-wise maximum) and marks the
-// excluded rows, and the ranking of ONE query follows unchanged.  Ordered by the stream alone, like everything above.
+// of compute_scores run as for any batch, one pass of terms_fold_kernel (below) folds the (Q, n) score matrix into one vector (the
+// row-wise maximum) and marks the excluded rows, and the ranking of ONE query follows unchanged.  Ordered by the stream alone, like
+// everything above.
 
 // Up to CC_LIKE_MAX_ROWS row numbers by value, in the kernel arguments (-1 behind the last one): the query rows of a
 // cc_index_rank_like, for the gather and for the fold.
@@ -799,66 +801,11 @@ __global__ __launch_bounds__(64) void fetch_rows_kernel(const char* __restrict__
   }
 }
 
-// the larger of two scores in the order of the ranking keys: +0 beats -0
-__device__ __forceinline__ float omax(float a, float b) { return ordered(b) > ordered(a) ? b : a; }
-
-// S (Q, n) -> S[0][r] = max over q of S[q][r], in place, and dead[r] (dead != null).  mode 1: the query rows are dead; mode 2: every
-// row of group G and slot T is (the query rows among them: they all have that group and that slot).  A thread reads S[.][r] and
-// writes S[0][r] and dead[r] of its own rows only, so no thread reads what another one writes and the pass needs neither atomics nor
-// LDS.  VEC (n % 4 == 0: row q of S starts at byte 4 q n, a multiple of 16 only then): four consecutive rows per thread with one
-// 16-byte load per query, the loads of a thread independent of each other.  Otherwise one row per thread and 4-byte loads.
-template <bool VEC>
-__global__ __launch_bounds__(256) void like_fold_kernel(float* __restrict__ S, int Q, long n, const int* __restrict__ grp, const int* __restrict__ trk,
-                                                        const LikeRows rows, int mode, int G, int T, unsigned char* __restrict__ dead) {
-  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nt = (long)gridDim.x * 256;
-  if (VEC) {
-    const long n4 = n >> 2;
-    float4* S4 = reinterpret_cast<float4*>(S);
-    for (long i = tid; i < n4; i += nt) {
-      if (Q > 1) {
-        float4 m = S4[i];
-#pragma unroll 4
-        for (int q = 1; q < Q; ++q) {
-          const float4 x = S4[(long)q * n4 + i];
-          m.x = omax(m.x, x.x); m.y = omax(m.y, x.y); m.z = omax(m.z, x.z); m.w = omax(m.w, x.w);
-        }
-        S4[i] = m;
-      }
-      if (dead) {
-        unsigned d = 0u;
-        if (mode == 2) {
-          const int4 g = reinterpret_cast<const int4*>(grp)[i], t = reinterpret_cast<const int4*>(trk)[i];
-          d = (g.x == G && t.x == T ? 1u : 0u) | (g.y == G && t.y == T ? 1u << 8 : 0u) | (g.z == G && t.z == T ? 1u << 16 : 0u) | (g.w == G && t.w == T ? 1u << 24 : 0u);
-        } else {
-          for (int j = 0; j < rows.n; ++j) {
-            const long k = (long)rows.r[j] - 4 * i;
-            if (k >= 0 && k < 4) d |= 1u << (8 * (int)k);
-          }
-        }
-        reinterpret_cast<unsigned*>(dead)[i] = d;
-      }
-    }
-  } else {
-    for (long r = tid; r < n; r += nt) {
-      if (Q > 1) {
-        float m = S[r];
-#pragma unroll 4
-        for (int q = 1; q < Q; ++q) m = omax(m, S[(long)q * n + r]);
-        S[r] = m;
-      }
-      if (dead) {
-        bool d = false;
-        if (mode == 2) d = grp[r] == G && trk[r] == T;
-        else for (int j = 0; j < rows.n; ++j) d = d || (long)rows.r[j] == r;
-        dead[r] = d ? 1 : 0;
-      }
-    }
-  }
-}
-
 // ---- compound search (cc_index_rank_terms / cc_index_timeline_terms) -----------------------------------------------------------------
-// like_fold_kernel with roles: S (T, n) -> S[0][r] = the ranking value of row r from the RANK terms, dead[r] from the REQUIRE / REJECT
-// terms and the exclude flags, which[r] = the RANK term that made the value.  What each term is travels by value in the arguments.
+// The fold of every ranking whose ONE score vector comes from several: S (T, n) -> S[0][r] = the ranking value of row r from the RANK
+// terms, dead[r] from the REQUIRE / REJECT terms and the exclude flags, which[r] = the RANK term that made the value.  What each term is
+// travels by value in the arguments.  cc_index_rank_like is the case "every term a stored row, RANK, MAX": the row-wise maximum in
+// the order of the ranking keys (+0 beats -0), the same bits whichever of equal scores is kept.
 struct TermParam { float weight, cut; int role, pad; };                      // 16 bytes: one scalar load per term
 struct TermSpec { int T, combine, pad0, pad1; TermParam t[CC_TERMS_MAX]; };
 
@@ -898,9 +845,10 @@ __device__ __forceinline__ void term_step(TermAcc (&a)[R], const TermParam m, bo
 
 __device__ __forceinline__ float term_value(const TermAcc& a, bool sum, unsigned flip) { return sum ? a.v : unordered(a.k ^ flip); }
 
-// The shape of like_fold_kernel: a thread reads S[.][r] of its own rows and writes S[0][r], dead[r] (dead != null) and which[r]
-// (which != null) of those rows only: no atomics, no LDS, no second score buffer, in place over row 0.  VEC (n % 4 == 0): four
-// consecutive rows per thread, one 16-byte load per term, dead / which written as one 32-bit word each.  Otherwise one row per thread.
+// A thread reads S[.][r] of its own rows and writes S[0][r], dead[r] (dead != null) and which[r] (which != null) of those rows only,
+// so no thread reads what another one writes: no atomics, no LDS, no second score buffer, in place over row 0.  VEC (n % 4 == 0: row
+// t of S starts at byte 4 t n, a multiple of 16 only then): four consecutive rows per thread, one 16-byte load per term, dead / which
+// written as one 32-bit word each.  Otherwise one row per thread and 4-byte loads.
 // What a term is is the same for every thread (one 16-byte scalar load from the arguments, uniform branches).  mode 1: the rows of
 // `excl` are dead too (the stored rows that are RANK terms); mode 2: every row of group G and slot Tk is.
 template <bool VEC>
@@ -1500,83 +1448,6 @@ int remove_impl(cc_index* h, bool by_rows, const uint8_t* drop, int64_t n_rows, 
   CC_API_END
 }
 
-// Top-k among the rows whose group is allowed (allowed: n_groups bytes on the HOST, one per group id, non-zero = keep;
-// null = every row).  Rows of a group id >= n_groups are filtered out.  tracks: the answers are tracks (their best row) and
-// slot-less rows instead of rows - one more pass over scores + trk between the scan and the selection.
-int search(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
-           int on_device, void* stream, bool tracks) {
-  CC_API_BEGIN
-  CC_CHECK(h && q && idx && score && Q > 0, "bad argument");
-  CC_CHECK(k > 0 && k <= kMaxK, "k must be in [1, 1024]");
-  CC_CHECK(!tracks || h->n < (1LL << 31), "a track search needs fewer than 2^31 rows");   // keys hold ~row and ~(n + row) in 32 bits
-  CC_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const size_t ob = (size_t)Q * k;
-  if (h->out_cap < ob) {
-    if (h->idx_dev) hipFree(h->idx_dev);
-    if (h->sc_dev) hipFree(h->sc_dev);
-    CC_HIP(hipMalloc((void**)&h->idx_dev, ob * 4 + 256)); CC_HIP(hipMalloc((void**)&h->sc_dev, ob * 4 + 256)); h->out_cap = ob;
-  }
-  const int nchunk = (int)std::max<int64_t>(1, (h->n + kChunk - 1) / kChunk);
-  ensure((void**)&h->cand, &h->cand_cap, (size_t)Q * nchunk * k * 8);
-  // Host caller with a small result (the interactive case: one query, k = 100): the merge kernel writes (id, score) into
-  // pinned host memory and the only host-side wait is the stream synchronize - no pageable copies in either direction.
-  const size_t qbytes = ((size_t)Q * h->dim * 4 + 255) & ~(size_t)255;
-  const bool zero_copy = !on_device && ob * 8 <= kPinResultBytes;
-  if (zero_copy) ensure_pinned(h, qbytes + ob * 8);
-  int* idx_out = zero_copy ? reinterpret_cast<int*>(h->pin + qbytes) : h->idx_dev;
-  float* sc_out = zero_copy ? reinterpret_cast<float*>(h->pin + qbytes + ob * 4) : h->sc_dev;
-  const unsigned char* allowed_dev = nullptr;
-  if (allowed) {
-    CC_CHECK(n_groups > 0 && n_groups <= (1 << 24), "bad group count");
-    // the kernel indexes the bitmap with the row's group id: size it for every id the caller may have used (ids are < 2^24)
-    if (h->allowed_cap < n_groups) {
-      if (h->allowed) hipFree(h->allowed);
-      h->allowed = nullptr; h->allowed_cap = 0;
-      int cap = 1024; while (cap < n_groups) cap *= 2;
-      CC_HIP(hipMalloc((void**)&h->allowed, (size_t)cap)); h->allowed_cap = cap;
-    }
-    CC_HIP(hipMemsetAsync(h->allowed, 0, (size_t)h->allowed_cap, s));
-    CC_HIP(hipMemcpyAsync(h->allowed, allowed, (size_t)n_groups, hipMemcpyHostToDevice, s));
-    allowed_dev = h->allowed;
-  }
-  if (h->n > 0) {
-    upload_queries(h, q, Q, on_device, s);
-    compute_scores(h, Q, s);
-    if (tracks) {
-      const int T = std::max(h->n_slots, 1);
-      ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
-      ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
-      CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
-      ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * h->n * 4);
-      CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
-      hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((h->n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, (long)h->n, T, h->trk, h->grp,
-                         allowed_dev, h->allowed_cap, RowWhere{}, h->best, h->first);
-      hipLaunchKernelGGL(topk_stage1<true>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
-                         h->trk, h->best, h->first, T, h->key_hi);
-    } else {
-      hipLaunchKernelGGL(topk_stage1<false>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
-                         nullptr, nullptr, nullptr, 0, nullptr);
-    }
-  } else {
-    CC_HIP(hipMemsetAsync(h->cand, 0, (size_t)Q * nchunk * k * 8, s));
-  }
-  if (tracks) hipLaunchKernelGGL(topk_stage2<true>, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out, (long)h->n, h->trk, h->best, std::max(h->n_slots, 1));
-  else hipLaunchKernelGGL(topk_stage2<false>, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out, (long)h->n, nullptr, nullptr, 0);
-  CC_HIP(hipGetLastError());
-  if (zero_copy) {
-    CC_HIP(hipStreamSynchronize(s));
-    memcpy(idx, idx_out, ob * 4);
-    memcpy(score, sc_out, ob * 4);
-  } else {
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    CC_HIP(hipMemcpyAsync(idx, h->idx_dev, ob * 4, kind, s));
-    CC_HIP(hipMemcpyAsync(score, h->sc_dev, ob * 4, kind, s));
-    if (!on_device) CC_HIP(hipStreamSynchronize(s));
-  }
-  CC_API_END
-}
-
 // The per-group filter of a call on the device (h->allowed, zero beyond n_groups), or null without one.
 const unsigned char* upload_allowed(cc_index* h, const uint8_t* allowed, int n_groups, hipStream_t s) {
   if (!allowed) return nullptr;
@@ -1606,6 +1477,84 @@ RowWhere make_where(const cc_index* h, const cc_row_filter* where) {
   return w;
 }
 
+// Room for (Q, k) answers in h->idx_dev / h->sc_dev: where search() and rank() leave what a copy then takes to the caller.
+void ensure_out(cc_index* h, size_t ob) {
+  if (h->out_cap >= ob) return;
+  if (h->idx_dev) hipFree(h->idx_dev);
+  if (h->sc_dev) hipFree(h->sc_dev);
+  h->idx_dev = nullptr; h->sc_dev = nullptr; h->out_cap = 0;
+  CC_HIP(hipMalloc((void**)&h->idx_dev, ob * 4 + 256)); CC_HIP(hipMalloc((void**)&h->sc_dev, ob * 4 + 256)); h->out_cap = ob;
+}
+
+// The track reduction of search() and rank_keys() over the (Q, n) scores: h->best and h->first made and cleared, then the launch.  n > 0.
+void track_reduce(cc_index* h, int Q, const unsigned char* allowed_dev, const RowWhere& w, hipStream_t s) {
+  const long n = (long)h->n;
+  const int T = std::max(h->n_slots, 1);
+  ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
+  ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
+  CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
+  CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
+  hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, n, T, h->trk, h->grp,
+                     allowed_dev, h->allowed_cap, w, h->best, h->first);
+}
+
+// Top-k among the rows whose group is allowed (allowed: n_groups bytes on the HOST, one per group id, non-zero = keep;
+// null = every row).  Rows of a group id >= n_groups are filtered out.  tracks: the answers are tracks (their best row) and
+// slot-less rows instead of rows - one more pass over scores + trk between the scan and the selection.
+int search(cc_index* h, const float* q, int Q, int k, const uint8_t* allowed, int n_groups, int32_t* idx, float* score,
+           int on_device, void* stream, bool tracks) {
+  CC_API_BEGIN
+  CC_CHECK(h && q && idx && score && Q > 0, "bad argument");
+  CC_CHECK(k > 0 && k <= kMaxK, "k must be in [1, 1024]");
+  CC_CHECK(!tracks || h->n < (1LL << 31), "a track search needs fewer than 2^31 rows");   // keys hold ~row and ~(n + row) in 32 bits
+  CC_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const size_t ob = (size_t)Q * k;
+  ensure_out(h, ob);
+  const int nchunk = (int)std::max<int64_t>(1, (h->n + kChunk - 1) / kChunk);
+  ensure((void**)&h->cand, &h->cand_cap, (size_t)Q * nchunk * k * 8);
+  // Host caller with a small result (the interactive case: one query, k = 100): the merge kernel writes (id, score) into
+  // pinned host memory and the only host-side wait is the stream synchronize - no pageable copies in either direction.
+  const size_t qbytes = ((size_t)Q * h->dim * 4 + 255) & ~(size_t)255;
+  const bool zero_copy = !on_device && ob * 8 <= kPinResultBytes;
+  if (zero_copy) ensure_pinned(h, qbytes + ob * 8);
+  int* idx_out = zero_copy ? reinterpret_cast<int*>(h->pin + qbytes) : h->idx_dev;
+  float* sc_out = zero_copy ? reinterpret_cast<float*>(h->pin + qbytes + ob * 4) : h->sc_dev;
+  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  // the kernel indexes the bitmap with the row's group id: upload_allowed sizes it for every id the caller may have used (ids are < 2^24)
+  const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
+  if (h->n > 0) {
+    upload_queries(h, q, Q, on_device, s);
+    compute_scores(h, Q, s);
+    if (tracks) {
+      const int T = std::max(h->n_slots, 1);
+      ensure((void**)&h->key_hi, &h->key_hi_cap, (size_t)Q * h->n * 4);
+      track_reduce(h, Q, allowed_dev, RowWhere{}, s);
+      hipLaunchKernelGGL(topk_stage1<true>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
+                         h->trk, h->best, h->first, T, h->key_hi);
+    } else {
+      hipLaunchKernelGGL(topk_stage1<false>, dim3(nchunk, Q), dim3(1024), 0, s, h->scores, (long)h->n, k, h->cand, h->grp, allowed_dev, h->allowed_cap,
+                         nullptr, nullptr, nullptr, 0, nullptr);
+    }
+  } else {
+    CC_HIP(hipMemsetAsync(h->cand, 0, (size_t)Q * nchunk * k * 8, s));
+  }
+  if (tracks) hipLaunchKernelGGL(topk_stage2<true>, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out, (long)h->n, h->trk, h->best, std::max(h->n_slots, 1));
+  else hipLaunchKernelGGL(topk_stage2<false>, dim3(Q), dim3(1024), 0, s, h->cand, (long)nchunk * k, k, idx_out, sc_out, (long)h->n, nullptr, nullptr, 0);
+  CC_HIP(hipGetLastError());
+  if (zero_copy) {
+    CC_HIP(hipStreamSynchronize(s));
+    memcpy(idx, idx_out, ob * 4);
+    memcpy(score, sc_out, ob * 4);
+  } else {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    CC_HIP(hipMemcpyAsync(idx, h->idx_dev, ob * 4, kind, s));
+    CC_HIP(hipMemcpyAsync(score, h->sc_dev, ob * 4, kind, s));
+    if (!on_device) CC_HIP(hipStreamSynchronize(s));
+  }
+  CC_API_END
+}
+
 // What cc_index_rank_where and cc_index_timeline share behind the scan: (track reduction,) keys + totals.  n > 0.
 void rank_keys(cc_index* h, int Q, bool tracks, float min_score, const unsigned char* allowed_dev, const RowWhere& w, unsigned* tot_dev, hipStream_t s) {
   const long n = (long)h->n;
@@ -1613,12 +1562,7 @@ void rank_keys(cc_index* h, int Q, bool tracks, float min_score, const unsigned 
   const unsigned nblk = (unsigned)((n + kRankRows - 1) / kRankRows);
   const int T = std::max(h->n_slots, 1);
   if (tracks) {
-    ensure((void**)&h->best, &h->best_cap, (size_t)Q * T * 8);
-    ensure((void**)&h->first, &h->first_cap, (size_t)T * 4);
-    CC_HIP(hipMemsetAsync(h->best, 0, (size_t)Q * T * 8, s));
-    CC_HIP(hipMemsetAsync(h->first, 0xff, (size_t)T * 4, s));
-    hipLaunchKernelGGL(track_reduce_kernel, dim3((unsigned)((n + kTrkRows - 1) / kTrkRows), Q), dim3(256), 0, s, h->scores, n, T, h->trk, h->grp,
-                       allowed_dev, h->allowed_cap, w, h->best, h->first);
+    track_reduce(h, Q, allowed_dev, w, s);
     hipLaunchKernelGGL(rank_keys_kernel<true>, dim3(nblk, Q), dim3(256), 0, s, h->scores, n, h->grp, allowed_dev, h->allowed_cap, h->trk, h->best, h->first, T,
                        min_score, w, h->key_hi, tot_dev);
   } else {
@@ -1671,50 +1615,36 @@ void gather_rows(cc_index* h, const int64_t* rows, int n, float* out, hipStream_
   CC_HIP(hipEventRecord(h->rows_ev, s));
 }
 
-// The query side of cc_index_rank_like, checked: the rows, and what is excluded (0 nothing, 1 the query rows, 2 group G + slot T).
-struct LikeQuery { const int64_t* rows; int n, exclude, G, T; };
+// The query side of a folded ranking (cc_index_rank_terms / cc_index_timeline_terms, cc_index_rank_like), checked: the vectors, the rows, what each term is (spec), which
+// rows the exclude bits kill (mode 0 nothing, 1 the rows of excl, 2 group G + slot Tk), whether any term or flag can kill a row, and
+// where the caller wants `which` (null: not asked for).
+struct TermsQuery { const float* q; int n_vec; const int64_t* rows; int n_rows; TermSpec spec; LikeRows excl; int mode, G, Tk; bool kills; int32_t* which; };
 
-int like_check(cc_index* h, const int64_t* rows, int n_rows, int flags, LikeQuery* like) {
+// The query side of cc_index_rank_like, checked by its own rules, as the compound question it is: no vector, every row a RANK term of
+// weight 1 under MAX, the exclude bits as they are, no `which`.
+int like_check(cc_index* h, const int64_t* rows, int n_rows, int flags, TermsQuery* tq) {
   CC_API_BEGIN
   CC_CHECK(h && rows, "null argument");
   CC_CHECK(n_rows >= 1 && n_rows <= CC_LIKE_MAX_ROWS, "n_rows must be in [1, CC_LIKE_MAX_ROWS]");
   CC_CHECK((flags & ~(CC_RANK_TRACKS | CC_LIKE_EXCLUDE_ROWS | CC_LIKE_EXCLUDE_TRACK)) == 0, "unknown flag bits");
   check_rows(h, rows, n_rows);
-  *like = LikeQuery{rows, n_rows, (flags & CC_LIKE_EXCLUDE_TRACK) ? 2 : (flags & CC_LIKE_EXCLUDE_ROWS) ? 1 : 0, 0, -1};
-  if (like->exclude == 2) {
+  *tq = TermsQuery{};
+  tq->rows = rows; tq->n_rows = n_rows;
+  tq->spec.T = n_rows; tq->spec.combine = CC_COMBINE_MAX;
+  for (int t = 0; t < n_rows; ++t) tq->spec.t[t] = TermParam{1.f, 0.f, CC_TERM_RANK, 0};
+  tq->excl = like_rows(rows, n_rows);                // n < 2^31 (checked by rank())
+  tq->mode = (flags & CC_LIKE_EXCLUDE_TRACK) ? 2 : (flags & CC_LIKE_EXCLUDE_ROWS) ? 1 : 0;
+  tq->G = 0; tq->Tk = -1;
+  tq->kills = tq->mode != 0;
+  if (tq->mode == 2) {
     CC_CHECK(h->grp_host.size() == (size_t)h->n && h->trk_host.size() == (size_t)h->n, "the host columns are out of step with the index");
-    like->G = h->grp_host[(size_t)rows[0]]; like->T = h->trk_host[(size_t)rows[0]];
-    CC_CHECK(like->T >= 0, "CC_LIKE_EXCLUDE_TRACK needs query rows with a track slot");
+    tq->G = h->grp_host[(size_t)rows[0]]; tq->Tk = h->trk_host[(size_t)rows[0]];
+    CC_CHECK(tq->Tk >= 0, "CC_LIKE_EXCLUDE_TRACK needs query rows with a track slot");
     for (int i = 1; i < n_rows; ++i)
-      CC_CHECK(h->grp_host[(size_t)rows[i]] == like->G && h->trk_host[(size_t)rows[i]] == like->T, "CC_LIKE_EXCLUDE_TRACK needs query rows of one group and one track slot");
+      CC_CHECK(h->grp_host[(size_t)rows[i]] == tq->G && h->trk_host[(size_t)rows[i]] == tq->Tk, "CC_LIKE_EXCLUDE_TRACK needs query rows of one group and one track slot");
   }
   CC_API_END
 }
-
-// What cc_index_rank_like runs where cc_index_rank_where uploads and scores its queries: gather, score, fold (+ the dead bytes).
-// Leaves the folded vector in row 0 of h->scores and, with an exclusion, w.dead set.  One query row and no exclusion: no fold.
-void like_scores(cc_index* h, const LikeQuery& like, RowWhere& w, hipStream_t s) {
-  const long n = (long)h->n;
-  ensure_queries(h, like.n);
-  gather_rows(h, like.rows, like.n, h->q_dev, s);
-  compute_scores(h, like.n, s);
-  if (like.n == 1 && !like.exclude) return;
-  unsigned char* dead = nullptr;
-  if (like.exclude) { ensure((void**)&h->dead, &h->dead_cap, (size_t)n); w.dead = dead = h->dead; }
-  const LikeRows lr = like_rows(like.rows, like.n);  // n < 2^31 (checked by rank())
-  if (n % 4 == 0)
-    hipLaunchKernelGGL(like_fold_kernel<true>, dim3((unsigned)std::min<long>((n / 4 + 255) / 256, 256 * 8)), dim3(256), 0, s, h->scores, like.n, n, h->grp, h->trk, lr,
-                       like.exclude, like.G, like.T, dead);
-  else
-    hipLaunchKernelGGL(like_fold_kernel<false>, dim3((unsigned)std::min<long>((n + 255) / 256, 256 * 8)), dim3(256), 0, s, h->scores, like.n, n, h->grp, h->trk, lr,
-                       like.exclude, like.G, like.T, dead);
-  CC_HIP(hipGetLastError());
-}
-
-// The query side of cc_index_rank_terms / cc_index_timeline_terms, checked: the vectors, the rows, what each term is (spec), which
-// rows the exclude bits kill (mode 0 nothing, 1 the rows of excl, 2 group G + slot Tk), whether any term or flag can kill a row, and
-// where the caller wants `which` (null: not asked for).
-struct TermsQuery { const float* q; int n_vec; const int64_t* rows; int n_rows; TermSpec spec; LikeRows excl; int mode, G, Tk; bool kills; int32_t* which; };
 
 int terms_check(cc_index* h, const float* q, int n_vec, const int64_t* rows, int n_rows, const cc_term* terms, int combine, int flags, int32_t* which,
                 TermsQuery* tq) {
@@ -1762,9 +1692,10 @@ int terms_check(cc_index* h, const float* q, int n_vec, const int64_t* rows, int
   CC_API_END
 }
 
-// What cc_index_rank_terms runs where cc_index_rank_where uploads and scores its queries: the vectors copied and the rows gathered
-// into ONE batch of T queries, scored by the route of that batch, folded.  Leaves v in row 0 of h->scores, w.dead set when a term or a
-// flag can kill a row, and h->which_row written when `which` is asked for.  One RANK vector under MAX / MIN and nothing else: no fold.
+// What cc_index_rank_terms and cc_index_rank_like run where cc_index_rank_where uploads and scores its queries: the vectors copied and
+// the rows gathered into ONE batch of T queries, scored by the route of that batch, folded.  Leaves v in row 0 of h->scores, w.dead set
+// when a term or a flag can kill a row, and h->which_row written when `which` is asked for.  One RANK term under MAX / MIN and nothing
+// else: no fold.
 void terms_scores(cc_index* h, const TermsQuery& tq, RowWhere& w, int on_device, hipStream_t s) {
   const long n = (long)h->n;
   const int T = tq.spec.T;
@@ -1883,14 +1814,67 @@ void near_scores(cc_index* h, const NearQuery& nq, RowWhere& w, bool tracks, flo
   w.dead = h->dead;
 }
 
-// Where the ONE score vector of a ranking comes from when it is not a caller's query: the fold of a cc_index_rank_like, that of a
-// cc_index_rank_terms / cc_index_timeline_terms or the join of a cc_index_rank_near / cc_index_timeline_near.  Exactly one of the three is set.
-struct FoldQuery { const LikeQuery* like; const TermsQuery* terms; const NearQuery* near; };
+// Where the ONE score vector of a ranking comes from when it is not a caller's query: the fold of a cc_index_rank_like / cc_index_rank_terms /
+// cc_index_timeline_terms or the join of a cc_index_rank_near / cc_index_timeline_near.  Exactly one of the two is set.
+struct FoldQuery { const TermsQuery* terms; const NearQuery* near; };
 
 void fold_scores(cc_index* h, const FoldQuery& f, RowWhere& w, bool tracks, float min_score, const unsigned char* allowed_dev, int on_device, hipStream_t s) {
-  if (f.like) like_scores(h, *f.like, w, s);
-  else if (f.terms) terms_scores(h, *f.terms, w, on_device, s);
+  if (f.terms) terms_scores(h, *f.terms, w, on_device, s);
   else near_scores(h, *f.near, w, tracks, min_score, allowed_dev, on_device, s);
+}
+
+// What rank() and timeline() share around their own selection.  rank_begin: the call as checked - the stream, the row filter, whether
+// tracks answer, the together question behind a fold, and qbytes, the head of the pinned block that the queries go through.  The caller
+// sizes the pinned block and its scratch behind that and says where the totals stand (tot_host, tot_dev).
+struct RankCall {
+  bool tracks; RowWhere w; hipStream_t s; long n; const NearQuery* near; size_t qbytes;
+  NearWs nws;                                     // a together call: its own scratch, whose total rank_scores clears
+  unsigned* tot_host; unsigned* tot_dev;          // (Q) the totals, and on the host behind them the full length of a together call's list
+};
+
+RankCall rank_begin(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
+                    bool outputs, void* stream, const FoldQuery* fold) {
+  CC_CHECK(h && (q || fold) && outputs, "null argument");
+  CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
+  CC_CHECK(min_score == min_score, "min_score is NaN");
+  CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
+  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");       // keys hold ~row and ~(n + row) in 32 bits
+  RankCall c{};
+  c.tracks = (flags & CC_RANK_TRACKS) != 0;
+  c.w = make_where(h, where);
+  CC_HIP(hipSetDevice(h->device));
+  c.s = stream ? (hipStream_t)stream : h->stream;
+  c.n = (long)h->n;
+  c.near = fold ? fold->near : nullptr;
+  const int nq = c.near ? 2 : fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
+  c.qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255;
+  return c;
+}
+
+// The ONE score vector per query and its keys: the together scratch total cleared, then (n > 0) the group filter, the scores - a
+// fold's, or the caller's queries uploaded and scored -, (track reduction,) keys + totals.
+void rank_scores(cc_index* h, RankCall& c, const float* q, int Q, float min_score, const uint8_t* allowed, int n_groups, int on_device, const FoldQuery* fold) {
+  if (c.near) { c.nws = near_ws(h); CC_HIP(hipMemsetAsync(c.nws.total, 0, 4, c.s)); }
+  if (c.n <= 0) return;
+  const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, c.s);
+  if (fold) fold_scores(h, *fold, c.w, c.tracks, min_score, allowed_dev, on_device, c.s);
+  else {
+    upload_queries(h, q, Q, on_device, c.s);
+    compute_scores(h, Q, c.s);
+  }
+  rank_keys(h, Q, c.tracks, min_score, allowed_dev, c.w, c.tot_dev, c.s);
+}
+
+// Behind everything a call has put on the stream: the totals (and a together call's list length) to the host, when asked for.  A host
+// caller waits for the stream whatever it asked for: its results come by the same stream.
+void rank_totals(const RankCall& c, int Q, int64_t* total, int on_device) {
+  if (total) CC_HIP(hipMemcpyAsync(c.tot_host, c.tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, c.s));
+  const bool want_np = c.near && c.near->n_partners;
+  if (want_np) CC_HIP(hipMemcpyAsync(c.tot_host + Q, c.nws.total, 4, hipMemcpyDeviceToHost, c.s));
+  if (!on_device || total || want_np) CC_HIP(hipStreamSynchronize(c.s));
+  if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)c.tot_host[i];
+  if (want_np) *c.near->n_partners = (int64_t)c.tot_host[Q];
 }
 
 // cc_index_rank / cc_index_rank_where.  Launches on one stream: scan, (track reduction,) keys + totals, then per batch of up to 16 windows of kMaxK answers:
@@ -1901,29 +1885,19 @@ void fold_scores(cc_index* h, const FoldQuery& f, RowWhere& w, bool tracks, floa
 int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float min_score, int flags, const uint8_t* allowed, int n_groups,
          const cc_row_filter* where, int32_t* idx, float* score, int64_t* total, int on_device, void* stream, const FoldQuery* fold = nullptr) {
   CC_API_BEGIN
-  CC_CHECK(h && (q || fold) && idx && score, "null argument");
-  CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
+  RankCall c = rank_begin(h, q, Q, min_score, flags, allowed, n_groups, where, idx && score, stream, fold);
   CC_CHECK(start >= 0, "start must not be negative");
   CC_CHECK(count >= 1 && count <= (1LL << 40) / Q, "count must be positive (and Q * count below 2^40)");
-  CC_CHECK(min_score == min_score, "min_score is NaN");
-  CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
-  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
-  CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");       // keys hold ~row and ~(n + row) in 32 bits
-  const bool tracks = (flags & CC_RANK_TRACKS) != 0;
-  RowWhere w = make_where(h, where);
-  CC_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const long n = (long)h->n;
-  const size_t ob = (size_t)Q * (size_t)count;
-  const NearQuery* near = fold ? fold->near : nullptr;
-  const int nq = near ? 2 : fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
+  const hipStream_t s = c.s;
+  const long n = c.n;
+  const NearQuery* near = c.near;
+  const size_t qbytes = c.qbytes, ob = (size_t)Q * (size_t)count;
   int32_t* which = fold && fold->terms ? fold->terms->which : nullptr;
-  const size_t qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255;
   const bool zero_copy = !on_device && ob * 8 <= kPinResultBytes;            // small host results: written into pinned memory, as search() does
   // idx, score and, asked for, `which` in a slot of its own; a together call: partner and partner_score in two slots behind score
   const size_t res_bytes = zero_copy ? (ob * (near ? 16 : which ? 12 : 8) + 255) & ~(size_t)255 : 0;
   ensure_pinned(h, qbytes + res_bytes + (size_t)(Q + (near ? 1 : 0)) * 4);   // the totals, and behind them the full length of a together call's list
-  unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes + res_bytes);
+  c.tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes + res_bytes);
   int* idx_out = idx; float* sc_out = score;
   int* which_out = which;
   int* partner_out = near ? near->partner : nullptr; float* pscore_out = near ? near->partner_score : nullptr;
@@ -1934,12 +1908,7 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   } else if (!on_device) {
     if (which) { ensure((void**)&h->which_dev, &h->which_dev_cap, ob * 4); which_out = h->which_dev; }
     if (want_partner) { ensure((void**)&h->near_dev, &h->near_dev_cap, ob * 8); partner_out = h->near_dev; pscore_out = reinterpret_cast<float*>(h->near_dev + ob); }
-    if (h->out_cap < ob) {
-      if (h->idx_dev) hipFree(h->idx_dev);
-      if (h->sc_dev) hipFree(h->sc_dev);
-      h->idx_dev = nullptr; h->sc_dev = nullptr; h->out_cap = 0;
-      CC_HIP(hipMalloc((void**)&h->idx_dev, ob * 4 + 256)); CC_HIP(hipMalloc((void**)&h->sc_dev, ob * 4 + 256)); h->out_cap = ob;
-    }
+    ensure_out(h, ob);
     idx_out = h->idx_dev; sc_out = h->sc_dev;
   }
   const size_t sel_bytes = (size_t)Q * kRankSel * sizeof(RankSel), hist_bytes = (size_t)Q * kRankSel * 256 * 4, cnt_bytes = (size_t)Q * kRankSel * 4;
@@ -1947,32 +1916,19 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
   RankSel* sel = reinterpret_cast<RankSel*>(h->rank_ws);
   unsigned* ghist = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes);
   unsigned* wcnt = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes + hist_bytes);
-  unsigned* tot_dev = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes + hist_bytes + cnt_bytes);
-  CC_HIP(hipMemsetAsync(tot_dev, 0, (size_t)Q * 4, s));
+  c.tot_dev = reinterpret_cast<unsigned*>(h->rank_ws + sel_bytes + hist_bytes + cnt_bytes);
+  CC_HIP(hipMemsetAsync(c.tot_dev, 0, (size_t)Q * 4, s));
   // answers the index can give from `start` on: at most one per row.  What lies behind them is padding whatever the scores are.
   const int64_t avail = std::max<int64_t>(0, std::min<int64_t>(count, (int64_t)n - start));
   if (avail < count)
     hipLaunchKernelGGL(rank_pad_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, sc_out, ob);
-  NearWs nws{};
-  if (near) { nws = near_ws(h); CC_HIP(hipMemsetAsync(nws.total, 0, 4, s)); }
-  if (n > 0) {
-    const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    if (fold) fold_scores(h, *fold, w, tracks, min_score, allowed_dev, on_device, s);
-    else {
-      upload_queries(h, q, Q, on_device, s);
-      compute_scores(h, Q, s);
-    }
-    rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
-    rank_select(h, Q, tracks, start, avail, count, sel, ghist, wcnt, idx_out, sc_out, s);
-  }
+  rank_scores(h, c, q, Q, min_score, allowed, n_groups, on_device, fold);
+  if (n > 0) rank_select(h, Q, c.tracks, start, avail, count, sel, ghist, wcnt, idx_out, sc_out, s);
   if (which)   // every entry of idx is written by now (an emit or the padding): one term byte per answer, -1 behind the last one
     hipLaunchKernelGGL(which_gather_kernel, dim3((unsigned)std::min<size_t>((ob + 255) / 256, 4096)), dim3(256), 0, s, idx_out, h->which_row, n, ob, which_out);
   CC_HIP(hipGetLastError());
   if (want_partner)   // the same for a together call: the partner of the row each answer names, from the fold's places (an empty index: all padding)
-    launch_near_gather(idx_out, h->near_pos, nws.L, n, ob, near->cap, partner_out, pscore_out, s);
-  if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
-  const bool want_np = near && near->n_partners;
-  if (want_np) CC_HIP(hipMemcpyAsync(tot_host + Q, nws.total, 4, hipMemcpyDeviceToHost, s));
+    launch_near_gather(idx_out, h->near_pos, c.nws.L, n, ob, near->cap, partner_out, pscore_out, s);
   if (!on_device && !zero_copy) {
     CC_HIP(hipMemcpyAsync(idx, h->idx_dev, ob * 4, hipMemcpyDeviceToHost, s));
     CC_HIP(hipMemcpyAsync(score, h->sc_dev, ob * 4, hipMemcpyDeviceToHost, s));
@@ -1980,14 +1936,12 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
     if (near && near->partner) CC_HIP(hipMemcpyAsync(near->partner, partner_out, ob * 4, hipMemcpyDeviceToHost, s));
     if (near && near->partner_score) CC_HIP(hipMemcpyAsync(near->partner_score, pscore_out, ob * 4, hipMemcpyDeviceToHost, s));
   }
-  if (!on_device || total || want_np) CC_HIP(hipStreamSynchronize(s));
+  rank_totals(c, Q, total, on_device);
   if (zero_copy) {
     memcpy(idx, idx_out, ob * 4); memcpy(score, sc_out, ob * 4); if (which) memcpy(which, which_out, ob * 4);
     if (near && near->partner) memcpy(near->partner, partner_out, ob * 4);
     if (near && near->partner_score) memcpy(near->partner_score, pscore_out, ob * 4);
   }
-  if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
-  if (want_np) *near->n_partners = (int64_t)tot_host[Q];
   CC_API_END
 }
 
@@ -1996,54 +1950,31 @@ int rank(cc_index* h, const float* q, int Q, int64_t start, int64_t count, float
 int timeline(cc_index* h, const float* q, int Q, float min_score, int flags, const uint8_t* allowed, int n_groups, const cc_row_filter* where,
              int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int on_device, void* stream, const FoldQuery* fold = nullptr) {
   CC_API_BEGIN
-  CC_CHECK(h && (q || fold) && counts, "null argument");
-  CC_CHECK(Q >= 1 && Q <= 65535, "Q must be in [1, 65535]");
-  CC_CHECK(min_score == min_score, "min_score is NaN");
-  CC_CHECK((flags & ~CC_RANK_TRACKS) == 0, "unknown flag bits");
-  CC_CHECK(!allowed || (n_groups > 0 && n_groups <= (1 << 24)), "bad group count");
+  RankCall c = rank_begin(h, q, Q, min_score, flags, allowed, n_groups, where, counts != nullptr, stream, fold);
   CC_CHECK(bin_seconds >= 1, "bin_seconds must be at least 1");
   CC_CHECK(n_bins >= 1 && n_bins <= 4096, "n_bins must be in [1, 4096]");
-  CC_CHECK(h->n < (1LL << 31), "ranking needs fewer than 2^31 rows");
-  const bool tracks = (flags & CC_RANK_TRACKS) != 0;
-  RowWhere w = make_where(h, where);
-  CC_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const long n = (long)h->n;
-  const NearQuery* near = fold ? fold->near : nullptr;
-  const int nq = near ? 2 : fold && fold->terms ? std::max(fold->terms->n_vec, 1) : Q;  // the queries that go through the pinned block
-  const size_t qbytes = ((size_t)nq * h->dim * 4 + 255) & ~(size_t)255, cbytes = (size_t)Q * n_bins * 4;
-  ensure_pinned(h, qbytes + (size_t)(Q + (near ? 1 : 0)) * 4);               // the totals, and behind them the full length of a together call's list
-  unsigned* tot_host = reinterpret_cast<unsigned*>(h->pin + qbytes);
+  const hipStream_t s = c.s;
+  const long n = c.n;
+  const size_t cbytes = (size_t)Q * n_bins * 4;
+  ensure_pinned(h, c.qbytes + (size_t)(Q + (c.near ? 1 : 0)) * 4);           // the totals, and behind them the full length of a together call's list
+  c.tot_host = reinterpret_cast<unsigned*>(h->pin + c.qbytes);
   ensure((void**)&h->rank_ws, &h->rank_ws_cap, (size_t)Q * 4 + cbytes);     // per query the total, then (host caller) the bins
-  unsigned* tot_dev = reinterpret_cast<unsigned*>(h->rank_ws);
-  unsigned* cnt_dev = on_device ? counts : tot_dev + Q;
-  CC_HIP(hipMemsetAsync(tot_dev, 0, (size_t)Q * 4, s));
+  c.tot_dev = reinterpret_cast<unsigned*>(h->rank_ws);
+  unsigned* cnt_dev = on_device ? counts : c.tot_dev + Q;
+  CC_HIP(hipMemsetAsync(c.tot_dev, 0, (size_t)Q * 4, s));
   CC_HIP(hipMemsetAsync(cnt_dev, 0, cbytes, s));
-  NearWs nws{};
-  if (near) { nws = near_ws(h); CC_HIP(hipMemsetAsync(nws.total, 0, 4, s)); }
+  rank_scores(h, c, q, Q, min_score, allowed, n_groups, on_device, fold);
   if (n > 0) {
-    const unsigned char* allowed_dev = upload_allowed(h, allowed, n_groups, s);
-    if (fold) fold_scores(h, *fold, w, tracks, min_score, allowed_dev, on_device, s);
-    else {
-      upload_queries(h, q, Q, on_device, s);
-      compute_scores(h, Q, s);
-    }
-    rank_keys(h, Q, tracks, min_score, allowed_dev, w, tot_dev, s);
     const dim3 grid((unsigned)((n + kRankRows - 1) / kRankRows), Q);
     const size_t lds = (size_t)n_bins * 4;
-    if (tracks) hipLaunchKernelGGL(timeline_kernel<true>, grid, dim3(256), lds, s, h->key_hi, n, h->trk, h->best, std::max(h->n_slots, 1), h->ts,
-                                   (long long)t0, (unsigned)bin_seconds, n_bins, cnt_dev);
+    if (c.tracks) hipLaunchKernelGGL(timeline_kernel<true>, grid, dim3(256), lds, s, h->key_hi, n, h->trk, h->best, std::max(h->n_slots, 1), h->ts,
+                                     (long long)t0, (unsigned)bin_seconds, n_bins, cnt_dev);
     else hipLaunchKernelGGL(timeline_kernel<false>, grid, dim3(256), lds, s, h->key_hi, n, nullptr, nullptr, 0, h->ts,
                             (long long)t0, (unsigned)bin_seconds, n_bins, cnt_dev);
   }
   CC_HIP(hipGetLastError());
-  if (total) CC_HIP(hipMemcpyAsync(tot_host, tot_dev, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
-  const bool want_np = near && near->n_partners;
-  if (want_np) CC_HIP(hipMemcpyAsync(tot_host + Q, nws.total, 4, hipMemcpyDeviceToHost, s));
   if (!on_device) CC_HIP(hipMemcpyAsync(counts, cnt_dev, cbytes, hipMemcpyDeviceToHost, s));
-  if (!on_device || total || want_np) CC_HIP(hipStreamSynchronize(s));
-  if (total) for (int i = 0; i < Q; ++i) total[i] = (int64_t)tot_host[i];
-  if (want_np) *near->n_partners = (int64_t)tot_host[Q];
+  rank_totals(c, Q, total, on_device);
   CC_API_END
 }
 
@@ -2100,9 +2031,9 @@ int cc_index_fetch_rows(cc_index* h, const int64_t* rows, int n, float* out, int
 int cc_index_rank_like(cc_index* h, const int64_t* rows, int n_rows, int64_t start, int64_t count, float min_score, int flags,
                        const uint8_t* allowed, int n_groups, const cc_row_filter* where,
                        int32_t* idx, float* score, int64_t* total, int on_device, void* stream) {
-  LikeQuery like{};
-  if (const int rc = like_check(h, rows, n_rows, flags, &like)) return rc;
-  const FoldQuery fold{&like, nullptr};
+  TermsQuery tq{};
+  if (const int rc = like_check(h, rows, n_rows, flags, &tq)) return rc;
+  const FoldQuery fold{&tq, nullptr};
   return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &fold);
 }
 
@@ -2111,7 +2042,7 @@ int cc_index_rank_terms(cc_index* h, const float* q, int n_vec, const int64_t* r
                         int32_t* idx, float* score, int32_t* which, int64_t* total, int on_device, void* stream) {
   TermsQuery tq{};
   if (const int rc = terms_check(h, q, n_vec, rows, n_rows, terms, combine, flags, which, &tq)) return rc;
-  const FoldQuery fold{nullptr, &tq};
+  const FoldQuery fold{&tq, nullptr};
   return rank(h, nullptr, 1, start, count, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, idx, score, total, on_device, stream, &fold);
 }
 
@@ -2120,7 +2051,7 @@ int cc_index_timeline_terms(cc_index* h, const float* q, int n_vec, const int64_
                             uint32_t* counts, int64_t* total, int on_device, void* stream) {
   TermsQuery tq{};
   if (const int rc = terms_check(h, q, n_vec, rows, n_rows, terms, combine, flags, nullptr, &tq)) return rc;
-  const FoldQuery fold{nullptr, &tq};
+  const FoldQuery fold{&tq, nullptr};
   return timeline(h, nullptr, 1, min_score, flags & CC_RANK_TRACKS, allowed, n_groups, where, t0, bin_seconds, n_bins, counts, total, on_device, stream, &fold);
 }
 
@@ -2132,7 +2063,7 @@ int cc_index_rank_near(cc_index* h, const float* qa, int64_t row_a, const float*
                        int on_device, void* stream) {
   NearQuery nq{};
   if (const int rc = near_check(h, qa, row_a, qb, row_b, within, max_partners, cut_b, value, flags, where_b, partner, partner_score, n_partners, &nq)) return rc;
-  const FoldQuery fold{nullptr, nullptr, &nq};
+  const FoldQuery fold{nullptr, &nq};
   return rank(h, nullptr, 1, start, count, min_score, flags, allowed, n_groups, where_a, idx, score, total, on_device, stream, &fold);
 }
 
@@ -2141,7 +2072,7 @@ int cc_index_timeline_near(cc_index* h, const float* qa, int64_t row_a, const fl
                            int32_t t0, int32_t bin_seconds, int n_bins, uint32_t* counts, int64_t* total, int64_t* n_partners, int on_device, void* stream) {
   NearQuery nq{};
   if (const int rc = near_check(h, qa, row_a, qb, row_b, within, max_partners, cut_b, value, flags, where_b, nullptr, nullptr, n_partners, &nq)) return rc;
-  const FoldQuery fold{nullptr, nullptr, &nq};
+  const FoldQuery fold{nullptr, &nq};
   return timeline(h, nullptr, 1, min_score, flags, allowed, n_groups, where_a, t0, bin_seconds, n_bins, counts, total, on_device, stream, &fold);
 }
 

@@ -244,8 +244,8 @@ __device__ __forceinline__ void decode_i8_piece(const uint4 v, float s, float4* 
 // ---- which rows compete (index.hip's rankings, index_digest.hip's selection) -----------------------------------------------------
 constexpr int kRowNoTs = INT32_MIN;                      // CC_ROW_NO_TS
 // cc_row_filter as the kernels take it (by value, in the kernel arguments): a null column = no filter on that attribute.
-// dead: one byte per row, non-zero = the row is out of the running (cc_index_rank_like's exclusion, written by like_fold_kernel;
-// cc_index_rank_terms' REQUIRE / REJECT terms and exclusion, written by terms_fold_kernel); null everywhere else.
+// dead: one byte per row, non-zero = the row is out of the running (cc_index_rank_like's exclusion and cc_index_rank_terms' REQUIRE /
+// REJECT terms and exclusion, both written by terms_fold_kernel); null everywhere else.
 struct RowWhere { const int* ts; const int* cls; int ts_min, ts_max; unsigned long long m0, m1, m2, m3; const unsigned char* dead; };
 #if defined(__HIPCC__)
 __device__ __forceinline__ bool row_allowed(const int* __restrict__ grp, const unsigned char* __restrict__ allowed, int n_allowed, long r) {

@@ -21,6 +21,7 @@ from . import _lib
 from .alerts import AlertBook, WatchList  # noqa: F401  (re-exported: the alert surface belongs to this module's ObjectFinder)
 from .arch import CLIP_L14, ClipArch
 from .helpers import Tensor, as_numpy
+from .index import EmbeddingIndex, row_filter  # noqa: F401  (re-exported: this module's ObjectFinder is built on them)
 from .weights import load_safetensors
 from .yolov9 import DTYPES
 
@@ -139,32 +140,6 @@ class OpenCLIP:
             pass
 
 
-def row_filter(ts_range=None, classes=None) -> Optional["_lib.RowFilter"]:
-    """The row filter of `rank` / `rank_device` / `timeline` (cc_row_filter), or None when neither argument is given.
-    ts_range: (first, last) seconds, inclusive at both ends, either may be None for "open"; classes: the class ids that
-    pass, each in [0, 255].  A row without the attribute never passes a filter on it.  An empty window (first > last, or
-    outside int32) and an empty class set are errors: they could only answer nothing."""
-    if ts_range is None and classes is None:
-        return None
-    f = _lib.RowFilter()
-    if ts_range is not None:
-        lo, hi = ts_range
-        lo, hi = (-(1 << 31) if lo is None else int(lo)), ((1 << 31) - 1 if hi is None else int(hi))
-        if lo > hi or lo >= 1 << 31 or hi < -(1 << 31):
-            raise ValueError(f"ts_range ({lo}, {hi}) is empty")
-        f.use_ts, f.ts_min, f.ts_max = 1, max(lo, -(1 << 31)), min(hi, (1 << 31) - 1)
-    if classes is not None:
-        ids = sorted({int(c) for c in np.asarray(classes).reshape(-1).tolist()})
-        if not ids:
-            raise ValueError("classes is empty")
-        if ids[0] < 0 or ids[-1] > 255:
-            raise ValueError("classes: ids in [0, 255]")
-        f.use_cls = 1
-        for c in ids:
-            f.cls_mask[c >> 6] |= 1 << (c & 63)
-    return f
-
-
 class Term(NamedTuple):
     """One term of `ObjectFinder.compound`: exactly one of text (a query string, encoded by the CLIP text tower), path (a stored
     crop, by its key or the endpoint's form, as `similar` takes it) or embedding (a vector of the index's width).  role "rank": the
@@ -191,734 +166,6 @@ def pick_track_rows(row: int, members) -> np.ndarray:
     others = m[m != int(row)]
     at = np.linspace(0, others.size - 1, _lib.LIKE_MAX_ROWS - 1).round().astype(np.int64)
     return np.sort(np.r_[others[at], np.int64(row)])
-
-
-class EmbeddingIndex:
-    """Device-resident (N,dim) matrix with scan + top-k (cc_index_*).  storage "f32" (exact f32 scores), "bf16" (half the
-    bytes per scan, scores within ~1e-3 for unit vectors; dim % 256 == 0 and at most 40960) or "i8" (int8 codes with one f32 scale per 32 elements: dim * 9 / 8
-    bytes a row, scores within ~1e-3 as well; include/clearcam_hip.h has the rule).  `capacity` is the initial allocation; the
-    matrix grows.
-
-    Batches on "i8" rows: fewer than 18 queries are scored by scan passes, bit-identical to single queries; from 18 on (dim <= 4096)
-    one MFMA launch scores the whole batch, the same exact products summed in another order (last-bit differences, the same error
-    bound).  Either way a (query, row) score depends on that pair alone, equal rows tie exactly and ties break by row id.
-    `last_scores_path()` tells which kernel ran."""
-
-    STORAGE = {"f32": 0, "bf16": 2, "i8": 8}           # name -> the `storage` argument of cc_index_create_ex
-
-    def __init__(self, dim: int = 768, capacity: int = 1 << 20, device: int = 0, storage: str = "f32"):
-        self.dim, self.device, self.storage = dim, device, storage
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().cc_index_create_ex(C.byref(self._h), dim, max(int(capacity), 1), device, self.STORAGE[storage]))
-
-    @property
-    def capacity(self) -> int:
-        c = C.c_int64()
-        _lib.check(_lib.lib().cc_index_info(self._h, C.byref(c), None, None))
-        return c.value
-
-    def __len__(self) -> int:
-        n = C.c_int64()
-        _lib.check(_lib.lib().cc_index_size(self._h, C.byref(n)))
-        return n.value
-
-    row_filter = staticmethod(row_filter)
-
-    def add(self, emb, groups=None, tracks=None, ts=None, classes=None) -> None:
-        """Append rows: (n,dim) / (n,1,dim) / (dim,) float32, host array or CUDA torch tensor.  Rows of any other width are
-        rejected (a 512-d face row must never land in the 768-d crop matrix).  groups: one int per row (search filter unit).
-        tracks: one slot per row, a dense number per distinct track id or -1 for a crop without one (`search_tracks`).
-        ts: one int32 per row, the seconds into the day's recording, _lib.ROW_NO_TS for a row without; classes: one detector
-        class in [0, 255] per row, -1 for a row without.  Not given: no row has the attribute (it then passes no filter on it)."""
-        on_dev = bool(getattr(emb, "is_cuda", False))
-        if on_dev:
-            a = emb.contiguous().float()
-            if a.shape[-1] != self.dim:
-                raise ValueError(f"expected {self.dim}-d rows, got {tuple(a.shape)}")
-            a = a.reshape(-1, self.dim)
-        else:
-            a = np.asarray(as_numpy(emb), dtype=np.float32)
-            if a.ndim == 0 or a.shape[-1] != self.dim:
-                raise ValueError(f"expected {self.dim}-d rows, got {a.shape}")
-            a = np.ascontiguousarray(a.reshape(-1, self.dim))
-        g = None
-        if groups is not None:
-            g = np.ascontiguousarray(np.asarray(groups, np.int32).reshape(-1))
-            if g.shape[0] != a.shape[0] or (g.size and (g.min() < 0 or g.max() >= 1 << 24)):
-                raise ValueError("groups: one id in [0, 2^24) per row")
-        t = None
-        if tracks is not None:
-            t = np.ascontiguousarray(np.asarray(tracks, np.int32).reshape(-1))
-            if t.shape[0] != a.shape[0] or (t.size and (t.min() < -1 or t.max() >= 1 << 24)):
-                raise ValueError("tracks: one slot in [0, 2^24) or -1 per row")
-        s = c = None
-        if ts is not None:
-            s64 = np.asarray(ts, np.int64).reshape(-1)
-            if s64.shape[0] != a.shape[0] or (s64.size and (s64.min() < -(1 << 31) or s64.max() >= 1 << 31)):
-                raise ValueError("ts: one int32 per row")
-            s = np.ascontiguousarray(s64.astype(np.int32))
-        if classes is not None:
-            c = np.ascontiguousarray(np.asarray(classes, np.int32).reshape(-1))
-            if c.shape[0] != a.shape[0] or (c.size and (c.min() < -1 or c.max() > 255)):
-                raise ValueError("classes: one id in [0, 255] or -1 per row")
-        _lib.check(_lib.lib().cc_index_add_described(self._h, _lib.ptr(a), a.shape[0], int(on_dev), _lib.ptr(g) if g is not None else None,
-                                                     _lib.ptr(t) if t is not None else None, _lib.ptr(s) if s is not None else None,
-                                                     _lib.ptr(c) if c is not None else None))
-
-    def row_info(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(ts (N,) int32, class (N,) int32) of every row as the device holds them (cc_index_row_info)."""
-        n = len(self)
-        ts, c = np.empty(n, np.int32), np.empty(n, np.int32)
-        _lib.check(_lib.lib().cc_index_row_info(self._h, 0, n, _lib.ptr(ts), _lib.ptr(c)))
-        return ts, c
-
-    def remove(self, rows) -> int:
-        """Take rows out; the survivors keep their order and are renumbered densely (new id = survivors before the row), so
-        every search answers as an index built from the survivors would.  rows: a bool / uint8 mask with one entry per row
-        (non-zero removes), or an array of row numbers.  Compaction in place on the device (cc_index_remove_rows): capacity
-        and track slots stay.  Returns the number of rows removed."""
-        a = np.asarray(rows)
-        if a.dtype == np.bool_ or a.dtype == np.uint8:
-            mask = np.ascontiguousarray(a.reshape(-1), dtype=np.uint8)
-        else:
-            ids = a.reshape(-1).astype(np.int64)
-            n = len(self)
-            if ids.size and (ids.min() < 0 or ids.max() >= n):
-                raise IndexError(f"row numbers must be in [0, {n})")
-            mask = np.zeros(n, np.uint8)
-            mask[ids] = 1
-        removed = C.c_int64()
-        _lib.check(_lib.lib().cc_index_remove_rows(self._h, _lib.ptr(mask), int(mask.size), C.byref(removed)))
-        return removed.value
-
-    def remove_groups(self, drop) -> int:
-        """`remove` for every row whose group id g has drop[g] != 0 (uint8, one byte per group; groups past the end of `drop`
-        stay).  The keep flags are computed on the device from the stored group ids: no per-row work on the host."""
-        d = np.ascontiguousarray(np.asarray(drop).reshape(-1), dtype=np.uint8)
-        if d.size == 0:
-            return 0
-        removed = C.c_int64()
-        _lib.check(_lib.lib().cc_index_remove_groups(self._h, _lib.ptr(d), int(d.size), C.byref(removed)))
-        return removed.value
-
-    def scores(self, q) -> np.ndarray:
-        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
-        out = np.empty((qa.shape[0], len(self)), np.float32)
-        if len(self):
-            _lib.check(_lib.lib().cc_index_scores(self._h, _lib.ptr(qa), qa.shape[0], _lib.ptr(out), 0, None))
-        return out
-
-    def last_scores_path(self) -> int:
-        """Which kernel produced the scores of the last scoring call (scores / search* / rank) on this index: 0 scan passes,
-        1 the f32 / bf16 MFMA GEMM, 2 the int8 MFMA kernel (cc_index_last_path)."""
-        p = C.c_int()
-        _lib.check(_lib.lib().cc_index_last_path(self._h, C.byref(p)))
-        return p.value
-
-    def search(self, q, k: int, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
-        """(Q,dim) queries -> (idx (Q,k) int32, score (Q,k) f32), descending, ties by lower row id; -1/-inf past N.
-        allowed: optional uint8 array, one entry per group id — only rows of groups with a non-zero entry compete."""
-        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
-        idx = np.empty((qa.shape[0], k), np.int32)
-        sc = np.empty((qa.shape[0], k), np.float32)
-        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_search_groups(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
-                                                     0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 0, None))
-        return idx, sc
-
-    def search_tracks(self, q, k: int, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
-        """`search` with tracks as the answers (models/objects.py:378-390 on the device): among the allowed rows every track
-        slot counts once, with its best row (equal scores: the lower row), and rows of slot -1 count as themselves.  Descending
-        by score; equal scores: tracks by their first allowed row, then the slot-less rows by row id.  Fewer than k answers
-        leave -1/-inf at the end.  One call, exact for any data: no candidate list to widen."""
-        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
-        idx = np.empty((qa.shape[0], k), np.int32)
-        sc = np.empty((qa.shape[0], k), np.float32)
-        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_search_tracks(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
-                                                     0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 0, None))
-        return idx, sc
-
-    def search_tracks_device(self, q, k: int, allowed=None):
-        """`search_tracks` with the result left on the GPU, like `search_device` (allowed stays a host array)."""
-        return self._search_device("cc_index_search_tracks", q, k, allowed)
-
-    @staticmethod
-    def cut_f32(min_score) -> np.float32:
-        """The smallest float32 that is >= the caller's cut (a Python float; None: -inf, no cut).  Scores are float32 and the
-        reference tests `score < cut` in double, so `score >= cut_f32(cut)` in f32 keeps exactly what `not score < cut` keeps."""
-        if min_score is None:
-            return np.float32(-np.inf)
-        t = float(min_score)
-        with np.errstate(over="ignore"):
-            c = np.float32(t)
-        if float(c) < t:                                   # rounded down: one step up
-            c = np.nextafter(c, np.float32(np.inf))
-        return c
-
-    def rank(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
-             classes=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """Answers start .. start+count-1 of the WHOLE descending order -> (idx (Q,count) int32, score (Q,count) f32, total (Q,)
-        int64), at any depth and of any length, in one call (cc_index_rank).  tracks=True: the answers and their order are those of
-        `search_tracks`; False: every allowed row answers for itself, ordered as `search` orders them.  Only answers with
-        score >= min_score exist (`cut_f32` of the value given): ranks are counted among them and `total` is their number, so a
-        cut inside a run of equal scores keeps the whole run.  -1/-inf past the last answer.
-        ts_range / classes (`row_filter`): only rows that pass compete, and the call answers as an index built from those rows
-        alone would - a track is reduced among its passing rows and placed by its first passing one (cc_index_rank_where)."""
-        where = self.row_filter(ts_range, classes)
-        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
-        start, count = int(start), int(count)
-        if count < 1 or start < 0:
-            idx, sc = np.empty((1, 1), np.int32), np.empty((1, 1), np.float32)     # the library names the error
-        else:
-            idx, sc = np.empty((qa.shape[0], count), np.int32), np.empty((qa.shape[0], count), np.float32)
-        total = np.zeros(qa.shape[0], np.int64)
-        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        head = (self._h, _lib.ptr(qa), qa.shape[0], start, count, float(self.cut_f32(min_score)), 1 if tracks else 0,
-                _lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size))
-        tail = (_lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 0, None)
-        if where is None:
-            _lib.check(_lib.lib().cc_index_rank(*head, *tail))
-        else:
-            _lib.check(_lib.lib().cc_index_rank_where(*head, C.byref(where), *tail))
-        return idx, sc, total
-
-    def rank_device(self, q, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, with_total: bool = True,
-                    ts_range=None, classes=None):
-        """`rank` with idx / score left on the GPU like `search_tracks_device`.  `total` still comes back as a host array, which
-        costs one wait for the stream; with_total=False returns None in its place and waits for nothing."""
-        args = (int(start), int(count), float(self.cut_f32(min_score)), 1 if tracks else 0)
-        return self._search_device("cc_index_rank", q, int(count), allowed, args, with_total, self.row_filter(ts_range, classes))
-
-    # -- query by stored rows: the queries are rows of this matrix (cc_index_fetch_rows / cc_index_rank_like) ------------------------
-    LIKE_EXCLUDE = {None: 0, "rows": _lib.LIKE_EXCLUDE_ROWS, "track": _lib.LIKE_EXCLUDE_TRACK}
-
-    @staticmethod
-    def _row_numbers(rows) -> np.ndarray:
-        a = np.asarray(rows)
-        if a.size and a.dtype.kind not in "iu":
-            raise TypeError("row numbers must be integers")
-        return np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
-
-    def _run_stream(self, dev):
-        """(current torch stream, the stream to hand to the library).  torch's default stream has the handle 0, which the library
-        reads as "no stream given" (it then runs on the index's own stream, which nothing orders against torch): the work runs on a
-        side stream fenced by the current one instead; the caller fences the other side (`cur.wait_stream(run)`) behind its call."""
-        import torch
-        cur = run = torch.cuda.current_stream(dev)
-        if cur.cuda_stream == 0:
-            if getattr(self, "_side_stream", None) is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            run = self._side_stream
-            run.wait_stream(cur)
-        return cur, run
-
-    def fetch(self, rows, device_out: bool = False):
-        """What the index holds for `rows` (numbers in any order, repeats allowed, at least one), decoded -> (n, dim) float32:
-        f32 rows as they were added, bf16 rows as the bf16 values, i8 rows as code * scale.  One gather on the device
-        (cc_index_fetch_rows).  device_out: a CUDA torch tensor on the current torch stream, nothing waited for.  A number outside
-        the index is an error."""
-        ids = self._row_numbers(rows)
-        if not device_out:
-            out = np.empty((ids.size, self.dim), np.float32)
-            _lib.check(_lib.lib().cc_index_fetch_rows(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _lib.ptr(out), 0, None))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device)
-        out = torch.empty((ids.size, self.dim), dtype=torch.float32, device=dev)
-        cur, run = self._run_stream(dev)
-        _lib.check(_lib.lib().cc_index_fetch_rows(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _lib.ptr(out), 1, C.c_void_p(run.cuda_stream)))
-        if run is not cur:
-            cur.wait_stream(run)
-        return out
-
-    def _rank_like(self, rows, start, count, allowed, min_score, tracks, exclude, where, out, total, on_device, stream):
-        if exclude not in self.LIKE_EXCLUDE:
-            raise ValueError('exclude: None, "rows" or "track"')
-        ids = self._row_numbers(rows)
-        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        flags = (_lib.RANK_TRACKS if tracks else 0) | self.LIKE_EXCLUDE[exclude]
-        _lib.check(_lib.lib().cc_index_rank_like(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), int(start), int(count),
-                                                 float(self.cut_f32(min_score)), flags, _lib.ptr(al) if al is not None else None,
-                                                 0 if al is None else int(al.size), C.byref(where) if where is not None else None,
-                                                 _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(total) if total is not None else None, on_device, stream))
-
-    def rank_like(self, rows, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, exclude=None, ts_range=None,
-                  classes=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """`rank` for ONE query made of 1 .. 64 stored rows ("more like this crop", or like any crop of this track) -> (idx
-        (1, count) int32, score (1, count) f32, total (1,) int64).  A row's score is its best score against any of `rows`
-        (scored as `scores(fetch(rows))` scores them, by the same kernel route), and that vector is ranked exactly as `rank`
-        ranks a query's: same answers per track, tie rules, cut, filters and padding.  exclude="rows": the query rows do not
-        compete; "track": no row of their directory group and track slot does (they must share one group and one slot >= 0).
-        A copy of an excluded crop elsewhere still answers, with the same score.  No embedding leaves or enters the GPU
-        (cc_index_rank_like)."""
-        where = self.row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        shape = (1, count) if count >= 1 and start >= 0 else (1, 1)                 # the library names the error
-        idx, sc, total = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
-        self._rank_like(rows, start, count, allowed, min_score, tracks, exclude, where, (idx, sc), total, 0, None)
-        return idx, sc, total
-
-    def rank_like_device(self, rows, start: int, count: int, allowed=None, min_score=None, tracks: bool = True, exclude=None,
-                         with_total: bool = True, ts_range=None, classes=None):
-        """`rank_like` with idx / score left on the GPU, as `rank_device` leaves them; with_total=False waits for nothing."""
-        import torch
-        where = self.row_filter(ts_range, classes)
-        dev = torch.device("cuda", self.device)
-        k = max(int(count), 1)
-        idx = torch.empty((1, k), dtype=torch.int32, device=dev)
-        sc = torch.empty((1, k), dtype=torch.float32, device=dev)
-        total = np.zeros(1, np.int64) if with_total else None
-        cur, run = self._run_stream(dev)
-        self._rank_like(rows, start, count, allowed, min_score, tracks, exclude, where, (idx, sc), total, 1, C.c_void_p(run.cuda_stream))
-        if run is not cur:
-            cur.wait_stream(run)
-        return idx, sc, total
-
-    # -- compound search: weighted, all-of and negative terms in one ranking (cc_index_rank_terms / cc_index_timeline_terms) -----------
-    TERM_ROLE = {"rank": _lib.TERM_RANK, "require": _lib.TERM_REQUIRE, "reject": _lib.TERM_REJECT}
-    COMBINE = {"max": _lib.COMBINE_MAX, "min": _lib.COMBINE_MIN, "sum": _lib.COMBINE_SUM}
-
-    def _terms(self, q, rows, roles, weights, cuts, combine, exclude, tracks):
-        """The query side of a compound call, checked -> (vectors (n_vec, dim) f32 or None, row numbers int64, (T,) _lib.Term array,
-        the combine rule, the flags).  Terms 0 .. n_vec-1 are the vectors, the stored rows follow; roles / weights / cuts have one
-        entry per term in that order (roles None: every term ranks; weights None: 1.0; a cut None: 0, read only for "require" /
-        "reject", where it is `cut_f32` of the value given)."""
-        if exclude not in self.LIKE_EXCLUDE:
-            raise ValueError('exclude: None, "rows" or "track"')
-        if combine not in self.COMBINE:
-            raise ValueError('combine: "max", "min" or "sum"')
-        qa = None
-        if q is not None:
-            if bool(getattr(q, "is_cuda", False)):
-                qa = q.contiguous().float().reshape(-1, self.dim)
-            else:
-                qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
-        ids = self._row_numbers([] if rows is None else rows)
-        n_vec = 0 if qa is None else int(qa.shape[0])
-        T = n_vec + int(ids.size)
-        roles = ["rank"] * T if roles is None else list(roles)
-        weights = [1.0] * T if weights is None else list(weights)
-        cuts = [None] * T if cuts is None else list(cuts)
-        if not (len(roles) == len(weights) == len(cuts) == T):
-            raise ValueError(f"roles, weights and cuts need one entry per term ({T})")
-        terms = (_lib.Term * max(T, 1))()
-        for t, (role, wt, cut) in enumerate(zip(roles, weights, cuts)):
-            if role not in self.TERM_ROLE:
-                raise ValueError('role: "rank", "require" or "reject"')
-            terms[t].role, terms[t].weight = self.TERM_ROLE[role], float(wt)
-            terms[t].cut = 0.0 if cut is None else float(self.cut_f32(cut))
-        return qa, ids, terms, self.COMBINE[combine], (_lib.RANK_TRACKS if tracks else 0) | self.LIKE_EXCLUDE[exclude]
-
-    def _rank_terms(self, spec, start, count, allowed, min_score, where, out, which, total, on_device, stream):
-        qa, ids, terms, combine, flags = spec
-        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_rank_terms(self._h, _lib.ptr(qa), 0 if qa is None else int(qa.shape[0]),
-                                                  ids.ctypes.data_as(C.POINTER(C.c_int64)) if ids.size else None, int(ids.size), terms, combine,
-                                                  int(start), int(count), float(self.cut_f32(min_score)), flags, _lib.ptr(al) if al is not None else None,
-                                                  0 if al is None else int(al.size), C.byref(where) if where is not None else None,
-                                                  _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(which), _lib.ptr(total) if total is not None else None,
-                                                  on_device, stream))
-
-    def rank_terms(self, q=None, rows=None, roles=None, weights=None, cuts=None, combine: str = "max", start: int = 0, count: int = 100,
-                   allowed=None, min_score=None, tracks: bool = True, exclude=None, ts_range=None, classes=None, which: bool = False):
-        """`rank` for ONE compound question of up to 64 terms -> (idx (1, count) int32, score (1, count) f32, total (1,) int64[, which
-        (1, count) int32]).  The terms are the vectors `q` ((n_vec, dim), e.g. text embeddings) followed by the stored rows `rows`,
-        scored in one batch as `scores(np.vstack([q, fetch(rows)]))` scores them.  roles[t]: "rank" - the term contributes to the
-        ranking value through `combine` ("max" / "min" of the rank terms' scores, or "sum": the float32 sum of weights[t] * score in
-        term order, negative weights allowed); "require" - a row competes only if the term scores it >= cuts[t]; "reject" - a row
-        scored >= cuts[t] does not compete ("white van, but not this one").  The value vector is ranked exactly as `rank` ranks a
-        query's among the rows left: same answers per track (reduced among the surviving rows, placed by the first of them), tie
-        rules, cut, filters and padding.  exclude="rows" / "track": as in `rank_like`, for the stored rows that are rank terms.  A
-        copy of a rejected crop elsewhere is rejected with it; a copy of an excluded one still answers.  which=True: per answer
-        the term that made its value (max / min: the lowest-numbered one attaining it; sum: the one with the largest product),
-        -1 past the last answer (cc_index_rank_terms)."""
-        spec = self._terms(q, rows, roles, weights, cuts, combine, exclude, tracks)
-        where = self.row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        shape = (1, count) if count >= 1 and start >= 0 else (1, 1)                 # the library names the error
-        idx, sc, total = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
-        wh = np.empty(shape, np.int32) if which else None
-        if spec[0] is not None and not isinstance(spec[0], np.ndarray):
-            spec = (spec[0].cpu().numpy(),) + spec[1:]
-        self._rank_terms(spec, start, count, allowed, min_score, where, (idx, sc), wh, total, 0, None)
-        return (idx, sc, total, wh) if which else (idx, sc, total)
-
-    def rank_terms_device(self, q=None, rows=None, roles=None, weights=None, cuts=None, combine: str = "max", start: int = 0, count: int = 100,
-                          allowed=None, min_score=None, tracks: bool = True, exclude=None, with_total: bool = True, ts_range=None, classes=None,
-                          which: bool = False):
-        """`rank_terms` with idx / score (and which) left on the GPU, as `rank_like_device` leaves them, on the current torch stream
-        (`distinct_device` can run behind it); with_total=False returns None for the total and waits for nothing."""
-        import torch
-        spec = self._terms(q, rows, roles, weights, cuts, combine, exclude, tracks)
-        where = self.row_filter(ts_range, classes)
-        dev = torch.device("cuda", self.device)
-        if isinstance(spec[0], np.ndarray):                                         # on_device: the vectors are a device pointer too
-            spec = (torch.as_tensor(spec[0]).to(dev),) + spec[1:]
-        k = max(int(count), 1)
-        idx = torch.empty((1, k), dtype=torch.int32, device=dev)
-        sc = torch.empty((1, k), dtype=torch.float32, device=dev)
-        wh = torch.empty((1, k), dtype=torch.int32, device=dev) if which else None
-        total = np.zeros(1, np.int64) if with_total else None
-        cur, run = self._run_stream(dev)
-        self._rank_terms(spec, start, count, allowed, min_score, where, (idx, sc), wh, total, 1, C.c_void_p(run.cuda_stream))
-        if run is not cur:
-            cur.wait_stream(run)
-            if spec[0] is not None:
-                spec[0].record_stream(run)
-        return (idx, sc, total, wh) if which else (idx, sc, total)
-
-    def timeline_terms(self, t0: int, bin_seconds: int, n_bins: int, q=None, rows=None, roles=None, weights=None, cuts=None, combine: str = "max",
-                       allowed=None, min_score=None, tracks: bool = True, exclude=None, ts_range=None, classes=None) -> Tuple[np.ndarray, np.ndarray]:
-        """How the answers of `rank_terms` (same terms and arguments) spread over time -> (counts (1, n_bins) int64, total (1,) int64),
-        binned as `timeline` bins them; `total` equals `rank_terms`' total (cc_index_timeline_terms)."""
-        qa, ids, terms, comb, flags = self._terms(q, rows, roles, weights, cuts, combine, exclude, tracks)
-        if qa is not None and not isinstance(qa, np.ndarray):
-            qa = qa.cpu().numpy()
-        where = self.row_filter(ts_range, classes)
-        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
-        if not -(1 << 31) <= t0 < 1 << 31 or not -(1 << 31) <= bin_seconds < 1 << 31 or not -(1 << 31) <= n_bins < 1 << 31:
-            raise ValueError("t0, bin_seconds and n_bins must fit in int32")
-        counts = np.zeros((1, min(max(n_bins, 1), 4096)), np.uint32)               # outside [1, 4096]: the library names the error
-        total = np.zeros(1, np.int64)
-        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_timeline_terms(self._h, _lib.ptr(qa), 0 if qa is None else int(qa.shape[0]),
-                                                      ids.ctypes.data_as(C.POINTER(C.c_int64)) if ids.size else None, int(ids.size), terms, comb,
-                                                      float(self.cut_f32(min_score)), flags, _lib.ptr(al) if al is not None else None,
-                                                      0 if al is None else int(al.size), C.byref(where) if where is not None else None,
-                                                      t0, bin_seconds, n_bins, _lib.ptr(counts), _lib.ptr(total), 0, None))
-        return counts.astype(np.int64), total
-
-    # -- together: rows with a partner nearby in time (cc_index_rank_near / cc_index_timeline_near) ----------------------------------------
-    def _near_side(self, x, device: bool):
-        """One side of a together call -> (vector or None, row number or -1): an int is a stored row, anything else a (dim,) vector
-        (a numpy array for a host call, a CUDA tensor for a device call)."""
-        if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
-            return None, int(x)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if not bool(getattr(x, "is_cuda", False)):
-                x = torch.as_tensor(np.ascontiguousarray(as_numpy(x), dtype=np.float32)).to(dev)
-            v = x.contiguous().float().reshape(-1)
-        else:
-            v = np.ascontiguousarray(as_numpy(x), dtype=np.float32).reshape(-1)
-        if int(v.shape[0]) != self.dim:
-            raise ValueError(f"a side of a together call is one vector of {self.dim} floats or one stored row")
-        return v, -1
-
-    def _near_question(self, a, b, within, partners, cut_b, value, min_score, tracks, device: bool):
-        """The question of a together call, checked -> the arguments h .. flags of cc_index_rank_near without start / count, and the
-        vectors to keep alive"""
-        if value not in _lib.NEAR_VALUE:
-            raise ValueError('value: "a" or "min"')
-        within, partners = int(within), int(partners)
-        if not -(1 << 31) <= within < 1 << 31 or not -(1 << 31) <= partners < 1 << 31:
-            raise ValueError("within and partners must fit in int32")
-        (va, ra), (vb, rb) = self._near_side(a, device), self._near_side(b, device)
-        head = (self._h, _lib.ptr(va), ra, _lib.ptr(vb), rb, within, partners, float(self.cut_f32(cut_b)), _lib.NEAR_VALUE[value])
-        return head, (float(self.cut_f32(min_score)), _lib.RANK_TRACKS if tracks else 0), (va, vb)
-
-    def _near_filters(self, allowed, where_a, where_b):
-        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        return (_lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size),
-                C.byref(where_a) if where_a is not None else None, C.byref(where_b) if where_b is not None else None)
-
-    def rank_near(self, a, b, within, start: int = 0, count: int = 100, partners: int = _lib.NEAR_DEFAULT_PARTNERS, cut_b=None, value: str = "min",
-                  allowed=None, min_score=None, tracks: bool = True, ts_range=None, classes=None, b_ts_range=None, b_classes=None):
-        """`rank` for the rows of question `a` that have a partner - an answer of question `b` - within `within` seconds in the same
-        group -> (idx (1, count) int32, score (1, count) f32, total (1,) int64, partner (1, count) int32, partner_score (1, count) f32,
-        n_partners int).  `a` / `b`: a (dim,) vector or an int, a stored row.  The partner list is the first `partners` (at most 16384)
-        answers of an ungrouped `rank` of `b` with the cut `cut_b` and the filter b_ts_range / b_classes, among rows that have a ts;
-        n_partners is its length without the cap.  A row's partner is the first entry of that list - the best-scoring one - that is
-        another row of the same group, at most `within` seconds away (64-bit difference) and not a crop of the row's own track; a row
-        without one does not compete.  value "a": the ranking value is `a`'s score; "min": the smaller of that and the partner's
-        score for `b`.  Everything else - answers per track, tie rules, `min_score` (on the value), ts_range / classes (for `a`),
-        `allowed` (for both), padding - is `rank`'s.  partner / partner_score: per answer the partner's row and its score for `b`, -1 /
-        -inf past the last answer (cc_index_rank_near)."""
-        head, tail, _keep = self._near_question(a, b, within, partners, cut_b, value, min_score, tracks, False)
-        wa, wb = self.row_filter(ts_range, classes), self.row_filter(b_ts_range, b_classes)
-        start, count = int(start), int(count)
-        shape = (1, count) if count >= 1 and start >= 0 else (1, 1)                 # the library names the error
-        idx, sc, total = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
-        pr, ps, n_partners = np.empty(shape, np.int32), np.empty(shape, np.float32), np.zeros(1, np.int64)
-        _lib.check(_lib.lib().cc_index_rank_near(*head, start, count, *tail, *self._near_filters(allowed, wa, wb), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(pr),
-                                                 _lib.ptr(ps), _lib.ptr(total), _lib.ptr(n_partners), 0, None))
-        return idx, sc, total, pr, ps, int(n_partners[0])
-
-    def rank_near_device(self, a, b, within, start: int = 0, count: int = 100, partners: int = _lib.NEAR_DEFAULT_PARTNERS, cut_b=None, value: str = "min",
-                         allowed=None, min_score=None, tracks: bool = True, with_total: bool = True, ts_range=None, classes=None, b_ts_range=None,
-                         b_classes=None):
-        """`rank_near` with idx / score / partner / partner_score left on the GPU, as `rank_device` leaves them, on the current torch
-        stream; with_total=False returns None for total and n_partners and waits for nothing."""
-        import torch
-        head, tail, keep = self._near_question(a, b, within, partners, cut_b, value, min_score, tracks, True)
-        wa, wb = self.row_filter(ts_range, classes), self.row_filter(b_ts_range, b_classes)
-        dev = torch.device("cuda", self.device)
-        k = max(int(count), 1)
-        idx, pr = (torch.empty((1, k), dtype=torch.int32, device=dev) for _ in range(2))
-        sc, ps = (torch.empty((1, k), dtype=torch.float32, device=dev) for _ in range(2))
-        total, n_partners = (np.zeros(1, np.int64), np.zeros(1, np.int64)) if with_total else (None, None)
-        cur, run = self._run_stream(dev)
-        _lib.check(_lib.lib().cc_index_rank_near(*head, int(start), int(count), *tail, *self._near_filters(allowed, wa, wb), _lib.ptr(idx), _lib.ptr(sc),
-                                                 _lib.ptr(pr), _lib.ptr(ps), _lib.ptr(total) if with_total else None,
-                                                 _lib.ptr(n_partners) if with_total else None, 1, C.c_void_p(run.cuda_stream)))
-        if run is not cur:
-            cur.wait_stream(run)
-            for v in keep:
-                if v is not None:
-                    v.record_stream(run)
-        return idx, sc, total, pr, ps, (int(n_partners[0]) if with_total else None)
-
-    def timeline_near(self, a, b, within, t0: int, bin_seconds: int, n_bins: int, partners: int = _lib.NEAR_DEFAULT_PARTNERS, cut_b=None,
-                      value: str = "min", allowed=None, min_score=None, tracks: bool = True, ts_range=None, classes=None, b_ts_range=None,
-                      b_classes=None):
-        """How the answers of `rank_near` (same question) spread over time -> (counts (1, n_bins) int64, total (1,) int64, n_partners
-        int), binned as `timeline` bins them; total and n_partners equal `rank_near`'s (cc_index_timeline_near)."""
-        head, tail, _keep = self._near_question(a, b, within, partners, cut_b, value, min_score, tracks, False)
-        wa, wb = self.row_filter(ts_range, classes), self.row_filter(b_ts_range, b_classes)
-        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
-        if not -(1 << 31) <= t0 < 1 << 31 or not -(1 << 31) <= bin_seconds < 1 << 31 or not -(1 << 31) <= n_bins < 1 << 31:
-            raise ValueError("t0, bin_seconds and n_bins must fit in int32")
-        counts = np.zeros((1, min(max(n_bins, 1), 4096)), np.uint32)               # outside [1, 4096]: the library names the error
-        total, n_partners = np.zeros(1, np.int64), np.zeros(1, np.int64)
-        _lib.check(_lib.lib().cc_index_timeline_near(*head, *tail, *self._near_filters(allowed, wa, wb), t0, bin_seconds, n_bins, _lib.ptr(counts),
-                                                     _lib.ptr(total), _lib.ptr(n_partners), 0, None))
-        return counts.astype(np.int64), total, int(n_partners[0])
-
-    # -- distinct answers: near-duplicate answers of a ranked list folded into the first of them (cc_index_gram / cc_index_distinct) ----
-    def gram(self, rows, device_out: bool = False):
-        """Pairwise similarities of stored rows -> (n, n) float32, out[i][j] = <fetch(rows)[i], fetch(rows)[j]> in f32, 1 <= n <= 1024
-        (cc_index_gram).  A pair's value depends on its two stored rows alone and the matrix equals its transpose bit for bit.
-        device_out: a CUDA torch tensor on the current torch stream, nothing waited for."""
-        ids = self._row_numbers(rows)
-        n = int(ids.size)
-        side = n if 1 <= n <= _lib.DISTINCT_MAX_DEPTH else 1                       # the library names the error
-        if not device_out:
-            out = np.empty((side, side), np.float32)
-            _lib.check(_lib.lib().cc_index_gram(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), n, _lib.ptr(out), 0, None))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device)
-        out = torch.empty((side, side), dtype=torch.float32, device=dev)
-        cur, run = self._run_stream(dev)
-        _lib.check(_lib.lib().cc_index_gram(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), n, _lib.ptr(out), 1, C.c_void_p(run.cuda_stream)))
-        if run is not cur:
-            cur.wait_stream(run)
-        return out
-
-    def distinct(self, idx, score=None, same_at: float = 0.9, start: int = 0, count=None):
-        """Thin ranked lists of row numbers -> (idx (Q, count) int32, score (Q, count) f32 or None, dups (Q, count) int32, total (Q,)
-        int64).  idx (Q, depth) or (depth,), depth <= 1024, Q <= 64, in ranked order (e.g. `rank(q, 0, depth)[0]`); entries < 0 or
-        >= len(self) are absent.  Walking a list in order, an entry is kept unless `gram` of it and an entry KEPT before it is
-        >= same_at (float32); a dropped entry is counted in `dups` of the first kept entry that matches it.  The kept entries are
-        the answers: start .. start+count-1 of them come back (count: depth by default), -1 / -inf / 0 past the last, and `total`
-        is their number.  `score` is passed through (cc_index_distinct)."""
-        ia = np.ascontiguousarray(np.asarray(idx), dtype=np.int32)
-        ia = ia.reshape(1, -1) if ia.ndim < 2 else ia.reshape(ia.shape[0], -1)
-        Q, depth = ia.shape
-        count = depth if count is None else int(count)
-        sa = None
-        if score is not None:
-            sa = np.ascontiguousarray(as_numpy(score), dtype=np.float32).reshape(Q, depth)
-        shape = (Q, count) if count >= 1 and Q >= 1 else (1, 1)                    # the library names the error
-        oi, od = np.empty(shape, np.int32), np.empty(shape, np.int32)
-        os_ = np.empty(shape, np.float32) if sa is not None else None
-        total = np.zeros(max(Q, 1), np.int64)
-        _lib.check(_lib.lib().cc_index_distinct(self._h, _lib.ptr(ia), _lib.ptr(sa), Q, depth, float(same_at), int(start), count,
-                                                _lib.ptr(oi), _lib.ptr(os_), _lib.ptr(od), _lib.ptr(total), 0, None))
-        return oi, os_, od, total
-
-    def distinct_device(self, idx, score=None, same_at: float = 0.9, start: int = 0, count=None, with_total: bool = True):
-        """`distinct` for CUDA tensors, e.g. the idx / score of `rank_device` or `rank_like_device`: the answers stay on the GPU, on
-        the current torch stream.  `total` comes back as a host array, which costs one wait for the stream; with_total=False
-        returns None in its place and waits for nothing."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        ia = idx.to(device=dev, dtype=torch.int32).contiguous()
-        ia = ia.reshape(1, -1) if ia.dim() < 2 else ia.reshape(ia.shape[0], -1)
-        Q, depth = int(ia.shape[0]), int(ia.shape[1])
-        count = depth if count is None else int(count)
-        sa = None if score is None else score.to(device=dev, dtype=torch.float32).contiguous().reshape(Q, depth)
-        shape = (Q, count) if count >= 1 and Q >= 1 else (1, 1)                    # the library names the error
-        oi = torch.empty(shape, dtype=torch.int32, device=dev)
-        od = torch.empty(shape, dtype=torch.int32, device=dev)
-        os_ = torch.empty(shape, dtype=torch.float32, device=dev) if sa is not None else None
-        total = np.zeros(max(Q, 1), np.int64) if with_total else None
-        cur, run = self._run_stream(dev)
-        _lib.check(_lib.lib().cc_index_distinct(self._h, _lib.ptr(ia), _lib.ptr(sa), Q, depth, float(same_at), int(start), count,
-                                                _lib.ptr(oi), _lib.ptr(os_), _lib.ptr(od), _lib.ptr(total), 1, C.c_void_p(run.cuda_stream)))
-        if run is not cur:
-            cur.wait_stream(run)
-        for t in (ia, sa):                              # inputs made here (a cast or a copy) must outlive the launches that read them
-            if t is not None:
-                t.record_stream(run)
-        return oi, os_, od, total
-
-    # -- day digest: every distinct object among the competing rows once, with count and times (cc_index_digest) -----------------------
-    DIGEST_BY = {"count": _lib.DIGEST_BY_COUNT, "first": _lib.DIGEST_BY_FIRST}
-
-    def _digest(self, same_at, start, count, allowed, where, max_leaders, by, out, owner, totals, on_device, stream):
-        if by not in self.DIGEST_BY:
-            raise ValueError('by: "count" or "first"')
-        # a device caller waits for nothing: the filter bytes stay referenced until the next call replaces them
-        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_digest(self._h, float(same_at), int(max_leaders), self.DIGEST_BY[by], _lib.ptr(al) if al is not None else None,
-                                              0 if al is None else int(al.size), C.byref(where) if where is not None else None, int(start), int(count),
-                                              *(_lib.ptr(o) for o in out), _lib.ptr(owner), _lib.ptr(totals), on_device, stream))
-
-    def digest(self, same_at: float = 0.9, start: int = 0, count=None, allowed=None, ts_range=None, classes=None, max_leaders: int = 1024,
-               by: str = "count", owners: bool = False):
-        """What is in the index, every distinct object once -> (rows (count,) int32, counts (count,) int32, ts_first (count,) int32,
-        ts_last (count,) int32, totals (3,) int64[, owner (len(self),) int32]).  No query: the rows that compete are `rank`'s with
-        tracks=False (allowed, ts_range, classes), walked in row order, which is ingest order.  A row joins the first-created leader
-        whose `gram` with it is >= same_at (float32), else it becomes a leader while fewer than max_leaders (<= 1024) exist, else
-        it is left over.  Per leader: its row (the first sighting), its members (itself included) and the min / max ts among them
-        (_lib.ROW_NO_TS: none has one).  by="count": most members first, equal counts by row; "first": in order of appearance.
-        Entries start .. start+count-1 come back (count: max_leaders by default), -1 / 0 / ROW_NO_TS past the last.  totals: leaders,
-        competing rows, left-over rows; the counts of all leaders sum to totals[1] - totals[2].  owners=True: per index row its
-        leader's row, -1 where the row did not compete, -2 where it was left over (cc_index_digest)."""
-        where = self.row_filter(ts_range, classes)
-        count = int(max_leaders) if count is None else int(count)
-        k = count if count >= 1 else 1                                             # the library names the error
-        out = tuple(np.empty(k, np.int32) for _ in range(4))
-        totals = np.zeros(3, np.int64)
-        owner = np.empty(max(len(self), 1), np.int32) if owners else None
-        self._digest(same_at, start, count, allowed, where, max_leaders, by, out, owner, totals, 0, None)
-        return (*out, totals, owner[:len(self)]) if owners else (*out, totals)
-
-    def digest_device(self, same_at: float = 0.9, start: int = 0, count=None, allowed=None, ts_range=None, classes=None, max_leaders: int = 1024,
-                      by: str = "count", owners: bool = False, with_total: bool = True):
-        """`digest` with rows / counts / ts_first / ts_last (and owner) left on the GPU as CUDA torch tensors on the current torch
-        stream.  `totals` comes back as a host array, which costs one wait for the stream; with_total=False returns None in its
-        place and nothing but tensors comes back (inside, the call reads back one number, the count of competing rows)."""
-        import torch
-        where = self.row_filter(ts_range, classes)
-        dev = torch.device("cuda", self.device)
-        count = int(max_leaders) if count is None else int(count)
-        out = tuple(torch.empty(max(count, 1), dtype=torch.int32, device=dev) for _ in range(4))
-        n = len(self)
-        owner = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if owners else None
-        totals = np.zeros(3, np.int64) if with_total else None
-        cur, run = self._run_stream(dev)
-        self._digest(same_at, start, count, allowed, where, max_leaders, by, out, owner, totals, 1, C.c_void_p(run.cuda_stream))
-        if run is not cur:
-            cur.wait_stream(run)
-        return (*out, totals, owner[:n]) if owners else (*out, totals)
-
-    # -- seen before: up to 1024 stored rows against all competing rows, reduced per object (cc_index_sightings) --------------------------
-    def _sightings(self, rows, same_at, allowed, where, skip_self, out, n_group_counts, total, on_device, stream):
-        ids = self._row_numbers(rows)
-        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_sightings(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), float(same_at),
-                                                 _lib.SIGHT_SKIP_SELF if skip_self else 0, _lib.ptr(al) if al is not None else None,
-                                                 0 if al is None else int(al.size), C.byref(where) if where is not None else None,
-                                                 *(_lib.ptr(o) for o in out), int(n_group_counts), _lib.ptr(total), on_device, stream))
-
-    @staticmethod
-    def _sightings_shape(rows, group_counts):
-        n, g = int(np.asarray(rows).size), int(group_counts)
-        return (n if 1 <= n <= _lib.SIGHT_MAX_OBJECTS else 1), (g if 0 <= g <= _lib.SIGHT_MAX_GROUPS else 1)   # outside: the library names the error
-
-    def sightings(self, rows, same_at: float = 0.9, allowed=None, ts_range=None, classes=None, skip_self: bool = False, group_counts: int = 0,
-                  with_total: bool = True):
-        """Stored rows (the objects, 1 .. 1024 of them, repeats allowed) against ALL competing rows -> (count (n,) int32, best_row (n,)
-        int32, best_score (n,) f32, group_counts (n, group_counts) uint32 or None, total).  The rows that compete are `rank`'s with
-        tracks=False (allowed, ts_range, classes); an object need not compete itself.  The value of a pair is `gram` of the two rows
-        (that very float).  count: the pairs >= same_at (float32); best: the pair with the largest value, equal values by the lower
-        row, -1 / -inf without a pair, whatever same_at; group_counts[i][g]: the matches of object i in group g (matches in groups
-        >= group_counts are in count only).  skip_self: the pair of an object with its own row number does not exist.  total: the
-        number of competing rows (cc_index_sightings)."""
-        where = self.row_filter(ts_range, classes)
-        n, g = self._sightings_shape(rows, group_counts)
-        out = (np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32), np.empty((n, g), np.uint32) if group_counts else None)
-        total = np.zeros(1, np.int64) if with_total else None
-        self._sightings(rows, same_at, allowed, where, skip_self, out, group_counts, total, 0, None)
-        return (*out, None if total is None else int(total[0]))
-
-    def sightings_device(self, rows, same_at: float = 0.9, allowed=None, ts_range=None, classes=None, skip_self: bool = False,
-                         group_counts: int = 0, with_total: bool = True):
-        """`sightings` with the four outputs left on the GPU as CUDA torch tensors on the current torch stream (rows stay a host
-        list).  with_total=False returns None for the total and waits for nothing: inside, nothing is read back."""
-        import torch
-        where = self.row_filter(ts_range, classes)
-        dev = torch.device("cuda", self.device)
-        n, g = self._sightings_shape(rows, group_counts)
-        out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-               torch.empty(n, dtype=torch.float32, device=dev),
-               torch.empty((n, g), dtype=torch.int32, device=dev) if group_counts else None)      # uint32 counts in an int32 tensor
-        total = np.zeros(1, np.int64) if with_total else None
-        cur, run = self._run_stream(dev)
-        self._sightings(rows, same_at, allowed, where, skip_self, out, group_counts, total, 1, C.c_void_p(run.cuda_stream))
-        if run is not cur:
-            cur.wait_stream(run)
-        return (*out, None if total is None else int(total[0]))
-
-    def timeline(self, q, t0: int, bin_seconds: int, n_bins: int, allowed=None, min_score=None, tracks: bool = True, ts_range=None,
-                 classes=None) -> Tuple[np.ndarray, np.ndarray]:
-        """How the answers of `rank` (same arguments) spread over time -> (counts (Q, n_bins) int64, total (Q,) int64), in one call
-        (cc_index_timeline).  An answer falls into bin floor((ts - t0) / bin_seconds), ts being that of the row `rank` names for it
-        (a track: its best passing crop); an answer without ts or outside the n_bins bins is counted in `total` only, which
-        equals `rank`'s total.  bin_seconds >= 1, 1 <= n_bins <= 4096, t0 an int32."""
-        where = self.row_filter(ts_range, classes)
-        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
-        if not -(1 << 31) <= t0 < 1 << 31 or not -(1 << 31) <= bin_seconds < 1 << 31 or not -(1 << 31) <= n_bins < 1 << 31:
-            raise ValueError("t0, bin_seconds and n_bins must fit in int32")
-        qa = np.ascontiguousarray(as_numpy(q), dtype=np.float32).reshape(-1, self.dim)
-        counts = np.zeros((qa.shape[0], min(max(n_bins, 1), 4096)), np.uint32)     # outside [1, 4096]: the library names the error
-        total = np.zeros(qa.shape[0], np.int64)
-        al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        _lib.check(_lib.lib().cc_index_timeline(self._h, _lib.ptr(qa), qa.shape[0], float(self.cut_f32(min_score)), 1 if tracks else 0,
-                                                _lib.ptr(al) if al is not None else None, 0 if al is None else int(al.size),
-                                                C.byref(where) if where is not None else None, t0, bin_seconds, n_bins,
-                                                _lib.ptr(counts), _lib.ptr(total), 0, None))
-        return counts.astype(np.int64), total
-
-    def search_device(self, q, k: int):
-        """`search` with the result left on the GPU: (idx int32, score f32) CUDA torch tensors on the current torch stream,
-        for callers that keep going on the device (clearcam_amd.dist.ShardedIndex: all-gather + merge)."""
-        return self._search_device("cc_index_search_groups", q, k, None)
-
-    def _search_device(self, call: str, q, k: int, allowed, rank_args=None, with_total: bool = False, where=None):
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not bool(getattr(q, "is_cuda", False)):
-            # on_device=1 tells the library that BOTH the queries and the outputs are device pointers: a host query is uploaded
-            # here first, on the caller's stream (a host pointer handed to a device-to-device copy only works by accident of
-            # ROCm's pointer inference, and the temporary could be freed while the copy is pending)
-            q = torch.as_tensor(np.ascontiguousarray(as_numpy(q), dtype=np.float32)).to(dev)
-        qa = q.contiguous().float().reshape(-1, self.dim)
-        idx = torch.empty((qa.shape[0], k), dtype=torch.int32, device=dev)
-        sc = torch.empty((qa.shape[0], k), dtype=torch.float32, device=dev)
-        cur, run = self._run_stream(dev)
-        # nothing waits for the stream here: the filter bytes stay referenced until the next call replaces them
-        al = self._allowed_in_flight = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.uint8)
-        total = np.zeros(qa.shape[0], np.int64) if with_total else None
-        if rank_args is not None and where is not None:
-            _lib.check(_lib.lib().cc_index_rank_where(self._h, _lib.ptr(qa), qa.shape[0], *rank_args, _lib.ptr(al) if al is not None else None,
-                                                      0 if al is None else int(al.size), C.byref(where), _lib.ptr(idx), _lib.ptr(sc),
-                                                      _lib.ptr(total), 1, C.c_void_p(run.cuda_stream)))
-        elif rank_args is not None:
-            _lib.check(_lib.lib().cc_index_rank(self._h, _lib.ptr(qa), qa.shape[0], *rank_args, _lib.ptr(al) if al is not None else None,
-                                                0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(total), 1,
-                                                C.c_void_p(run.cuda_stream)))
-        else:
-            _lib.check(getattr(_lib.lib(), call)(self._h, _lib.ptr(qa), qa.shape[0], k, _lib.ptr(al) if al is not None else None,
-                                                  0 if al is None else int(al.size), _lib.ptr(idx), _lib.ptr(sc), 1, C.c_void_p(run.cuda_stream)))
-        if run is not cur:
-            cur.wait_stream(run)
-        return (idx, sc) if rank_args is None else (idx, sc, total)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.lib().cc_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _RowTable:

@@ -248,6 +248,58 @@ def test_a_track_that_lost_its_first_row_is_placed_by_its_first_competing_row(st
     ix.close()
 
 
+def small_world(n):
+    """n rows in 3 groups: rows 3, 7, 11, ... (64 of them) are slot 0 of group 1, the query track; rows 7 and 11 of it are byte-equal,
+    so two query rows score every row alike; row 2 (slot 5, group 2) is a copy of row 3, row 1 is slot 0 in group 2 (the slot goes on
+    answering with the track dead); the rest: slots 1 .. 8, every seventh row slot-less."""
+    rng = np.random.default_rng(n)
+    E = unit(rng.standard_normal((n, DIM)))
+    track = 3 + 4 * np.arange(64)
+    slot = (1 + np.arange(n) % 8).astype(np.int32)
+    slot[::7] = -1
+    group = (1 + rng.integers(0, 3, n)).astype(np.int32)
+    slot[track], group[track] = 0, 1
+    E[11], E[2] = E[7], E[3]
+    slot[2], group[2], slot[1], group[1] = 5, 2, 0, 2
+    return E, slot, group, track
+
+
+@pytest.mark.parametrize("n", [260, 261])                                           # four rows per thread / one row per thread
+def test_the_fold_of_a_set_is_the_compound_fold_at_its_edges(n):
+    """rank_like runs the fold of rank_terms (every row a RANK term, MAX): sets of 1, 3, 4, 5 and 64 rows (the one-row case, both sides
+    of the fold's four-term step, the most a call takes), with nothing, the rows and the track excluded, tracks on and off, against
+    the model on the device's own scores and against rank_terms of the same rows, bit for bit."""
+    from clearcam_amd.objects import EmbeddingIndex
+    E, slot, group, track = small_world(n)
+    ix = EmbeddingIndex(DIM, n, storage="f32")                                      # the fold does not depend on the storage
+    ix.add(E, group, slot)
+    none = np.full(n, -(1 << 31), np.int32), np.full(n, -1, np.int32)
+    for k in (1, 3, 4, 5, 64):
+        rows = track[:k] if k > 1 else track[1:2]                                   # from 3 rows on: rows 7 and 11, the equal pair, are in
+        S = ix.scores(ix.fetch(rows))
+        assert S.shape == (k, n) and (k < 3 or np.array_equal(bits(S[1]), bits(S[2])))
+        for exclude in (None, "rows", "track"):
+            for tracks in (True, False):
+                what = (n, k, exclude, tracks)
+                want = like_model(S, slot, group, 4, *none, rows, 0, n, None, None, tracks, exclude)
+                got = ix.rank_like(rows, 0, n, tracks=tracks, exclude=exclude)
+                same(got, want, what)
+                same(ix.rank_terms(rows=rows, start=0, count=n, tracks=tracks, exclude=exclude), got, what + ("rank_terms",))
+                same(ix.rank_like(rows, 5, 40, tracks=tracks, exclude=exclude), like_model(S, slot, group, 4, *none, rows, 5, 40, None, None, tracks, exclude), what + ("page",))
+                ans = got[0][0, :int(got[2][0])]
+                dead = set() if exclude is None else set(rows.tolist()) if exclude == "rows" else set(track.tolist())
+                assert not set(ans.tolist()) & dead
+                if not tracks:
+                    assert got[2][0] == n - len(dead)
+                    if k > 1:
+                        assert 2 in ans                                             # the copy of an excluded crop still answers
+        if k == 1:
+            q = ix.fetch(rows)
+            for tracks in (True, False):
+                same(ix.rank_like(rows, 0, n, tracks=tracks), ix.rank(q, 0, n, tracks=tracks), (n, "one row is rank of the fetched row", tracks))
+    ix.close()
+
+
 # 5 ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("storage", STORAGES)
 def test_the_order_of_the_set_changes_nothing(worlds, storage):

@@ -10,7 +10,7 @@ round medians:
   A  rank(0, 100), one query on the device                              the yardstick of a one-vector question
   D  rank_like(the 64 rows of the track, 0, 100, exclude=track)         the yardstick of a 64-row question
   F  rank_terms, one vector RANK term                                   A's launches
-  G  rank_terms, the same 64 rows as RANK terms, MAX, track excluded,   D's launches with terms_fold_kernel for like_fold_kernel, one more
+  G  rank_terms, the same 64 rows as RANK terms, MAX, track excluded,   D's launches (the same terms_fold_kernel), one more
      which asked for                                                    byte a row stored, and the gather of 100 entries
   H  rank_terms, a text RANK term, 8 stored REJECT rows, one REQUIRE    ten terms scored by scan passes (below the GEMM / MFMA thresholds), one fold
      vector
