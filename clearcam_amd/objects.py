@@ -22,14 +22,9 @@ from .alerts import AlertBook, WatchList  # noqa: F401  (re-exported: the alert 
 from .arch import CLIP_L14, ClipArch
 from .helpers import Tensor, as_numpy
 from .index import EmbeddingIndex, row_filter  # noqa: F401  (re-exported: this module's ObjectFinder is built on them)
+from .row_table import _RowTable, event_img_info, pick_track_rows  # noqa: F401  (re-exported: callers and tools import them from here)
 from .weights import load_safetensors
 from .yolov9 import DTYPES
-
-
-def event_img_info(image: str) -> dict:
-    """``clearcam.py:1193``: '<ts>_<track id>_<class id>' crop file stem."""
-    p = image.split("_")
-    return {"ts": int(float(p[0])), "object_id": int(p[1]), "class_id": int(p[2])}
 
 
 class OpenCLIP:
@@ -153,167 +148,6 @@ class Term(NamedTuple):
     cut: Optional[float] = None
 
 
-def pick_track_rows(row: int, members) -> np.ndarray:
-    """The query rows of `ObjectFinder.similar(..., whole_track=True)`: `members` are the rows of the clicked crop's track (`row`
-    among them).  Up to _lib.LIKE_MAX_ROWS rows: all of them.  More: the clicked row plus 63 of the m - 1 others, those at
-    positions np.linspace(0, m - 2, 63).round() of the others in row order, so the pick spans the whole track, is the same on every
-    call and never drops the clicked crop.  Ascending, distinct."""
-    m = np.unique(np.asarray(members, np.int64))
-    if int(row) not in m:
-        raise ValueError("the clicked row is not among the track's rows")
-    if m.size <= _lib.LIKE_MAX_ROWS:
-        return m
-    others = m[m != int(row)]
-    at = np.linspace(0, others.size - 1, _lib.LIKE_MAX_ROWS - 1).round().astype(np.int64)
-    return np.sort(np.r_[others[at], np.int64(row)])
-
-
-class _RowTable:
-    """Host-side description of the rows of one device matrix, built ONCE when rows are added, so that a search costs
-    O(groups + candidates) Python instead of the reference's O(N) loop (models/objects.py:365-376).
-
-    The reference filters a crop by two substring tests on its '/'-normalised path — f"/cameras/{cam}/" and
-    f"/objects/{day}/" or "/objects/video/" (:368-371).  Both patterns end in '/', so they can only match inside the
-    directory part of the path: rows are grouped by directory string and the tests run once per group.  Group 0 holds the
-    rows the reference never returns (file name not *.jpg, :374)."""
-
-    def __init__(self):
-        self.paths: List[str] = []
-        self.dirs: List[str] = [""]            # group id -> directory part (group 0: never allowed)
-        self.dir_id: Dict[str, int] = {}
-        self.truthy: List[bool] = [False]      # group has a crop whose track id is truthy (the `any(item[2] ...)` of :378)
-        self.bad: List[bool] = [False]         # group has a *.jpg name event_img_info cannot parse (the reference raises on it)
-        self.group: List[int] = []
-        self.oid: List[Optional[int]] = []     # track id per row exactly as event_img_info returns it (any sign), None = no '_' in the name
-        self.slot_of: Dict[int, int] = {}      # track id -> dense slot, in order of first appearance (id 0 and negative ids are ids)
-        self.slot: List[int] = []              # slot per row, -1 where oid is None: what the device reduces by (EmbeddingIndex.search_tracks)
-        self.ts: List[int] = []                # seconds into the day's recording per row (event_img_info's `ts`), _lib.ROW_NO_TS = none
-        self.cls: List[int] = []               # detector class per row (event_img_info's `class_id`) in [0, 255], -1 = none
-        self.row: Dict[str, int] = {}          # path -> row; a path stored twice names its last row (the reference's dict keeps the last value of a key)
-
-    def row_of(self, path: str) -> int:
-        """The row that holds `path` (a stored key, exactly as it was given); KeyError when there is none."""
-        return self.row[path]
-
-    @staticmethod
-    def name_attrs(path: str) -> Tuple[int, int]:
-        """(ts, class) of a crop as the device stores them: `event_img_info` of the '<ts>_<track>_<class>.jpg' name, i.e.
-        int(float(first part)) and int(third part).  "None" (_lib.ROW_NO_TS / -1) when the name is no *.jpg, has no '_', does
-        not parse, or the value does not fit (ts: an int32 other than ROW_NO_TS itself; class: [0, 255])."""
-        fn = os.path.basename(path)
-        if not fn.lower().endswith(".jpg") or "_" not in fn:
-            return _lib.ROW_NO_TS, -1
-        try:
-            info = event_img_info(fn.split(".jpg")[0])
-        except Exception:                      # noqa: BLE001  a name the reference raises on carries no attributes
-            return _lib.ROW_NO_TS, -1
-        ts, c = info["ts"], info["class_id"]
-        return (ts if _lib.ROW_NO_TS < ts < (1 << 31) else _lib.ROW_NO_TS), (c if 0 <= c <= 255 else -1)
-
-    def describe(self, path: str) -> Tuple[int, int]:
-        norm = path.replace("\\", "/")
-        fn = os.path.basename(path)
-        if not fn.lower().endswith(".jpg"):
-            return 0, None
-        d = norm[:norm.rfind("/") + 1]
-        g = self.dir_id.get(d)
-        if g is None:
-            g = self.dir_id[d] = len(self.dirs)
-            self.dirs.append(d); self.truthy.append(False); self.bad.append(False)
-        oid = None
-        if "_" in fn:
-            try:
-                oid = event_img_info(fn.split(".jpg")[0])["object_id"]
-            except Exception:                  # noqa: BLE001  names the reference raises on take the exact slow path at search time
-                self.bad[g] = True
-                oid = None
-        if oid:                                # the reference's `any(item[2] ...)`: id 0 and None are falsy
-            self.truthy[g] = True
-        return g, oid
-
-    def extend(self, paths) -> np.ndarray:
-        groups = np.empty(len(paths), np.int32)
-        base = len(self.paths)
-        for i, p in enumerate(paths):
-            g, oid = self.describe(p)
-            groups[i] = g
-            self.row[p] = base + i
-            self.group.append(g); self.oid.append(oid)
-            self.slot.append(-1 if oid is None else self.slot_of.setdefault(oid, len(self.slot_of)))
-            ts, c = self.name_attrs(p)
-            self.ts.append(ts); self.cls.append(c)
-        self.paths.extend(paths)
-        return groups
-
-    def slots(self, start: int = 0) -> np.ndarray:
-        return np.asarray(self.slot[start:], np.int32)
-
-    def attrs(self, start: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        """(ts, class) of the rows from `start` on, as EmbeddingIndex.add takes them."""
-        return np.asarray(self.ts[start:], np.int32), np.asarray(self.cls[start:], np.int32)
-
-    def passing(self, where) -> np.ndarray:
-        """Bool per row: the row passes the row filter (an `EmbeddingIndex.row_filter`, None: every row), as the device decides."""
-        ok = np.ones(len(self.paths), bool)
-        if where is None:
-            return ok
-        ts, c = self.attrs()
-        if where.use_ts:
-            ok &= (ts != _lib.ROW_NO_TS) & (ts >= where.ts_min) & (ts <= where.ts_max)
-        if where.use_cls:
-            bits = np.array([(int(where.cls_mask[i >> 6]) >> (i & 63)) & 1 for i in range(256)], bool)
-            ok &= (c >= 0) & bits[np.clip(c, 0, 255)]
-        return ok
-
-    @staticmethod
-    def dir_of(path: str) -> str:
-        """The directory part `describe` groups by: '/'-normalised, with its trailing '/'."""
-        norm = path.replace("\\", "/")
-        return norm[:norm.rfind("/") + 1]
-
-    def remove(self, mask) -> int:
-        """Forget the rows with a non-zero entry in `mask` (one per row), in step with EmbeddingIndex.remove on the device: the
-        survivors keep their order.  Directory group ids and track slots are stable (`dirs` / `dir_id` / `slot_of` keep their
-        entries, the device keeps its ids), so a later crop of the same folder or track reuses them; `truthy` / `bad` are
-        recomputed for the groups that lost rows.  Returns the number of rows forgotten."""
-        drop = np.asarray(mask).reshape(-1) != 0
-        if drop.size != len(self.paths):
-            raise ValueError(f"expected one entry per row ({len(self.paths)}), got {drop.size}")
-        gone = np.flatnonzero(drop)
-        if gone.size == 0:
-            return 0
-        lost = {self.group[r] for r in gone.tolist()} - {0}
-        keep = np.flatnonzero(~drop).tolist()
-        self.paths = [self.paths[r] for r in keep]
-        self.group = [self.group[r] for r in keep]
-        self.oid = [self.oid[r] for r in keep]
-        self.slot = [self.slot[r] for r in keep]
-        self.ts = [self.ts[r] for r in keep]
-        self.cls = [self.cls[r] for r in keep]
-        self.row = {p: r for r, p in enumerate(self.paths)}
-        for g in lost:
-            self.truthy[g] = self.bad[g] = False
-        for r, g in enumerate(self.group):
-            if g in lost:
-                oid = self.oid[r]
-                if oid:
-                    self.truthy[g] = True
-                elif oid is None and "_" in os.path.basename(self.paths[r]):   # a name `describe` could not parse
-                    self.bad[g] = True
-        return int(gone.size)
-
-    def allowed(self, cam_name, timestamp) -> np.ndarray:
-        al = np.zeros(len(self.dirs), np.uint8)
-        for g in range(1, len(self.dirs)):
-            d = self.dirs[g]
-            if cam_name and f"/cameras/{cam_name}/" not in d:
-                continue
-            if timestamp and f"/objects/{timestamp}/" not in d and "/objects/video/" not in d:
-                continue
-            al[g] = 1
-        return al
-
-
 def pack_crops(crops, tail: int = 0):
     """List of (H,W,3) uint8 arrays -> (packed bytes, offsets int64, heights int32, widths int32): the packed-buffer convention of
     cc_crop_preprocess / cc_face_locate / cc_face_align.  `tail` zero bytes are appended behind the last crop."""
@@ -361,6 +195,82 @@ class _PackedCrops(NamedTuple):
     offsets: np.ndarray
     hs: np.ndarray
     ws: np.ndarray
+
+
+# -- what ObjectFinder's questions share: argument checks (each names the question it speaks for), the scope, rows and scores to answers --
+def _row_kw(ts_range, classes):
+    """-> (row filter or None, the keyword arguments that carry it to the index: none without a filter)"""
+    where = row_filter(ts_range, classes)
+    return where, ({} if where is None else {"ts_range": ts_range, "classes": classes})
+
+
+def _page_args(name: str, start, count) -> Tuple[int, int]:
+    start, count = int(start), int(count)
+    if start < 0 or count < 1:
+        raise ValueError(f"{name} needs start >= 0 and count >= 1")
+    return start, count
+
+
+def _bin_args(name: str, t0, bin_seconds, n_bins) -> Tuple[int, int, int]:
+    t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
+    if bin_seconds < 1 or not 1 <= n_bins <= 4096:
+        raise ValueError(f"{name} needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
+    return t0, bin_seconds, n_bins
+
+
+def _cut_arg(cut, name: str = "min_score"):
+    if cut is not None and cut != cut:
+        raise ValueError(f"{name} is NaN")
+    return cut
+
+
+def _choice_arg(name: str, value, choices) -> None:
+    """`value` is one of `choices` (None, or names), which the message lists in their order"""
+    if value not in choices:
+        said = [str(c) if c is None else f'"{c}"' for c in choices]
+        raise ValueError(f"{name}: {', '.join(said[:-1])} or {said[-1]}")
+
+
+class _Scope(NamedTuple):
+    """What a question resolves once, before its one index call."""
+    index: object
+    table: _RowTable
+    allowed: np.ndarray        # per directory group: the folder is one of (cam_name, timestamp)
+    grouped: bool              # a live folder holds a truthy track id: answers are grouped per track (models/objects.py:378)
+    bad: bool                  # a live folder holds a *.jpg name the reference raises on
+    where: object              # the row filter, None: every row
+    kw: dict                   # what carries the row filter to the index
+
+
+def _competing(s: _Scope, ok=None) -> List[int]:
+    """The rows of the live folders that pass the row filter (`ok`: a bool per row that stands in for it)"""
+    ok = s.table.passing(s.where) if ok is None else ok
+    return [r for r in range(len(s.table.paths)) if s.allowed[s.table.group[r]] and ok[r]]
+
+
+def _raise_as_reference(table: _RowTable, rows) -> None:
+    """Let the names among `rows` that the reference itself would raise on raise the same way"""
+    for r in rows:
+        fn = os.path.basename(table.paths[r])
+        if "_" in fn:
+            event_img_info(fn.split(".jpg")[0])
+
+
+def _answers(table: _RowTable, rows, scores, *columns) -> list:
+    """One query's rows (a list, -1 where the page ran out) and scores, as the index returns them -> [(path, score, *columns)]"""
+    paths = table.paths
+    if not columns:                                # the common page, kept to the plain comprehension: a hundred answers per call
+        return [(paths[r], float(v)) for r, v in zip(rows, scores) if r >= 0]
+    return [(paths[r], float(v), *rest) for r, v, *rest in zip(rows, scores, *columns) if r >= 0]
+
+
+def _above(full, min_score) -> list:
+    """A host-ranked list of (path, score) cut as the device cuts it"""
+    return [r for r in full if min_score is None or not r[1] < min_score]
+
+
+def _ts_or_none(t) -> Optional[int]:
+    return None if t == _lib.ROW_NO_TS else int(t)
 
 
 class ObjectFinder:
@@ -890,18 +800,80 @@ class ObjectFinder:
             return self._dev["store"]
         return self._device_index(self.face_embeddings if is_face else self.image_embeddings, "face" if is_face else "image")
 
-    def _search_setup(self, query, cam_name, timestamp, text_embedding, is_face):
-        """What `search` and `search_page` share: -> (q, index, table, allowed) or None when there is nothing to search."""
+    # -- the one path of the questions, in this order: argument checks that need no state (ValueError); nothing stored (the reference's
+    # -- line, the empty answer); an index that cannot answer (RuntimeError); stored paths (KeyError) and vector widths (ValueError); no
+    # -- live folder (the empty answer); folders with names that do not parse (fall back or raise, per question); the one index call.
+    def _store(self, is_face, needs=(), cannot=None):
+        """First step of a question's scope -> (index, table), or None when nothing is stored.  `needs`: the index methods the
+        question cannot do without."""
         if not self._has_rows(is_face):
             print("No embeddings available.")
             return None
-        if text_embedding is None:
-            text_embedding = self.model._encode_text(query).numpy()
-        q = np.asarray(as_numpy(text_embedding), np.float32).reshape(-1)
         index, table = self._index_and_table(is_face)
-        if q.size != index.dim:
-            raise ValueError(f"query has {q.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
-        return q, index, table, table.allowed(cam_name, timestamp)
+        for m in needs:
+            if not hasattr(index, m):
+                raise RuntimeError(cannot)
+        return index, table
+
+    @staticmethod
+    def _scope(index, table: "_RowTable", cam_name, timestamp, where, kw, no_host_ranking=None) -> Optional[_Scope]:
+        """Second step: the folders -> the scope, or None when no folder is live.  no_host_ranking: the name of a question that grows
+        none, for which a live folder with names the reference raises on is an error."""
+        allowed = table.allowed(cam_name, timestamp)
+        live = np.flatnonzero(allowed)
+        if live.size == 0:
+            return None
+        bad = [g for g in live if table.bad[g]]
+        if bad and no_host_ranking:
+            raise ValueError(f"{no_host_ranking} cannot rank the folder {table.dirs[bad[0]]}: it holds crop names that do not parse")
+        return _Scope(index, table, allowed, any(table.truthy[g] for g in live), bool(bad), where, kw)
+
+    def _vector(self, what: str, src, is_text: bool, index, is_face) -> np.ndarray:
+        """A query text (encoded by the CLIP text tower), an embedding or an ndarray -> a flat float32 vector of the index's width
+        (what=None: of whatever width, as a `Term`'s text always was)"""
+        v = np.asarray(as_numpy(self.model._encode_text(src).numpy() if is_text else src), np.float32).reshape(-1)
+        if what is not None and v.size != index.dim:
+            raise ValueError(f"{what} has {v.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
+        return v
+
+    def _search_setup(self, query, cam_name, timestamp, text_embedding, is_face, ts_range, classes):
+        """What `search`, `search_page` and `timeline` share: -> (q, scope) or None when there is nothing to search."""
+        where, kw = _row_kw(ts_range, classes)
+        store = self._store(is_face)
+        if store is None:
+            return None
+        q = self._vector("query", query if text_embedding is None else text_embedding, text_embedding is None, store[0], is_face)
+        s = self._scope(*store, cam_name, timestamp, where, kw)
+        return None if s is None else (q, s)
+
+    @staticmethod
+    def _host_page(s: _Scope, full, min_score, distinct, depth, start, count):
+        """The tail of a question ranked on the host, `full` its (path, score) list: cut, then sliced - or with `distinct` the page of
+        its first `depth` answers thinned by their rows in the index."""
+        kept = _above(full, min_score)
+        if distinct is None:
+            return kept[start:start + count], len(kept)
+        if not hasattr(s.index, "distinct"):
+            raise RuntimeError("this index cannot thin its answers")
+        head = kept[:depth]
+        if not head:
+            return [], 0
+        rows = np.array([s.table.row_of(p) for p, _ in head], np.int32)
+        oi, os_, od, total = s.index.distinct(rows, np.array([v for _, v in head], np.float32), distinct, start, min(count, len(head)))
+        return _answers(s.table, oi[0].tolist(), os_[0], od[0].tolist()), int(total[0])
+
+    @staticmethod
+    def _ranked_page(s: _Scope, method: str, ask, distinct, depth, start, count):
+        """One page of a ranking by the index -> (results, total, what the index returned).  ask(fn, start, count, **more) makes the
+        question's call of fn: the index's `method`, or with `distinct` its _device twin over the first `depth` answers, which are
+        thinned where they are: only the page of the kept ones leaves the GPU."""
+        rows = len(s.table.paths)
+        if distinct is None:
+            out = ask(getattr(s.index, method), start, min(count, rows))
+            return _answers(s.table, out[0][0].tolist(), out[1][0]), int(out[2][0]), out
+        out = ask(getattr(s.index, method + "_device"), 0, min(depth, rows), with_total=False)
+        oi, os_, od, total = s.index.distinct_device(out[0], out[1], distinct, start, min(count, int(out[0].shape[-1])))
+        return _answers(s.table, oi[0].cpu().tolist(), os_[0].cpu().numpy(), od[0].cpu().tolist()), int(total[0]), out
 
     def search_page(self, query=None, start=0, count=100, cam_name=None, timestamp=None, text_embedding=None, is_face=False, min_score=None,
                     ts_range=None, classes=None, distinct=None, distinct_depth=1024):
@@ -918,67 +890,29 @@ class ObjectFinder:
         >= distinct with one KEPT before it is dropped - one object under many track ids, days or cameras answers once.  The page
         is cut from the kept answers: -> ([(path, score, dups)], total), dups the answers folded into that one ("+12 similar") and
         total the kept answers among those first distinct_depth.  None: exactly the call without it."""
-        where = row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        if start < 0 or count < 1:
-            raise ValueError("search_page needs start >= 0 and count >= 1")
-        if min_score is not None and min_score != min_score:
-            raise ValueError("min_score is NaN")
+        start, count = _page_args("search_page", start, count)
+        _cut_arg(min_score)
         distinct, distinct_depth = self._distinct_args(distinct, distinct_depth)
-        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
+        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face, ts_range, classes)
         if setup is None:
             return [], 0
-        q, index, table, allowed = setup
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
-            return [], 0
-        if any(table.bad[g] for g in live) or not hasattr(index, "rank"):
+        q, s = setup
+        if s.bad or not hasattr(s.index, "rank"):
             # names the reference raises on (it raises here too), or an index that cannot rank: the whole list, cut on the host
-            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face,
-                               ts_range=ts_range, classes=classes)
-            kept = [r for r in full if min_score is None or not r[1] < min_score]
-            if distinct is not None:
-                return self._distinct_host(index, table, kept, distinct, distinct_depth, start, count)
-            return kept[start:start + count], len(kept)
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        if distinct is not None:
-            depth = min(distinct_depth, len(table.paths))
-            idx, sc, _ = index.rank_device(q, 0, depth, allowed, min_score, tracks=any(table.truthy[g] for g in live), with_total=False, **kw)
-            return self._distinct_page(index, table, idx, sc, distinct, start, count)
-        idx, sc, total = index.rank(q, start, min(count, len(table.paths)), allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
-        return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
+            return self._host_page(s, self._search(q, s, len(s.table.paths)), min_score, distinct, distinct_depth, start, count)
+        return self._ranked_page(s, "rank", lambda fn, at, n, **more: fn(q, at, n, s.allowed, min_score, tracks=s.grouped, **more, **s.kw),
+                                 distinct, distinct_depth, start, count)[:2]
 
     @staticmethod
     def _distinct_args(distinct, distinct_depth):
         """The two arguments of a distinct page, checked before any GPU work -> (None or float, int)."""
         if distinct is None:
             return None, distinct_depth
-        distinct = float(distinct)
-        if distinct != distinct:
-            raise ValueError("distinct is NaN")
+        distinct = _cut_arg(float(distinct), "distinct")
         distinct_depth = int(distinct_depth)
         if not 1 <= distinct_depth <= _lib.DISTINCT_MAX_DEPTH:
             raise ValueError(f"distinct_depth must be in [1, {_lib.DISTINCT_MAX_DEPTH}]")
         return distinct, distinct_depth
-
-    @staticmethod
-    def _distinct_page(index, table: "_RowTable", idx, sc, distinct: float, start: int, count: int):
-        """Ranked answers on the device (1, depth) -> the page of the kept ones; only the page leaves the GPU."""
-        oi, os_, od, total = index.distinct_device(idx, sc, distinct, start, min(count, int(idx.shape[-1])))
-        rows, scores, dups = oi[0].cpu().tolist(), os_[0].cpu().numpy(), od[0].cpu().tolist()
-        return [(table.paths[r], float(v), int(d)) for r, v, d in zip(rows, scores, dups) if r >= 0], int(total[0])
-
-    @staticmethod
-    def _distinct_host(index, table: "_RowTable", kept, distinct: float, depth: int, start: int, count: int):
-        """A host-ranked list of (path, score) -> the page of its first `depth` answers thinned by their rows in the index."""
-        if not hasattr(index, "distinct"):
-            raise RuntimeError("this index cannot thin its answers")
-        head = kept[:depth]
-        if not head:
-            return [], 0
-        rows = np.array([table.row_of(p) for p, _ in head], np.int32)
-        oi, os_, od, total = index.distinct(rows, np.array([v for _, v in head], np.float32), distinct, start, min(count, len(head)))
-        return [(table.paths[r], float(v), int(d)) for r, v, d in zip(oi[0].tolist(), os_[0], od[0].tolist()) if r >= 0], int(total[0])
 
     def _stored_row(self, table: "_RowTable", path: str) -> int:
         """The row of a stored crop named by its key, or by the endpoint's '/<cam>/objects/<day>/<file>' under base_path."""
@@ -1002,64 +936,53 @@ class ObjectFinder:
         of it would miss.  A crop without a track id stands alone.  exclude="rows": the query crops are not answers; "track":
         no crop of the clicked track is ("rows" for a crop without a track id).  distinct / distinct_depth: as in `search_page`,
         the answers then are (path, score, dups)."""
-        where = row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        if start < 0 or count < 1:
-            raise ValueError("similar needs start >= 0 and count >= 1")
-        if min_score is not None and min_score != min_score:
-            raise ValueError("min_score is NaN")
+        where, kw = _row_kw(ts_range, classes)
+        start, count = _page_args("similar", start, count)
+        _cut_arg(min_score)
         distinct, distinct_depth = self._distinct_args(distinct, distinct_depth)
-        if exclude not in (None, "rows", "track"):
-            raise ValueError('exclude: None, "rows" or "track"')
-        if not self._has_rows(is_face):
-            print("No embeddings available.")
+        _choice_arg("exclude", exclude, (None, "rows", "track"))
+        store = self._store(is_face)
+        if store is None:
             return [], 0
-        index, table = self._index_and_table(is_face)
+        index, table = store
         row = self._stored_row(table, path)
-        if not hasattr(index, "rank_like"):
+        if not hasattr(index, "rank_like"):                 # behind the lookup, where it always stood: an unknown path is a KeyError on any index
             raise RuntimeError("this index cannot be queried by its stored rows")
         group, slot = table.group[row], table.slot[row]
+
+        def of_track():
+            return (np.asarray(table.group) == group) & (np.asarray(table.slot) == slot)
         rows = np.array([row], np.int64)
         if slot < 0:
             exclude = "rows" if exclude == "track" else exclude
         elif whole_track:
-            rows = pick_track_rows(row, np.flatnonzero((np.asarray(table.group) == group) & (np.asarray(table.slot) == slot)))
-        allowed = table.allowed(cam_name, timestamp)
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
+            rows = pick_track_rows(row, np.flatnonzero(of_track()))
+        s = self._scope(index, table, cam_name, timestamp, where, kw)
+        if s is None:
             return [], 0
-        grouped = any(table.truthy[g] for g in live)
-        if any(table.bad[g] for g in live):
+        if s.bad:
             # names the reference raises on: `search` with the clicked row's embedding raises the same way.  Where a row filter hides
             # those names from it, the answer is ranked on the host from the index's own scores.
             q = index.fetch(rows)
-            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q[list(rows).index(row)], is_face=is_face,
-                               ts_range=ts_range, classes=classes)
+            full = self._search(self._vector("query", q[list(rows).index(row)], False, index, is_face), s, len(table.paths))
             if len(rows) > 1 or exclude:
                 v = index.scores(q).max(axis=0)
                 ok = table.passing(where)
                 if exclude == "track":
-                    ok &= ~((np.asarray(table.group) == group) & (np.asarray(table.slot) == slot))
+                    ok &= ~of_track()
                 elif exclude == "rows":
                     ok[rows] = False
-                cand = [r for r in range(len(table.paths)) if allowed[table.group[r]] and ok[r]]
-                full = self._rank(table, cand, [float(v[r]) for r in cand], grouped)
-            kept = [r for r in full if min_score is None or not r[1] < min_score]
-            if distinct is not None:
-                return self._distinct_host(index, table, kept, distinct, distinct_depth, start, count)
-            return kept[start:start + count], len(kept)
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        if distinct is not None:
-            depth = min(distinct_depth, len(table.paths))
-            idx, sc, _ = index.rank_like_device(rows, 0, depth, allowed, min_score, tracks=grouped, exclude=exclude, with_total=False, **kw)
-            return self._distinct_page(index, table, idx, sc, distinct, start, count)
-        idx, sc, total = index.rank_like(rows, start, min(count, len(table.paths)), allowed, min_score, tracks=grouped, exclude=exclude, **kw)
-        return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0], int(total[0])
+                cand = _competing(s, ok)
+                full = self._rank(table, cand, [float(v[r]) for r in cand], s.grouped)
+            return self._host_page(s, full, min_score, distinct, distinct_depth, start, count)
+        return self._ranked_page(s, "rank_like", lambda fn, at, n, **more: fn(rows, at, n, s.allowed, min_score, tracks=s.grouped, exclude=exclude,
+                                                                             **more, **kw), distinct, distinct_depth, start, count)[:2]
 
-    def _compound_setup(self, terms, combine, cam_name, timestamp, is_face, min_score, exclude):
-        """What `compound` and `compound_timeline` share, everything checked before any GPU work -> (index, table, the keyword
-        arguments of `EmbeddingIndex.rank_terms` that say what is asked, order) or None when there is nothing to search.  The index
-        takes the vectors before the stored rows: order[t] is the position in `terms` of the index's term t."""
+    def _compound_setup(self, terms, combine, cam_name, timestamp, is_face, min_score, exclude, ts_range=None, classes=None):
+        """What `compound` and `compound_timeline` share, everything checked before any GPU work -> (scope, the keyword arguments of
+        `EmbeddingIndex.rank_terms` that say what is asked, row filter included, order) or None when there is nothing to search.  The index takes the
+        vectors before the stored rows: order[t] is the position in `terms` of the index's term t."""
+        where, kw = _row_kw(ts_range, classes)
         terms = [t if isinstance(t, Term) else Term(*t) for t in terms]
         if not 1 <= len(terms) <= _lib.TERMS_MAX:
             raise ValueError(f"compound needs 1 .. {_lib.TERMS_MAX} terms")
@@ -1072,41 +995,29 @@ class ObjectFinder:
                 raise ValueError("a require / reject Term needs a cut")
         if not any(t.role == "rank" for t in terms):
             raise ValueError("compound needs at least one rank Term")
-        if combine not in EmbeddingIndex.COMBINE:
-            raise ValueError('combine: "max", "min" or "sum"')
-        if exclude not in (None, "rows", "track"):
-            raise ValueError('exclude: None, "rows" or "track"')
-        if min_score is not None and min_score != min_score:
-            raise ValueError("min_score is NaN")
-        if not self._has_rows(is_face):
-            print("No embeddings available.")
+        _choice_arg("combine", combine, EmbeddingIndex.COMBINE)
+        _choice_arg("exclude", exclude, (None, "rows", "track"))
+        _cut_arg(min_score)
+        store = self._store(is_face, ("rank_terms",), "this index cannot rank compound questions")
+        if store is None:
             return None
-        index, table = self._index_and_table(is_face)
-        if not hasattr(index, "rank_terms"):
-            raise RuntimeError("this index cannot rank compound questions")
+        index, table = store
         vec_at = [i for i, t in enumerate(terms) if t.path is None]
         row_at = [i for i, t in enumerate(terms) if t.path is not None]
         rows = np.array([self._stored_row(table, terms[i].path) for i in row_at], np.int64)
-        for i in vec_at:
-            if terms[i].embedding is not None and np.size(as_numpy(terms[i].embedding)) != index.dim:
-                raise ValueError(f"a Term's embedding has {np.size(as_numpy(terms[i].embedding))} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
-        allowed = table.allowed(cam_name, timestamp)
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
+        given = {i: self._vector("a Term's embedding", terms[i].embedding, False, index, is_face) for i in vec_at if terms[i].embedding is not None}
+        s = self._scope(index, table, cam_name, timestamp, where, kw, no_host_ranking="compound search")
+        if s is None:
             return None
-        for g in live:
-            if table.bad[g]:                        # names the reference raises on: no host ranking is grown for this call
-                raise ValueError(f"compound search cannot rank the folder {table.dirs[g]}: it holds crop names that do not parse")
-        vecs = [np.asarray(as_numpy(self.model._encode_text(terms[i].text).numpy() if terms[i].text is not None else terms[i].embedding),
-                           np.float32).reshape(-1) for i in vec_at]
+        vecs = [given[i] if i in given else self._vector(None, terms[i].text, True, index, is_face) for i in vec_at]
         order = vec_at + row_at
         ranked = [int(r) for r, i in zip(rows, row_at) if terms[i].role == "rank"]
         if exclude == "track" and ranked and all(table.slot[r] < 0 for r in ranked):
             exclude = "rows"                        # crops without a track id stand alone, as in `similar`
         ask = dict(q=np.stack(vecs) if vecs else None, rows=rows if rows.size else None, roles=[terms[i].role for i in order],
-                   weights=[terms[i].weight for i in order], cuts=[terms[i].cut for i in order], combine=combine, allowed=allowed,
-                   min_score=min_score, tracks=any(table.truthy[g] for g in live), exclude=exclude)
-        return index, table, ask, order
+                   weights=[terms[i].weight for i in order], cuts=[terms[i].cut for i in order], combine=combine, allowed=s.allowed,
+                   min_score=min_score, tracks=s.grouped, exclude=exclude, **kw)
+        return s, ask, order
 
     def compound(self, terms, start=0, count=100, combine="max", cam_name=None, timestamp=None, is_face=False, min_score=None, ts_range=None,
                  classes=None, exclude=None, explain=False, distinct=None, distinct_depth=1024):
@@ -1120,44 +1031,31 @@ class ObjectFinder:
         score (max / min: the first one attaining it; sum: the one with the largest product).  An unknown path raises KeyError;
         a folder with crop names the reference raises on raises ValueError.  One `EmbeddingIndex.rank_terms` call: only `count`
         answers leave the GPU, no score matrix."""
-        where = row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        if start < 0 or count < 1:
-            raise ValueError("compound needs start >= 0 and count >= 1")
+        start, count = _page_args("compound", start, count)
         distinct, distinct_depth = self._distinct_args(distinct, distinct_depth)
-        setup = self._compound_setup(terms, combine, cam_name, timestamp, is_face, min_score, exclude)
+        setup = self._compound_setup(terms, combine, cam_name, timestamp, is_face, min_score, exclude, ts_range, classes)
         if setup is None:
             return [], 0
-        index, table, ask, order = setup
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        if distinct is not None:
-            depth = min(distinct_depth, len(table.paths))
-            out = index.rank_terms_device(start=0, count=depth, with_total=False, which=explain, **ask, **kw)
-            res, total = self._distinct_page(index, table, out[0], out[1], distinct, start, count)
-            if explain:                             # a row answers once: the term of a kept answer is that of its row in the list walked
-                term_of = dict(zip(out[0][0].cpu().tolist(), out[3][0].cpu().tolist()))
-                res = [r + (order[term_of[table.row_of(r[0])]],) for r in res]
-            return res, total
-        out = index.rank_terms(start=start, count=min(count, len(table.paths)), which=explain, **ask, **kw)
-        res = [(table.paths[r], float(v)) for r, v in zip(out[0][0].tolist(), out[1][0]) if r >= 0]
-        if explain:
+        s, ask, order = setup
+        res, total, out = self._ranked_page(s, "rank_terms", lambda fn, at, n, **more: fn(start=at, count=n, which=explain, **more, **ask),
+                                            distinct, distinct_depth, start, count)
+        if explain and distinct is None:
             res = [r + (order[w],) for r, w in zip(res, out[3][0].tolist())]
-        return res, int(out[2][0])
+        elif explain:                               # a row answers once: the term of a kept answer is that of its row in the list walked
+            term_of = dict(zip(out[0][0].cpu().tolist(), out[3][0].cpu().tolist()))
+            res = [r + (order[term_of[s.table.row_of(r[0])]],) for r in res]
+        return res, total
 
     def compound_timeline(self, terms, t0=0, bin_seconds=3600, n_bins=24, combine="max", cam_name=None, timestamp=None, is_face=False,
                           min_score=None, ts_range=None, classes=None, exclude=None):
         """How the results of `compound` (same terms and arguments) spread over the day -> (counts (n_bins,) int64, total), binned as
         `timeline` bins them; `total` is `compound`'s.  One `EmbeddingIndex.timeline_terms` call."""
-        where = row_filter(ts_range, classes)
-        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
-        if bin_seconds < 1 or not 1 <= n_bins <= 4096:
-            raise ValueError("compound_timeline needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
-        setup = self._compound_setup(terms, combine, cam_name, timestamp, is_face, min_score, exclude)
+        t0, bin_seconds, n_bins = _bin_args("compound_timeline", t0, bin_seconds, n_bins)
+        setup = self._compound_setup(terms, combine, cam_name, timestamp, is_face, min_score, exclude, ts_range, classes)
         if setup is None:
             return np.zeros(n_bins, np.int64), 0
-        index, table, ask, _ = setup
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        c, total = index.timeline_terms(t0, bin_seconds, n_bins, **ask, **kw)
+        s, ask, _ = setup
+        c, total = s.index.timeline_terms(t0, bin_seconds, n_bins, **ask)
         return c[0], int(total[0])
 
     @staticmethod
@@ -1175,46 +1073,35 @@ class ObjectFinder:
             raise ValueError("a side of together needs exactly one of text, path and embedding")
         return "embedding"
 
-    def _together_setup(self, a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners):
-        """What `together` and `together_timeline` share, everything checked before any GPU work -> (index, table, the keyword
-        arguments of `EmbeddingIndex.rank_near` that say what is asked) or None when there is nothing to search."""
+    def _together_setup(self, a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners, ts_range=None, classes=None,
+                        with_classes=None):
+        """What `together` and `together_timeline` share, everything checked before any GPU work -> (scope, the keyword arguments of
+        `EmbeddingIndex.rank_near` that say what is asked, row filters included) or None when there is nothing to search."""
+        where, kw = _row_kw(ts_range, classes)
+        if row_filter(None, with_classes) is not None:
+            kw["b_classes"] = with_classes
         kinds = [self._together_source(a), self._together_source(b)]
-        if value not in _lib.NEAR_VALUE:
-            raise ValueError('value: "a" or "min"')
+        _choice_arg("value", value, _lib.NEAR_VALUE)
         within, partners = int(within), int(partners)
         if not 0 <= within < 1 << 31:
             raise ValueError("within: seconds in [0, 2^31)")
         if not 1 <= partners <= _lib.NEAR_MAX_PARTNERS:
             raise ValueError(f"partners must be in [1, {_lib.NEAR_MAX_PARTNERS}]")
         for cut in (min_score, min_partner):
-            if cut is not None and cut != cut:
-                raise ValueError("min_score / min_partner is NaN")
-        if not self._has_rows(is_face):
-            print("No embeddings available.")
+            _cut_arg(cut, "min_score / min_partner")
+        store = self._store(is_face, ("rank_near",), "this index cannot join two questions")
+        if store is None:
             return None
-        index, table = self._index_and_table(is_face)
-        if not hasattr(index, "rank_near"):
-            raise RuntimeError("this index cannot join two questions")
+        index, table = store
         sides = []
         for x, kind in zip((a, b), kinds):
             src = getattr(x, kind) if isinstance(x, Term) else x
-            if kind == "path":
-                sides.append(self._stored_row(table, src))
-            else:
-                v = np.asarray(as_numpy(self.model._encode_text(src).numpy() if kind == "text" else src), np.float32).reshape(-1)
-                if v.size != index.dim:
-                    raise ValueError(f"a side of together has {v.size} dimensions, the {'face' if is_face else 'crop'} index {index.dim}")
-                sides.append(v)
-        allowed = table.allowed(cam_name, timestamp)
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
+            sides.append(self._stored_row(table, src) if kind == "path" else self._vector("a side of together", src, kind == "text", index, is_face))
+        s = self._scope(index, table, cam_name, timestamp, where, kw, no_host_ranking="together")
+        if s is None:
             return None
-        for g in live:
-            if table.bad[g]:                        # names the reference raises on: no host ranking is grown for this call
-                raise ValueError(f"together cannot rank the folder {table.dirs[g]}: it holds crop names that do not parse")
-        ask = dict(a=sides[0], b=sides[1], within=within, partners=partners, cut_b=min_partner, value=value, allowed=allowed, min_score=min_score,
-                   tracks=any(table.truthy[g] for g in live))
-        return index, table, ask
+        return s, dict(a=sides[0], b=sides[1], within=within, partners=partners, cut_b=min_partner, value=value, allowed=s.allowed, min_score=min_score,
+                       tracks=s.grouped, **kw)
 
     def together(self, a, b, within=30, start=0, count=100, cam_name=None, timestamp=None, is_face=False, min_score=0.21, min_partner=0.21, value="min",
                  ts_range=None, classes=None, with_classes=None, partners=_lib.NEAR_DEFAULT_PARTNERS):
@@ -1228,19 +1115,13 @@ class ObjectFinder:
         the smaller of its own score for `a` and its partner's for `b`; "a": its own alone.  Folders, min_score, ts_range / classes
         (for `a`) and grouping per track are `search_page`'s.  "partners": the crops that qualified as partners, "partners_left":
         those beyond the cap, which took no part.  One `EmbeddingIndex.rank_near` call: only the page leaves the GPU."""
-        where = row_filter(ts_range, classes)
-        where_b = row_filter(None, with_classes)
-        start, count = int(start), int(count)
-        if start < 0 or count < 1:
-            raise ValueError("together needs start >= 0 and count >= 1")
-        setup = self._together_setup(a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners)
+        start, count = _page_args("together", start, count)
+        setup = self._together_setup(a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners, ts_range, classes, with_classes)
         if setup is None:
             return [], {"total": 0, "partners": 0, "partners_left": 0}
-        index, table, ask = setup
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        if where_b is not None:
-            kw["b_classes"] = with_classes
-        idx, sc, total, pr, ps, n_partners = index.rank_near(start=start, count=min(count, len(table.paths)), **ask, **kw)
+        s, ask = setup
+        table = s.table
+        idx, sc, total, pr, ps, n_partners = s.index.rank_near(start=start, count=min(count, len(table.paths)), **ask)
         res = [(table.paths[r], float(v), table.paths[p], float(w), int(table.ts[p]) - int(table.ts[r]))
                for r, v, p, w in zip(idx[0].tolist(), sc[0], pr[0].tolist(), ps[0]) if r >= 0]
         return res, {"total": int(total[0]), "partners": min(n_partners, ask["partners"]), "partners_left": max(n_partners - ask["partners"], 0)}
@@ -1249,44 +1130,32 @@ class ObjectFinder:
                           min_partner=0.21, value="min", ts_range=None, classes=None, with_classes=None, partners=_lib.NEAR_DEFAULT_PARTNERS):
         """How the results of `together` (same question) spread over the day -> (counts (n_bins,) int64, total), binned as `timeline`
         bins them; `total` is `together`'s.  One `EmbeddingIndex.timeline_near` call."""
-        where = row_filter(ts_range, classes)
-        where_b = row_filter(None, with_classes)
-        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
-        if bin_seconds < 1 or not 1 <= n_bins <= 4096:
-            raise ValueError("together_timeline needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
-        setup = self._together_setup(a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners)
+        t0, bin_seconds, n_bins = _bin_args("together_timeline", t0, bin_seconds, n_bins)
+        setup = self._together_setup(a, b, within, cam_name, timestamp, is_face, min_score, min_partner, value, partners, ts_range, classes, with_classes)
         if setup is None:
             return np.zeros(n_bins, np.int64), 0
-        index, table, ask = setup
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        if where_b is not None:
-            kw["b_classes"] = with_classes
-        c, total, _ = index.timeline_near(t0=t0, bin_seconds=bin_seconds, n_bins=n_bins, **ask, **kw)
+        s, ask = setup
+        c, total, _ = s.index.timeline_near(t0=t0, bin_seconds=bin_seconds, n_bins=n_bins, **ask)
         return c[0], int(total[0])
 
     def search(self, query=None, top_k=10, cam_name=None, timestamp=None, text_embedding=None, is_face=False, ts_range=None, classes=None):
         """:356-390.  ts_range / classes: the row filter of `search_page`; with one given the device ranks (`EmbeddingIndex.rank`),
         and grouping per track is decided as without it, from the track ids of all crops in the allowed folders."""
-        where = row_filter(ts_range, classes)
-        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
-        if setup is None:
-            return []
-        q, index, table, allowed = setup
-        live = np.flatnonzero(allowed)
-        if live.size == 0 or top_k <= 0:
-            return []
-        exact_loop = any(table.bad[g] for g in live)
-        grouped = any(table.truthy[g] for g in live)
+        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face, ts_range, classes)
+        return [] if setup is None or top_k <= 0 else self._search(*setup, top_k)
+
+    def _search(self, q, s: _Scope, top_k):
+        """`search` inside a scope; with top_k = every row, the whole list for the questions that fall back to ranking on the host"""
+        index, table, allowed, grouped, exact_loop, where, kw = s.index, s.table, s.allowed, s.grouped, s.bad, s.where, s.kw
         if where is None and grouped and not exact_loop and top_k <= 1024 and hasattr(index, "search_tracks"):
             # the device reduces per track id and selects (one call, exact whatever the data: thousands of crops of one track, ties)
             idx, sc = index.search_tracks(q, int(top_k), allowed)
-            return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
+            return _answers(table, idx[0].tolist(), sc[0])
         if not exact_loop and hasattr(index, "rank"):
             # top_k > 1024, or no truthy track id among the allowed crops (the reference does not group then): the device ranks the
             # whole order and hands back its head.  At most one answer per row: "everything" (top_k = 10**9) allocates no more.
-            kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
             idx, sc, _ = index.rank(q, 0, min(int(top_k), len(table.paths)), allowed, None, tracks=grouped, **kw)
-            return [(table.paths[r], float(v)) for r, v in zip(idx[0].tolist(), sc[0]) if r >= 0]
+            return _answers(table, idx[0].tolist(), sc[0])
         # An index without `rank` (no track ids among the allowed rows, top_k > 1024 or no search_tracks either):
         # GPU: filtered top-K' (one HBM pass + radix select); host: the reference's best-per-track-id tail on K' rows.
         # The answer is exact once the top_k-th result scores strictly above the weakest candidate (no unseen row can
@@ -1312,13 +1181,9 @@ class ObjectFinder:
                 break
             kk = min(1024, kk * 4)
         scores = index.scores(q)[0]                         # the whole score vector, ranked like the reference does it
-        passing = table.passing(where)
-        rows = [r for r in range(len(table.paths)) if allowed[table.group[r]] and passing[r]]
+        rows = _competing(s)
         if exact_loop:                                      # names the reference itself would raise on: let it raise the same way
-            for r in rows:
-                fn = os.path.basename(table.paths[r])
-                if "_" in fn:
-                    event_img_info(fn.split(".jpg")[0])
+            _raise_as_reference(table, rows)
         return self._rank(table, rows, [float(scores[r]) for r in rows], grouped)[:top_k]
 
     def timeline(self, query=None, t0=0, bin_seconds=3600, n_bins=24, cam_name=None, timestamp=None, text_embedding=None, is_face=False,
@@ -1328,32 +1193,35 @@ class ObjectFinder:
         result's crop into bin (ts - t0) // bin_seconds.  A result whose name carries no ts, or whose bin lies outside
         [0, n_bins), is counted in `total` only; `total` is `search_page`'s.  One `EmbeddingIndex.timeline` call: n_bins counters
         leave the GPU, no scores."""
-        where = row_filter(ts_range, classes)
-        t0, bin_seconds, n_bins = int(t0), int(bin_seconds), int(n_bins)
-        if bin_seconds < 1 or not 1 <= n_bins <= 4096:
-            raise ValueError("timeline needs bin_seconds >= 1 and 1 <= n_bins <= 4096")
-        if min_score is not None and min_score != min_score:
-            raise ValueError("min_score is NaN")
+        t0, bin_seconds, n_bins = _bin_args("timeline", t0, bin_seconds, n_bins)
+        _cut_arg(min_score)
         counts = np.zeros(n_bins, np.int64)
-        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face)
+        setup = self._search_setup(query, cam_name, timestamp, text_embedding, is_face, ts_range, classes)
         if setup is None:
             return counts, 0
-        q, index, table, allowed = setup
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
-            return counts, 0
-        if any(table.bad[g] for g in live) or not hasattr(index, "timeline"):
-            full = self.search(top_k=len(table.paths), cam_name=cam_name, timestamp=timestamp, text_embedding=q, is_face=is_face,
-                               ts_range=ts_range, classes=classes)
-            kept = [r for r in full if min_score is None or not r[1] < min_score]
+        q, s = setup
+        if s.bad or not hasattr(s.index, "timeline"):
+            kept = _above(self._search(q, s, len(s.table.paths)), min_score)
             for path, _ in kept:
                 ts = _RowTable.name_attrs(path)[0]
                 if ts != _lib.ROW_NO_TS and 0 <= (ts - t0) // bin_seconds < n_bins:
                     counts[(ts - t0) // bin_seconds] += 1
             return counts, len(kept)
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        c, total = index.timeline(q, t0, bin_seconds, n_bins, allowed, min_score, tracks=any(table.truthy[g] for g in live), **kw)
+        c, total = s.index.timeline(q, t0, bin_seconds, n_bins, s.allowed, min_score, tracks=s.grouped, **s.kw)
         return c[0], int(total[0])
+
+    def _digest_setup(self, name, needs, orders, cam_name, timestamp, is_face, same_at, start, count, ts_range, classes, by):
+        """What `digest` and `seen_before` share -> (scope or None when there is nothing to walk, same_at, start, count).  Names the
+        reference raises on raise the same way, as `search` lets them, where they are among the crops that compete."""
+        where, kw = _row_kw(ts_range, classes)
+        start, count = _page_args(name, start, count)
+        same_at = _cut_arg(float(same_at), "same_at")
+        _choice_arg("by", by, orders)
+        store = self._store(is_face, needs, "this index cannot summarise its rows")
+        s = None if store is None else self._scope(*store, cam_name, timestamp, where, kw)
+        if s is not None and s.bad:
+            _raise_as_reference(s.table, _competing(s))
+        return s, same_at, start, count
 
     def digest(self, cam_name=None, timestamp=None, is_face=False, same_at=0.9, start=0, count=100, ts_range=None, classes=None, by="count"):
         """"What was on this camera today?": every distinct object among the stored crops of the allowed folders once ->
@@ -1365,36 +1233,12 @@ class ObjectFinder:
         Folders and row filter are `search_page`'s; no query, no model.  "objects" is the number of entries there are (at most
         1024 in one call), "crops" the crops that competed, "left_over" those that matched none of 1024 objects.  A *.jpg name the
         reference cannot parse raises ValueError where `search` would raise on it: among the crops that compete."""
-        where = row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        if start < 0 or count < 1:
-            raise ValueError("digest needs start >= 0 and count >= 1")
-        same_at = float(same_at)
-        if same_at != same_at:
-            raise ValueError("same_at is NaN")
-        if by not in EmbeddingIndex.DIGEST_BY:
-            raise ValueError('by: "count" or "first"')
-        empty = ([], {"objects": 0, "crops": 0, "left_over": 0})
-        if not self._has_rows(is_face):
-            print("No embeddings available.")
-            return empty
-        index, table = self._index_and_table(is_face)
-        if not hasattr(index, "digest"):
-            raise RuntimeError("this index cannot summarise its rows")
-        allowed = table.allowed(cam_name, timestamp)
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
-            return empty
-        if any(table.bad[g] for g in live):                 # names the reference raises on: raise the same way, as `search` does
-            passing = table.passing(where)
-            for r in range(len(table.paths)):
-                fn = os.path.basename(table.paths[r])
-                if allowed[table.group[r]] and passing[r] and "_" in fn:
-                    event_img_info(fn.split(".jpg")[0])
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        rows, counts, t0, t1, totals = index.digest(same_at, start, min(count, _lib.DIGEST_MAX_LEADERS), allowed, by=by, **kw)
-        none = _lib.ROW_NO_TS
-        out = [(table.paths[r], int(c), None if a == none else int(a), None if b == none else int(b))
+        s, same_at, start, count = self._digest_setup("digest", ("digest",), EmbeddingIndex.DIGEST_BY, cam_name, timestamp, is_face, same_at, start, count,
+                                                      ts_range, classes, by)
+        if s is None:
+            return [], {"objects": 0, "crops": 0, "left_over": 0}
+        rows, counts, t0, t1, totals = s.index.digest(same_at, start, min(count, _lib.DIGEST_MAX_LEADERS), s.allowed, by=by, **s.kw)
+        out = [(s.table.paths[r], int(c), _ts_or_none(a), _ts_or_none(b))
                for r, c, a, b in zip(rows.tolist(), counts.tolist(), t0.tolist(), t1.tolist()) if r >= 0]
         return out, {"objects": int(totals[0]), "crops": int(totals[1]), "left_over": int(totals[2])}
 
@@ -1424,36 +1268,14 @@ class ObjectFinder:
         history).  by="new": objects never seen before first, then most crops today, then order of appearance; "count" / "first":
         `digest`'s orders.  Entries start .. start+count-1 come back.  "new" counts the objects with seen_before == 0,
         "history_crops" the history crops that competed."""
-        where = row_filter(ts_range, classes)
-        start, count = int(start), int(count)
-        if start < 0 or count < 1:
-            raise ValueError("seen_before needs start >= 0 and count >= 1")
-        same_at = float(same_at)
-        if same_at != same_at:
-            raise ValueError("same_at is NaN")
-        if by not in self.SEEN_BY:
-            raise ValueError('by: "new", "count" or "first"')
-        empty = ([], {"objects": 0, "new": 0, "crops": 0, "left_over": 0, "history_crops": 0})
-        if not self._has_rows(is_face):
-            print("No embeddings available.")
-            return empty
-        index, table = self._index_and_table(is_face)
-        if not hasattr(index, "digest") or not hasattr(index, "sightings"):
-            raise RuntimeError("this index cannot summarise its rows")
-        allowed = table.allowed(cam_name, timestamp)
-        live = np.flatnonzero(allowed)
-        if live.size == 0:
-            return empty
-        if any(table.bad[g] for g in live):                 # names the reference raises on: raise the same way, as `digest` does
-            passing = table.passing(where)
-            for r in range(len(table.paths)):
-                fn = os.path.basename(table.paths[r])
-                if allowed[table.group[r]] and passing[r] and "_" in fn:
-                    event_img_info(fn.split(".jpg")[0])
-        kw = {} if where is None else {"ts_range": ts_range, "classes": classes}
-        rows, counts, t0, t1, totals = index.digest(same_at, 0, _lib.DIGEST_MAX_LEADERS, allowed, by="first", **kw)
+        s, same_at, start, count = self._digest_setup("seen_before", ("digest", "sightings"), self.SEEN_BY, cam_name, timestamp, is_face, same_at, start,
+                                                      count, ts_range, classes, by)
+        if s is None:
+            return [], {"objects": 0, "new": 0, "crops": 0, "left_over": 0, "history_crops": 0}
+        index, table, allowed = s.index, s.table, s.allowed
+        rows, counts, t0, t1, totals = index.digest(same_at, 0, _lib.DIGEST_MAX_LEADERS, allowed, by="first", **s.kw)
         lead = [r for r in rows.tolist() if r >= 0]
-        n, none = len(lead), _lib.ROW_NO_TS
+        n = len(lead)
         history = (np.asarray(table.allowed(history_cam, None)) != 0) & (np.asarray(allowed) == 0)
         seen = np.zeros(n, np.int64)
         best_row, best_score = np.full(n, -1, np.int64), np.full(n, -np.inf, np.float32)
@@ -1468,7 +1290,7 @@ class ObjectFinder:
             hit = [where_of[g] for g in np.flatnonzero(np.asarray(groups[i])).tolist()]
             days = {d for _, d in hit if d is not None}
             b = int(best_row[i])
-            entries.append((table.paths[r], int(counts[i]), None if t0[i] == none else int(t0[i]), None if t1[i] == none else int(t1[i]),
+            entries.append((table.paths[r], int(counts[i]), _ts_or_none(t0[i]), _ts_or_none(t1[i]),
                             int(seen[i]), len(days), sorted({c for c, _ in hit if c is not None}), max(days) if days else None,
                             table.paths[b] if b >= 0 else None, float(best_score[i]) if b >= 0 else None))
         order = list(range(n))                                                # by="first": the digest's own order
