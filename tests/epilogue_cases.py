@@ -290,6 +290,8 @@ _DEEP_ROUTES = [
     # the wide kernels' plain GEMM at CLIP's K, AdaFace's shortcut conv on the eight-wave kernel
     ("clip", "big128", "1x1_k1024", 0, None, False), ("clip", "persist", "1x1_k1024", 0, None, False),
     ("adaface", "one_tile", "1x1s2_k256", 0, None, False),
+    # CLIP's text tower at B = 64 (M = 4928: 180 tiles of 256 x 256): the in_proj GEMM without activation, one tile per block
+    ("clip", "one_tile", "1x1_k1024", 0, None, False),
 ]
 
 

@@ -95,7 +95,7 @@ def _clip_text(weights, clip_handles, dtype):
 
 
 PLANS = [("adaface", _adaface, (1, 3, 12, 40, 256)), ("blazeface", _blazeface, (1, 32)),
-         ("clip_image", _clip_image, (1, 8, 64)), ("clip_text", _clip_text, (1, 8))]
+         ("clip_image", _clip_image, (1, 8, 64, 255)), ("clip_text", _clip_text, (1, 8, 64))]     # 255: bench.py's batch
 assert tuple(p[0] for p in PLANS) == prc.PLANS
 
 

@@ -15,6 +15,7 @@ Tolerances (BASELINE.json north_star: "box coords/classes within 1e-3"):
 import ctypes as C
 import contextlib
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -93,7 +94,7 @@ TOL = {"f32": 2e-5, "f16": 3e-3, "bf16": 2e-2}            # max |err| / max |ref
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_layer_matches_torch(case, dtype):
     _, B, Cin, H, W_, Cout, k, stride, groups = case
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000)
     x = torch.randn(B, Cin, H, W_, generator=g)
     w = torch.randn(Cout, Cin // groups, k, k, generator=g) / (Cin // groups * k * k) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
@@ -110,7 +111,7 @@ def test_conv_layer_matches_torch(case, dtype):
 @pytest.mark.parametrize("case", SPECIAL_CASES, ids=[c[0] for c in SPECIAL_CASES])
 def test_specialised_3x3_kernels_match_torch(case, dtype):
     _, B, Cin, H, W_, Cout, variant = case
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000)
     x = torch.randn(B, Cin, H, W_, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
@@ -186,7 +187,7 @@ def test_split_weight_conv_matches_torch(case):
     everywhere (f32 accumulation order only moves a result across an f16 rounding boundary once in a few hundred), which plain
     f16 weights (11 bits) miss on a large share of the outputs."""
     _, B, Cin, H, W_, Cout, k, stride, groups, variant = case
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000)
     x = torch.randn(B, Cin, H, W_, generator=g)
     w = torch.randn(Cout, Cin // groups, k, k, generator=g) / (Cin // groups * k * k) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
@@ -225,7 +226,7 @@ def test_stream_1x1_equals_generic(case, act, dtype):
     _, B, Cin, H, W_, Cout = case
     if dtype == "f16s" and Cin == 512:
         pytest.skip("two planes of 512 channels exceed the register-resident weight budget: not an instantiated shape")
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000 + act)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000 + act)
     x = torch.randn(B, Cin, H, W_, generator=g)
     w = torch.randn(Cout, Cin, 1, 1, generator=g) / Cin ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
@@ -261,7 +262,7 @@ def test_tile64_3x3_equals_generic(case, act, dtype, width):
     """Variant 12 (weights resident in LDS in fragment order, double-buffered 10 x 34 patches, hand-pipelined taps, accumulator rows permuted
     for 16-byte stores) against torch and, bit for bit, against the generic tile kernel: same MFMA, same (tap, channel) walk, same epilogue."""
     _, B, H, W_ = case
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000 + act)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000 + act)
     x = torch.randn(B, 64, H, W_, generator=g)
     w = torch.randn(64, 64, 3, 3, generator=g) / 24.0
     b = torch.randn(64, generator=g) * 0.1
@@ -957,7 +958,7 @@ BIG_CASES = [
 def test_big_tile_kernel_matches_torch(case, dtype, variant):
     """256x256-tile, four-wave, single-barrier kernel (variant 5) against torch, with and without activation/bias."""
     _, B, Cin, H, W_, Cout, k = case
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000)
     x = torch.randn(B, Cin, H, W_, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
@@ -986,7 +987,7 @@ def test_persistent_eight_wave_kernel_matches_torch(case, dtype):
     from clearcam_amd import _lib as lib_
     L = lib_.lib()
     _, B, Cin, H, W_, Cout, k = case
-    g = torch.Generator().manual_seed(hash(case[0]) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(case[0].encode()) % 1000)
     x = torch.randn(B, Cin, H, W_, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
